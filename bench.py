@@ -26,6 +26,14 @@ over the ranks, ONE all-gather of the slot-major score records (exact int64 sums
 rank.  ``--runner sharded`` (BASELINE config 4's wording): contact rows split over the ranks, one all-reduce of the
 exact partial sums per move.  Both are bit-identical to one GPU for any N ("strong" scaling: one chain, split N ways).
 
+A plain run does only what the headline needs: set-up, warm-up, the timed steps, the outputs (``--dump-outputs DIR``) and
+the line.  ``--full`` adds everything else the line used to carry: hipEvent timers around the scoring kernels and the
+roofline object, the draw alone, the maintained-likelihood self-check, the reference's one-call-per-move loop, the
+nuisance-on loop, the settled parameters, the bombed and late shapes, and the CPU baseline checked move by move against
+the oracle.  ``--dump-outputs DIR`` writes, right after the timed steps, what the timed call returned for the moves of
+its last step and the genome state it left, as float64 ``DIR/<name>.npy`` (fixed inputs: the same arguments draw the same
+trajectory), so that two builds can be compared output for output.
+
 Prints ONE JSON line (rank 0).
 """
 import argparse
@@ -174,6 +182,33 @@ def secondary_shape(make_sampler, prob, n_neighbours, bomb, n_warm, n_moves, wha
     return out
 
 
+# the per-move fields of the records step_sampler_batch returns that are results of the model (step_sampler's 6-tuple and the size of
+# the candidate list); n_slice, n_evals and bytes_min count the work a build did, not what it computed
+DUMP_FIELDS = ("o", "dist", "mean_len", "op_sampled", "id_f_sampled", "n_contigs", "n_candidates")
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path, res, cands, state):
+    """--dump-outputs: the records and candidate lists of the last step's moves and the genome state (17 fields per bin) the timed
+    call left, float64.  Past DUMP_MAX_BYTES a fixed sample (seed 0, its own generator) of the moves and of the bins is kept."""
+    arrays = {k: np.asarray(res[k], np.float64) for k in DUMP_FIELDS}
+    arrays["candidates"] = np.asarray(cands, np.float64)
+    arrays["genome_state"] = np.asarray(state, np.float64)
+    total = sum(v.nbytes for v in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        rs = np.random.RandomState(0)
+        keep = 0.8 * DUMP_MAX_BYTES / float(total)  # (room for the two index arrays)
+        n_mv, n_bins = len(res), state.shape[1]
+        mv = np.sort(rs.choice(n_mv, max(1, int(n_mv * keep)), replace=False))
+        bins = np.sort(rs.choice(n_bins, max(1, int(n_bins * keep)), replace=False))
+        arrays = {k: (v[:, bins] if k == "genome_state" else v[mv]) for k, v in arrays.items()}
+        arrays["sample_moves"] = mv.astype(np.float64)
+        arrays["sample_bins"] = bins.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), v)
+
+
 def spawn_workers(a):
     """--gpus N without a launcher: start N ranks as children of this process (which never touches the GPU)."""
     import socket
@@ -215,7 +250,14 @@ def main():
     ap.add_argument("--cpu-budget", type=float, default=45.0, help="seconds of the oracle's timed sample (a fifth on one thread, the rest on 16)")
     ap.add_argument("--nuisance-moves", type=int, default=150, help="moves of the nuisance-on loop timed after the run (0: skip)")
     ap.add_argument("--nuisance-settle", type=int, default=2400, help="untimed (move, step) pairs in front of a second, settled measurement (0: skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure and check everything besides the headline (kernel timers and roofline, reference loop, nuisance-on loop, settled "
+                         "parameters, bombed / late shapes, CPU baseline against the oracle); the options above that tune those legs act only here")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed call returned for the moves of its last step, and the genome state it left, as float64 DIR/<name>.npy")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         spawn_workers(a)  # does not return
@@ -293,14 +335,15 @@ def main():
     if n_warm:
         first_res, first_cands = run(frags[:n_warm])
         first_res, first_cands = first_res[:96].copy(), np.array(first_cands[:96])
-    # hipEvent pairs around the two scoring kernels (k_screen, k_score_list) on the library's stream, every 4th launch: an event
-    # record between two kernels of a stream costs ~6 us of idle queue, four of them per batch were 4 % of the timed region
-    # (a short call -- the driver's 480 moves are ~15 launches of the dominant kernel, of 9 to 48 slots each since round 5's window rule --
-    # times every launch: four samples of launches that different read 0.093 - 0.114 for the same kernel; --timer-sampling N fixes it)
-    t_every = a.timer_sampling if a.timer_sampling > 0 else (1 if n_moves <= 1200 else 4)
-    s.ctx.set_timer_sampling(t_every)
-    s.ctx.reset_timers(1 | (((1 << 2) | (1 << 10)) << 1))
-    batches_before = s.ctx.batch_stats()["batches"] if (world == 1 or replicas) else 0
+    if a.full:
+        # hipEvent pairs around the two scoring kernels (k_screen, k_score_list) on the library's stream, every 4th launch: an event
+        # record between two kernels of a stream costs ~6 us of idle queue, four of them per batch were 4 % of the timed region
+        # (a short call -- the driver's 480 moves are ~15 launches of the dominant kernel, of 9 to 48 slots each since round 5's window rule --
+        # times every launch: four samples of launches that different read 0.093 - 0.114 for the same kernel; --timer-sampling N fixes it)
+        t_every = a.timer_sampling if a.timer_sampling > 0 else (1 if n_moves <= 1200 else 4)
+        s.ctx.set_timer_sampling(t_every)
+        s.ctx.reset_timers(1 | (((1 << 2) | (1 << 10)) << 1))
+        batches_before = s.ctx.batch_stats()["batches"] if (world == 1 or replicas) else 0
     if dist is not None:
         dist.barrier()
     torch.cuda.synchronize()
@@ -314,6 +357,40 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device="cpu" if one_device else "cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if rank == 0 and a.dump_outputs:  # before anything of --full moves the genome on
+        dump_outputs(a.dump_outputs, res[-mps:], np.asarray(cands)[-mps:], s.ctx.download_state())
+
+    out = {
+        "metric": "MCMC moves/s (accepted+rejected) at fixed n_frags x nnz",
+        "value": (world if replicas else 1) * n_moves / elapsed,  # replicas: every rank ran its own n_moves
+        "unit": "moves/s",
+        "n_gpus": dist.get_world_size() if dist is not None else 1,
+        "steps": a.steps,
+        "warmup": a.warmup,
+        "ms_per_step": 1e3 * elapsed / a.steps,
+        "higher_is_better": True,
+        "scaling": "weak" if replicas else "strong",
+        "vs_baseline": None,
+        "dtype": "f32 screening tier with a rigorous bound (every column) + f64 terms (f32 inputs) for the contenders / exact i64 fixed-point sums",
+        "data": "synthetic",
+        "config": {"workload": "synthetic Hi-C %s (%d sub-frags), level 4, %d neighbours, nuisance sampling off%s" % (
+            prob_name(prob), prob.n_sub_frags, a.neighbours, "" if a.params == "synthetic" else ", P(s) parameters of a settled chain"), "name": a.config, "seed": a.seed,
+            "step": "one batch of %d moves (step_sampler calls)" % mps, "moves_per_step": mps, "moves_timed": n_moves,
+            "moves_warmup": n_warm,
+            "parallelism": "1 GPU" if world == 1 else ("replicas only: %d independent chains, one per GPU, no data-path collective" % world) if replicas else (
+                "batch slots split over %d ranks, all-gather of score records" % world if a.runner == "batch" else
+                "contact rows split over %d ranks, all-reduce of exact partial sums per move" % world),
+            "timed_region": "candidate draw (host thread) + H2D + kernels + D2H of the result records",
+            "parameters": a.params},
+    }
+    if not a.full:
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+
     score_ms, n_launch = s.ctx.kernel_time_ms("score")
     screen_ms, n_screen = s.ctx.kernel_time_ms("screen")
     s.ctx.reset_timers(0)
@@ -491,33 +568,15 @@ def main():
         # quarter-rate instructions = 32 issue slots; an exact f64 term ~75 instructions at half rate or less.
         slots_per_term = 32.0 if dom_name == "k_screen" else 150.0
         valu_peak = 256 * 128 * 2.4e9
-        out = {
-            "metric": "MCMC moves/s (accepted+rejected) at fixed n_frags x nnz",
-            "value": (world if replicas else 1) * n_moves / elapsed,  # replicas: every rank ran its own n_moves
-            "unit": "moves/s",
-            "n_gpus": dist.get_world_size() if dist is not None else 1,
-            "steps": a.steps,
-            "warmup": a.warmup,
-            "ms_per_step": 1e3 * elapsed / a.steps,
-            "higher_is_better": True,
-            "scaling": "weak" if replicas else "strong",
-            "vs_baseline": None,
+        out.update({
             # BASELINE.md section 3's protocol read literally -- "wall-clock around step_sampler", ONE call per move, the reference's loop
             # (IG:221-228) unchanged but for the import: what a drop-in-by-import caller gets; `value` needs the caller to hand a cycle's
             # bins to step_sampler_batch, results identical
             "value_unchanged_caller": None if not ref_loop else ref_loop.get("moves_per_s"),
             "value_unchanged_caller_unit": "moves/s, one sampler.step_sampler call per move (median %s us per call)" % (
                 "%.0f" % ref_loop["us_per_call"] if ref_loop and ref_loop.get("us_per_call") else "?"),
-            "dtype": "f32 screening tier with a rigorous bound (every column) + f64 terms (f32 inputs) for the contenders / exact i64 fixed-point sums",
-            "data": "synthetic",
-            "config": {"workload": "synthetic Hi-C %s (%d sub-frags), level 4, %d neighbours, nuisance sampling off%s" % (
-                prob_name(prob), prob.n_sub_frags, a.neighbours, "" if a.params == "synthetic" else ", P(s) parameters of a settled chain"), "name": a.config, "seed": a.seed,
-                "step": "one batch of %d moves (step_sampler calls)" % mps, "moves_per_step": mps, "moves_timed": n_moves,
-                "moves_warmup": n_warm,
-                "parallelism": "1 GPU" if world == 1 else ("replicas only: %d independent chains, one per GPU, no data-path collective" % world) if replicas else (
-                    "batch slots split over %d ranks, all-gather of score records" % world if a.runner == "batch" else
-                    "contact rows split over %d ranks, all-reduce of exact partial sums per move" % world),
-                "timed_region": "candidate draw (host thread) + H2D + kernels + D2H of the result records",
+        })
+        out["config"].update({
                 "draw_us_per_move_alone": draw_us,
                 "candidate_genomes_per_s": float(res["n_candidates"].sum()) * 24 / elapsed,  # 24 mutations per candidate: built and screened
                 "columns_scored_exactly_per_s": None if not screened else screened[3] / max(screened[2], 1) * float(res["n_candidates"].sum()) * 24 / elapsed,
@@ -528,11 +587,10 @@ def main():
                 "settled_parameters": settled,
                 "late_assembly": late,
                 "bombed_start": bombed,
-                "parameters": a.params,
                 "nuisance_on_moves_per_s": None if nuis is None else nuis.get("moves_per_s"),
                 "reference_equivalent_GBps": b_ref * (n_moves / elapsed) / 1e9,
-                "B_ref_bytes_per_move": b_ref},
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": 8000.0, "unit": "GB/s", "frac": achieved / 8000.0,
+                "B_ref_bytes_per_move": b_ref})
+        out["roofline"] = {"bound": "hbm", "achieved": achieved, "peak": 8000.0, "unit": "GB/s", "frac": achieved / 8000.0,
                          "traffic": traffic, "traffic_source": traffic_src, "valu_busy_profiled": valu_busy, "kernel": dom_name,
                          "traffic_replayed": None if traffic is None else {
                              "replayed": True, "profiled_moves_per_launch": prof_mpl, "this_run_moves_per_launch": n_moves / n_launch,
@@ -561,8 +619,7 @@ def main():
                          "note": "B_min = sum_c[12 S_c + 20 m_c U + 8 U] + 68 n_touched per move (SURVEY 8(d)), summed over the moves "
                                  "of a launch.  Batches are scored in two tiers: every (contact, column) term through the float "
                                  "screening kernel (the dominant one: VALU-issue bound on an L2-resident working set, not HBM bound), "
-                                 "the exact f64 kernel only for the columns that can still win: DESIGN.md section 4.3-4.4"},
-        }
+                                 "the exact f64 kernel only for the columns that can still win: DESIGN.md section 4.3-4.4"}
         mismatch = None
         if not a.no_cpu_baseline and world == 1:
             try:

@@ -18,6 +18,10 @@ def test_library_exports_every_declared_symbol():
     header = open(os.path.join(ROOT, "include", "instagraal_hip.h")).read()
     names = sorted(set(re.findall(r"\b(ig_[a-z0-9_]+)\s*\(", header)))
     assert len(names) >= 30
+    # torch first, as hip_lib.lib() loads it: a library loaded before torch binds the system's HIP runtime, and the second runtime
+    # torch brings along leaves every later test of the same process without a device
+    import torch  # noqa: F401
+
     lib = ctypes.CDLL(hip_lib.LIB_PATH)
     missing = [n for n in names if not hasattr(lib, n)]
     assert not missing, missing

@@ -125,7 +125,7 @@ def test_bench_starts_its_own_ranks(runner):
     env = dict(os.environ, IG_BENCH_ONE_DEVICE="1")
     env.pop("WORLD_SIZE", None)
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--config", "small", "--steps", "60", "--warmup", "20",
-           "--moves-per-step", "1", "--no-cpu-baseline", "--nuisance-moves", "0", "--runner", runner]
+           "--moves-per-step", "1", "--no-cpu-baseline", "--nuisance-moves", "0", "--runner", runner, "--full"]
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300)
     assert p.returncode == 0, p.stdout[-1500:] + p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
@@ -149,7 +149,7 @@ def test_bench_line_contract_one_gpu():
     env = dict(os.environ)
     env.pop("WORLD_SIZE", None)
     p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--config", "small", "--steps", "4", "--warmup", "1", "--cpu-budget", "2",
-                        "--nuisance-moves", "20"], env=env, capture_output=True, text=True, timeout=600)
+                        "--nuisance-moves", "20", "--full"], env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stdout[-1500:] + p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, p.stdout[-2000:]
@@ -167,6 +167,44 @@ def test_bench_line_contract_one_gpu():
     c = out["cpu_baseline"]
     assert c["kind"] == "port" and c["unit"] == "moves/s" and c["value"] > 0 and c["cores"] >= 1
     assert out["config"]["nuisance_on_moves_per_s"] > 0
+
+
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """a plain `bench.py --steps K --warmup W --dump-outputs DIR` prints the headline alone (nothing of --full) and writes the last
+    step's results and the genome state as float64 arrays; a --full run of the same arguments times and dumps the same moves"""
+    import json
+    import subprocess
+    import sys
+
+    root = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
+    env = dict(os.environ)
+    env.pop("WORLD_SIZE", None)
+    outs, dumps = [], []
+    for k, extra in enumerate(([], ["--full", "--no-cpu-baseline", "--nuisance-moves", "0", "--reference-loop-moves", "0",
+                                    "--settled-batches", "0"])):
+        d = str(tmp_path / ("dump%d" % k))
+        p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--config", "small", "--steps", "3", "--warmup", "1",
+                            "--dump-outputs", d] + extra, env=env, capture_output=True, text=True, timeout=600)
+        assert p.returncode == 0, p.stdout[-1500:] + p.stderr[-3000:]
+        lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, p.stdout[-2000:]
+        outs.append(json.loads(lines[0]))
+        dumps.append({f[:-4]: np.load(os.path.join(d, f)) for f in sorted(os.listdir(d))})
+    plain, full = outs
+    for out in outs:
+        assert out["steps"] == 3 and out["warmup"] == 1 and out["unit"] == "moves/s" and out["higher_is_better"] is True and out["dtype"]
+        assert out["metric"] == "MCMC moves/s (accepted+rejected) at fixed n_frags x nnz"
+        assert out["config"]["moves_timed"] == 3 * 128 and out["config"]["moves_warmup"] == 128
+        assert abs(out["value"] * out["ms_per_step"] * 1e-3 - 128.0) < 1e-6 * 128.0
+    assert "roofline" not in plain and "cpu_baseline" not in plain and "value_unchanged_caller" not in plain
+    assert "roofline" in full and full["config"]["maintained_likelihood_exact"] is True
+    a, b = dumps
+    assert sorted(a) == sorted(b) and {"o", "dist", "op_sampled", "id_f_sampled", "n_contigs", "candidates", "genome_state"} <= set(a)
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    for k in a:
+        assert a[k].dtype in (np.float32, np.float64), k
+        assert np.array_equal(a[k], b[k]), k
+    assert a["o"].shape == (128,) and a["candidates"].shape == (128, 5) and a["genome_state"].shape[0] == 17
 
 
 def test_bench_refuses_ranks_without_devices():

@@ -36,7 +36,7 @@ try:
     mpl = float(line["config"]["moves_per_launch"])
 except Exception:
     pass
-out = {"command": "tools/profile_round.sh %s: rocprofv3 --pmc <one group per pass> -- python3 bench.py --no-cpu-baseline --nuisance-moves 0 "
+out = {"command": "tools/profile_round.sh %s: rocprofv3 --pmc <one group per pass> -- python3 bench.py --full --no-cpu-baseline --nuisance-moves 0 "
                   "--reference-loop-moves 0 --late-moves 0 --config %s%s --settled-batches 0 --steps 8 --warmup 2 (8 steps of 128 moves; one MI355X; "
                   "%s moves per launch chain)" % (tag, cfg.replace("settled", ""), " --params settled" if cfg.endswith("settled") else "",
                                                    "%.1f" % mpl if mpl else "?"),
