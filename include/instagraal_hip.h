@@ -222,6 +222,28 @@ int ig_bomb(ig_ctx* ctx, const int32_t* shuffle);                               
 int ig_genome_distance(ig_ctx* ctx, double* d);                                              /* CL:665-716 */
 int ig_get_valid_insert(ig_ctx* ctx, int32_t out12[12]); /* gpu_list_valid_insert, stale-flag state (Q4) */
 
+/* ---- the contact map of the current genome (display_current_matrix CL:2555-2605) ----
+ * The reference densifies sparse_matrix + sparse_matrix.T and indexes it by full_order_high, the sub-fragments in the order of the
+ * genome (CL:2563-2585, 2598-2599).  Here: the same ORDER, and the matrix under it as a binned image built from the device copy
+ * of the contacts, of bounded size whatever M is.
+ * Order: contigs by ascending contig id as ig_download_state returns it (the reference walks np.unique of its ids), a contig only if
+ * every one of its bins has activ == 1 (CL:2571); inside a contig the bins by pos, inside a bin the sub-fragments in table order,
+ * reversed when ori == -1 (CL:2576-2585).  order_M: caller-owned, M entries of room; order_M[r] = the sub-fragment at position r for
+ * r < *n_placed = T.
+ * Image: bin = max(1, ceil(T / max_side)) positions per pixel, side = ceil(T / bin), pixel of position r = r / bin;
+ * image[pi * side + pj] = sum of the counts of the uploaded contacts between pixels pi and pj, both ways round (a contact inside one
+ * pixel counts twice there): with max_side >= T the reference's matrix entry for entry, EXCEPT its diagonal -- ig_upload_contacts
+ * takes the strict upper triangle, so self-contacts (twice the diagonal of the input matrix in the reference's picture) are not in
+ * the image; a caller that has them adds them (instagraal_amd.sampler.contact_map does).  64-bit integer sums: exact, and the same
+ * from run to run.  image: caller-owned, image_capacity entries; *side and *bin are set first, then image_capacity < side * side is
+ * an error and nothing is written.
+ * Both calls read the CURRENT coordinates and change nothing a move reads (no state, tables, maintained sums, slice pools, window
+ * slots): moves scored ahead stay valid.  Synchronous.  They do NOT end a nuisance step or a chain in flight: between ig_nuis_begin /
+ * ig_nuis_step_begin and ig_nuis_end, and between ig_nuis_chain_begin and ig_nuis_chain_end, they return an error.
+ * A sharded handle (ig_set_shard) adds its shard's rows only: the partial images of all ranks sum to the image. */
+int ig_contact_map_order(ig_ctx* ctx, int32_t* order_M, int32_t* n_placed);
+int ig_contact_map(ig_ctx* ctx, int32_t max_side, int64_t* image, int64_t image_capacity, int32_t* side, int32_t* bin);
+
 /* ---- multi-GPU (contact shards) -------------------------- */
 /* Two-phase move: partial sums over this handle's contact shard are left in a device buffer of
  * ig_partials_count() int64 values; the caller all-reduces (SUM) it across ranks, then finishes. */
@@ -285,6 +307,10 @@ int ig_debug_step_stats(ig_ctx* ctx, int64_t out2[2]); /* ig_step_draw: {calls t
 int ig_debug_nuis_chain_stats(ig_ctx* ctx, int64_t out10[10]); /* chains: {calls, segments, pairs completed, ends by reason [7]} */
 int ig_debug_set_full_hist(int on); /* from-scratch pass: all-trans tiles from their count histograms (1, default) or contact by contact (0) */
 
+/* the contact map's pass (zero + k_contact_map + mirror) n times under max_side, hipEvents around each: ms_n[n]; combine = 0: the
+ * form with one atomic per contact end (the yardstick the wave-combined form is measured against); *image_sum (may be NULL): the
+ * sum of the last image */
+int ig_debug_contact_map_time(ig_ctx* ctx, int32_t max_side, int32_t combine, int32_t n, float* ms_n, int64_t* image_sum);
 #ifdef __cplusplus
 }
 #endif

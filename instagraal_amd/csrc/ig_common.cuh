@@ -325,6 +325,17 @@ struct ChainTest {     /* k_chain_hist_eval -> the decide wave, per set: the his
     double z;
 };
 
+/* the contact map of the current genome (ig_kernels_map.cuh): buffers kept from call to call */
+struct MapBuf {
+    int* base = nullptr;  /* [N] first position of the bin's contig in the order, -1: the contig is not placed */
+    int* pix = nullptr;   /* [M] pixel of every sub-fragment, -1: left out */
+    int* order = nullptr; /* [M] order[r] = sub-fragment at position r */
+    int* err = nullptr;
+    unsigned long long* image = nullptr; /* [image_cap] */
+    size_t image_cap = 0;
+    int N = 0, M = 0;
+};
+
 struct ig_ctx {
     int device;
     hipStream_t stream;
@@ -427,6 +438,7 @@ struct ig_ctx {
     Glob* glob;
     long long* scratch8; /* 8 x int64 reduction scratch of the from-scratch passes */
     MoveBuf mb;
+    MapBuf map;
     int* batch_out; /* committed moves, pending slot, (unused), candidates, predicted deltas used, contigs */
     int *host_bo, *host_bo_dev; /* the same in mapped host memory (+ [7] = sequence number of the decide launch), and its device address */
     int bo_seq;

@@ -1,6 +1,7 @@
 /* ig_host_core.inc -- part of ig_hip.hip (one translation unit; included there in order): the handle: the helper thread of the nuisance runs, allocation and timers, ig_create / ig_destroy, the from-scratch pass's launches, window buffers, slice pool and batch buffers. */
 
 /* ================================================================== host side */
+static void free_map_buffers(ig_ctx* c);   /* ig_host_map.inc */
 static void flush_pending_sums(ig_ctx* c); /* behind a decisively accepted nuisance step: see k_nuis_promote */
 
 /* ---- the launches of a run's NEXT step on a helper thread ------------------------------------------------------------------
@@ -447,6 +448,7 @@ extern "C" void ig_destroy(ig_ctx* c)
     if (c->host_step) hipHostFree(c->host_step);
     drain_timers(c);
     free_move_buffers(c);
+    free_map_buffers(c);
     hipFree(c->st_block);
     hipFree(c->tab.dist);
     hipFree(c->tab_prev.dist);

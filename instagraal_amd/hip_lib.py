@@ -18,7 +18,8 @@ SRC = os.path.join(HERE, "csrc", "ig_hip.hip")
 SRC_HOST = os.path.join(HERE, "csrc", "ig_draw.cpp")  # host-only part: the candidate draw
 DEPS = [SRC, SRC_HOST] + [os.path.join(HERE, "csrc", f) for f in ("ig_ops.cuh", "ig_common.cuh", "ig_model.cuh", "ig_kernels_setup.cuh",
                                                           "ig_kernels_score.cuh", "ig_kernels_screen.cuh", "ig_kernels_commit.cuh",
-                                                          "ig_kernels_nuis.cuh", "ig_host_core.inc", "ig_host_upload.inc",
+                                                          "ig_kernels_nuis.cuh", "ig_kernels_map.cuh", "ig_host_core.inc", "ig_host_upload.inc",
+                                                          "ig_host_map.inc",
                                                           "ig_host_batch.inc", "ig_host_nuis.inc", "ig_host_debug.inc")] + \
        [os.path.join(ROOT, "include", f) for f in ("ig_detmath.h", "ig_detmath_tables.h", "instagraal_hip.h")]
 
@@ -617,6 +618,39 @@ class Context:
         o = np.zeros(3, np.int64)
         _ck(lib().ig_scratch_bytes(self._h, _p(o)))
         return int(o[0]), int(o[1]), int(o[2])
+
+    # ---- the contact map of the current genome (display_current_matrix CL:2555-2605)
+    def contact_map_order(self):
+        """the placed sub-fragments in the order of the genome (the reference's full_order_high) -> int32 array"""
+        out = np.zeros(max(self.M, 1), np.int32)
+        n = C.c_int32()
+        _ck(lib().ig_contact_map_order(self._h, _p(out), C.byref(n)))
+        return out[:n.value].copy()
+
+    def contact_map(self, max_side):
+        """the contacts under that order, ``bin`` positions per pixel so that the side stays within ``max_side``
+        -> (image int64 [side, side], bin); self-contacts are not in it (the device holds the strict upper triangle)"""
+        from .contact_map import binning
+
+        max_side = int(max_side)
+        if not 1 <= max_side <= 2 ** 31 - 1:
+            raise HipError("contact_map: max_side must be >= 1 (got %d)" % max_side)
+        cap = min(max_side, max(self.M, 1))  # side <= min(max_side, T), T <= M
+        if cap * cap > 1 << 26:  # (a buffer of that many entries only if the image really has them)
+            cap = max(binning(self.contact_map_order().size, max_side)[1], 1)
+        img = np.empty(cap * cap, np.int64)
+        side, b = C.c_int32(), C.c_int32()
+        _ck(lib().ig_contact_map(self._h, C.c_int32(max_side), _p(img), C.c_int64(img.size), C.byref(side), C.byref(b)))
+        n = side.value
+        return img[:n * n].reshape(n, n).copy(), b.value
+
+    def debug_contact_map_time(self, max_side, combine=True, n=1):
+        """the map's pass n times with hipEvents around each -> (milliseconds [n], sum of the last image)"""
+        ms = np.zeros(int(n), np.float32)
+        tot = C.c_int64()
+        _ck(lib().ig_debug_contact_map_time(self._h, C.c_int32(int(max_side)), C.c_int32(int(bool(combine))), C.c_int32(int(n)), _p(ms),
+                                            C.byref(tot)))
+        return ms, int(tot.value)
 
     # ---- bookkeeping
     def renumber_contigs(self):

@@ -9,6 +9,7 @@ arguments (CL:92-125), same public methods and attributes that ``simulation`` an
     estimate_parameters_rippe / eval_likelihood_init              CL:2239-2372, 1193-1243
     bomb_the_genome, modify_gl_cuda_buffer, dist_inter_genome     CL:1925-1948, 2715-2881, 665-716
     apply_replay_simu, free_gpu                                   CL:2546-2553, 3167-3177
+    display_current_matrix(filename) -> 3-tuple, contact_map      CL:2555-2606
     gpu_vect_frags.copy_from_gpu() + numpy attributes             gpustruct.py:162-186
 
 What the reference does with ~450 synchronous pycuda launches and 5 PCIe sorts per move is ONE
@@ -736,6 +737,48 @@ class sampler:  # noqa: N801 - the reference's class name
         self.mean_length_contigs = np.float32(last["mean_len"])
         self.candidates = [int(x) for x in cands[n_done - 1] if x >= 0]
         return tuples, n_done
+
+    # ------------------------------------------------------------ contact map
+    def contact_map(self, max_side=2048):
+        """The contacts under the current genome as an exact integer image (``ig_contact_map``): the placed sub-fragments in the
+        reference's ``full_order_high``, ``bin = max(1, ceil(T / max_side))`` of them per pixel -> (image int64 [side, side], bin).
+        With ``max_side >= T`` it is the matrix the reference shows, ``(sparse_matrix + sparse_matrix.T)[order][:, order]``
+        (CL:2598-2599), entry for entry.  The device holds the strict upper triangle only; the diagonal of the symmetrised input
+        matrix is added here (a sampler built from ``coo=`` has none)."""
+        image, b = self.ctx.contact_map(max_side)
+        if self.sparse_matrix is not None and image.size:
+            d = np.asarray(self.sparse_matrix.diagonal())
+            nz = np.nonzero(d)[0]
+            if nz.size:
+                order = self.ctx.contact_map_order()
+                where = np.full(d.size, -1, np.int64)
+                where[order] = np.arange(order.size)
+                nz = nz[where[nz] >= 0]
+                px = where[nz] // b
+                np.add.at(image, (px, px), d[nz].astype(np.int64))
+        return image, b
+
+    def display_current_matrix(self, filename, max_side=2048):  # CL:2555-2606
+        """Writes the picture of the contact map of the current genome as the reference does (CL:2601-2605) and returns
+        ``(full_order, dict_contig, full_order_high)``: the bins and, per contig id, its bins in genome order, and the sub-fragments
+        in genome order (from the device).  Beyond ``max_side`` sub-fragments the picture is the binned image of ``contact_map``."""
+        from . import contact_map as cmap
+
+        g = self.gpu_vect_frags.copy_from_gpu()
+        full_order, dict_contig, _ = cmap.genome_order(g.pos, g.id_c, g.activ, g.id_d, g.ori, self.np_sub_frags_id)
+        full_order_high = self.ctx.contact_map_order().tolist()
+        image, _ = self.contact_map(max_side)
+        # matplotlib only here, and without pyplot: a figure on an Agg canvas of its own leaves the process's backend alone
+        from matplotlib.backends.backend_agg import FigureCanvasAgg
+        from matplotlib.figure import Figure
+
+        fig = Figure(figsize=(14, 14))
+        FigureCanvasAgg(fig)
+        ax = fig.subplots()
+        ax.imshow(image, vmax=np.percentile(image, 99) if image.size else None, interpolation="nearest")
+        ax.axis("off")
+        fig.savefig(filename, dpi=200, bbox_inches="tight")
+        return full_order, dict_contig, full_order_high
 
     def free_gpu(self):  # CL:3167-3177
         self.ctx.close()

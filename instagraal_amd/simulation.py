@@ -7,7 +7,8 @@ either side of the scoring path (reference: simu_single.py "
   hard-wires an empty duplicate list, SS:512, so these only add ``rep / activ / id_d``), the 29 constructor arguments
   of the sampler (SS:120-153) and the initial P(s) estimation (SS:157-171).
 * ``instagraal_class.full_em`` mirrors IG:196-291: cycles over shuffled bins, per-cycle outputs
-  (``save_simu_step_<j>.txt``, ``info_frags.txt``, ``genome.fasta``, the ``list_*.txt`` traces).  Cycles without
+  (``save_simu_step_<j>.txt``, ``info_frags.txt``, ``genome.fasta``, the ``list_*.txt`` traces, with ``save_matrix`` the
+  contact map ``matrix_cycle_<j>.png``).  Cycles without
   nuisance sampling run through ``step_sampler_batch`` (the results are identical).
 * ``run_instagraal`` mirrors IG:502-581.
 
@@ -224,6 +225,13 @@ class instagraal_class:
                     h.write(str(pos) + "\t" + str(start_bp) + "\t" + str(id_c) + "\t" + str(ori) + "\n")
             self.simulation.export_new_fasta()
             self.save_behaviour_to_txt()
+            try:  # IG:278-287
+                if save_matrix:
+                    sampler.display_current_matrix(self._out("matrix_cycle_%d.png" % j))
+            except OSError as e:
+                import warnings
+
+                warnings.warn("could not write the matrix at cycle %d: %s" % (j, e))
         self.save_behaviour_to_txt()
 
     def save_behaviour_to_txt(self):  # IG:293-330
@@ -242,15 +250,13 @@ def run_instagraal(hic_folder, reference_fa, output_folder=None, level=4, cycles
     """IG:502-581 (defaults of cli/main.py: level 4, 100 cycles, 5 neighbours, 1 std).  The three trailing switches of the
     reference's signature (IG:512-514) are accepted: ``save_pickle`` dumps the run object to ``graal.pkl`` as the reference
     tries to (IG:589-594: a warning when it cannot be pickled -- device handles here, h5py handles there); ``save_matrix``
-    asks for the matplotlib contact-map previews of ``display_current_matrix`` (IG:279-284), which are outside this path
-    (SURVEY 2a): ignored with a warning; ``simple`` calls ``instagraal_class.simple_start``, a method the reference does not
-    define (IG:582 raises AttributeError): refused."""
+    writes the contact map of the genome after every cycle to ``matrix_cycle_<j>.png`` (``display_current_matrix``, IG:279-284;
+    built on the GPU, binned to at most 2048 pixels a side: DESIGN 4.10); ``simple`` calls ``instagraal_class.simple_start``, a
+    method the reference does not define (IG:582 raises AttributeError): refused."""
     import warnings
 
     if simple and not pyramid_only:
         raise NotImplementedError("simple=True: the reference calls instagraal_class.simple_start (instagraal.py:582), which it does not define")
-    if save_matrix:
-        warnings.warn("save_matrix: the per-cycle contact-map previews (instagraal.py:279-284, matplotlib) are not part of this path; ignored")
     name = os.path.basename(os.path.normpath(str(hic_folder)))
     if pyramid_only:
         root = str(output_folder) if output_folder is not None else os.path.join(os.getcwd(), "results")
@@ -265,7 +271,7 @@ def run_instagraal(hic_folder, reference_fa, output_folder=None, level=4, cycles
         warnings.warn("--circular has no effect on the assembly (as in the reference: instagraal.py:569-570 sets the flag "
                       "after the sampler copied the fragment arrays)")
         p2.simulation.level.S_o_A_frags["circ"] += 1
-    p2.full_em(n_cycles=cycles, n_neighbours=neighborhood, bomb=bomb, id_start_sample_param=4)
+    p2.full_em(n_cycles=cycles, n_neighbours=neighborhood, bomb=bomb, id_start_sample_param=4, save_matrix=save_matrix)
     if save_pickle:  # IG:589-594
         import pickle
 
