@@ -244,6 +244,22 @@ int ig_get_valid_insert(ig_ctx* ctx, int32_t out12[12]); /* gpu_list_valid_inser
 int ig_contact_map_order(ig_ctx* ctx, int32_t* order_M, int32_t* n_placed);
 int ig_contact_map(ig_ctx* ctx, int32_t max_side, int64_t* image, int64_t image_capacity, int32_t* side, int32_t* bin);
 
+/* ---- the distance law P(s) of the current genome (no reference counterpart; the rule: instagraal_amd/distance_law.py) ---------
+ * edges: n_edges ascending finite floats (kb), 2 <= n_edges <= 4097; bin b holds the separations edges[b] <= s < edges[b + 1].
+ * A pair of sub-fragments of one placed contig (placed as for the contact map: every bin active) that is not a ring has
+ * s = fabsf(dist_i - dist_j) on the current coordinate table, in float.  observed[b] (n_edges - 1 entries): sum of the counts of the
+ * uploaded contacts between such pairs; pairs[b]: the number of such pairs, with or without a contact (NULL: the pairs pass is
+ * skipped and the pair scalars are -1).
+ * scalars: {0 out_of_range_observed, 1 out_of_range_pairs (s < edges[0] or s >= edges[n_edges - 1]), 2 trans_observed,
+ * 3 trans_pairs (both ends placed, different contigs; the pairs from the sub-fragment counts: T (T - 1) / 2 - placed_pairs),
+ * 4 ring_observed, 5 ring_pairs (inside a ring contig: two separations, left out of the law), 6 unplaced_observed (an end in a
+ * contig that is not placed), 7 placed_pairs = sum over the placed contigs of M_c (M_c - 1) / 2}.
+ * By construction: sum(observed) + scalars[0] + [2] + [4] + [6] = sum of all counts; sum(pairs) + scalars[1] + [5] = scalars[7].
+ * 64-bit integer sums: exact, the same from run to run.  Guards and effects as ig_contact_map: reads the CURRENT coordinates, changes
+ * nothing a move reads, synchronous, an error while a nuisance step or a chain is in flight.  A sharded handle (ig_set_shard) adds its
+ * shard's rows to observed and the observed scalars -- the ranks' results sum to the whole -- and computes the pairs whole. */
+int ig_distance_law(ig_ctx* ctx, const float* edges, int32_t n_edges, int64_t* observed, int64_t* pairs, int64_t scalars[8]);
+
 /* ---- multi-GPU (contact shards) -------------------------- */
 /* Two-phase move: partial sums over this handle's contact shard are left in a device buffer of
  * ig_partials_count() int64 values; the caller all-reduces (SUM) it across ranks, then finishes. */
@@ -311,6 +327,11 @@ int ig_debug_set_full_hist(int on); /* from-scratch pass: all-trans tiles from t
  * form with one atomic per contact end (the yardstick the wave-combined form is measured against); *image_sum (may be NULL): the
  * sum of the last image */
 int ig_debug_contact_map_time(ig_ctx* ctx, int32_t max_side, int32_t combine, int32_t n, float* ms_n, int64_t* image_sum);
+/* the distance law's passes n times each, hipEvents around each (zero + kernel): ms_observed_n[n] -- privatised = 1: the form with a
+ * histogram per workgroup in LDS, 0: one global atomic per contact (the yardstick) -- and ms_pairs_n[n] (may be NULL: not run);
+ * *checksum (may be NULL): the last observed pass's words, each weighted by its place: both forms must agree on it */
+int ig_debug_distance_law_time(ig_ctx* ctx, const float* edges, int32_t n_edges, int32_t privatised, int32_t n, float* ms_observed_n,
+                               float* ms_pairs_n, int64_t* checksum);
 #ifdef __cplusplus
 }
 #endif

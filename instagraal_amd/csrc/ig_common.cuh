@@ -336,6 +336,17 @@ struct MapBuf {
     int N = 0, M = 0;
 };
 
+/* the distance law of the current genome (ig_kernels_law.cuh): buffers kept from call to call */
+struct LawBuf {
+    int4* rec = nullptr;   /* [M] (dist, s_tot, contig, position or -1) per sub-fragment */
+    float* ds = nullptr;   /* [M] dist by position of the genome order */
+    int2* meta = nullptr;  /* [M] (first position of the contig, its sub-fragments; negated: a ring) by position */
+    float* edges = nullptr;
+    unsigned long long* out = nullptr; /* LAW_OUT_WORDS (ig_host_law.inc) */
+    int* flag = nullptr;   /* the pairs pass saw dist decrease inside a contig */
+    int M = 0;
+};
+
 struct ig_ctx {
     int device;
     hipStream_t stream;
@@ -439,6 +450,7 @@ struct ig_ctx {
     long long* scratch8; /* 8 x int64 reduction scratch of the from-scratch passes */
     MoveBuf mb;
     MapBuf map;
+    LawBuf law;
     int* batch_out; /* committed moves, pending slot, (unused), candidates, predicted deltas used, contigs */
     int *host_bo, *host_bo_dev; /* the same in mapped host memory (+ [7] = sequence number of the decide launch), and its device address */
     int bo_seq;

@@ -2,6 +2,7 @@
 
 /* ================================================================== host side */
 static void free_map_buffers(ig_ctx* c);   /* ig_host_map.inc */
+static void free_law_buffers(ig_ctx* c);   /* ig_host_law.inc */
 static void flush_pending_sums(ig_ctx* c); /* behind a decisively accepted nuisance step: see k_nuis_promote */
 
 /* ---- the launches of a run's NEXT step on a helper thread ------------------------------------------------------------------
@@ -449,6 +450,7 @@ extern "C" void ig_destroy(ig_ctx* c)
     drain_timers(c);
     free_move_buffers(c);
     free_map_buffers(c);
+    free_law_buffers(c);
     hipFree(c->st_block);
     hipFree(c->tab.dist);
     hipFree(c->tab_prev.dist);

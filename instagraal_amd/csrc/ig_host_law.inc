@@ -1,0 +1,164 @@
+/* ig_host_law.inc -- part of ig_hip.hip (one translation unit; included there in order): the distance law of the current genome
+ * (ig_kernels_law.cuh; the rule: instagraal_amd/distance_law.py). */
+
+/* LawBuf.out, in 64-bit words: the observed histogram and the observed pass's scalars, the pairs histogram and the pairs pass's
+ * scalars (each pass owns its half: the pairs half can be redone alone) */
+#define LAW_OUT_OBS 0
+#define LAW_OUT_OSC (LAW_MAX_BINS)
+#define LAW_OUT_PAIRS (LAW_MAX_BINS + LAW_NS)
+#define LAW_OUT_PSC (2 * LAW_MAX_BINS + LAW_NS)
+#define LAW_OUT_WORDS (2 * (LAW_MAX_BINS + LAW_NS))
+
+static void free_law_buffers(ig_ctx* c)
+{
+    hipFree(c->law.rec);
+    hipFree(c->law.ds);
+    hipFree(c->law.meta);
+    hipFree(c->law.edges);
+    hipFree(c->law.out);
+    hipFree(c->law.flag);
+    c->law = LawBuf{};
+}
+
+/* Argument checks, the guards of the map (map_prepare), then on the device: the genome order, the records of both passes, the
+ * edges.  T: placed sub-fragments. */
+static int law_prepare(ig_ctx* c, const char* who, const float* edges, int n_edges, bool want_pairs, int* T_out)
+{
+    if (!edges) return fail("%s: edges is NULL", who);
+    if (n_edges < 2 || n_edges > LAW_MAX_EDGES) return fail("%s: 2 <= n_edges <= %d (got %d)", who, LAW_MAX_EDGES, n_edges);
+    for (int i = 0; i < n_edges; i++) {
+        if (!(edges[i] - edges[i] == 0.0f)) return fail("%s: edge %d is not finite", who, i);
+        if (i && edges[i] < edges[i - 1]) return fail("%s: the edges are not sorted (edge %d < edge %d)", who, i, i - 1);
+    }
+    if (!c->have_contacts) return fail("%s: upload the contacts first", who);
+    int T = 0, bin = 1, side = 0;
+    if (map_prepare(c, who, 1, true, &T, &bin, &side)) return -1;
+    LawBuf& l = c->law;
+    const int M = c->M;
+    if (l.M != M) {
+        free_law_buffers(c);
+        DALLOC(l.rec, (size_t)M);
+        DALLOC(l.ds, (size_t)M);
+        DALLOC(l.meta, (size_t)M);
+        DALLOC(l.edges, (size_t)LAW_MAX_EDGES);
+        DALLOC(l.out, (size_t)LAW_OUT_WORDS);
+        DALLOC(l.flag, 1);
+        l.M = M;
+    }
+    HIPCK(hipMemcpyAsync(l.edges, edges, (size_t)n_edges * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_law_records, dim3((M + 255) / 256), dim3(256), 0, c->stream, c->tab, c->map.pix, M, l.rec);
+    if (want_pairs && T > 0) hipLaunchKernelGGL(k_law_sorted, dim3((T + 255) / 256), dim3(256), 0, c->stream, c->tab, c->map.order, M, T, l.ds, l.meta);
+    HIPCK(hipStreamSynchronize(c->stream)); /* (`edges` is the caller's pageable memory) */
+    *T_out = T;
+    return 0;
+}
+
+/* zero + the observed pass on the library's stream */
+static int law_enqueue_observed(ig_ctx* c, int n_edges, bool privatised)
+{
+    LawBuf& l = c->law;
+    HIPCK(hipMemsetAsync(l.out + LAW_OUT_OBS, 0, (size_t)(LAW_MAX_BINS + LAW_NS) * sizeof(unsigned long long), c->stream));
+    if (c->Z == 0) return 0;
+    /* a workgroup zeroes and flushes a histogram of its own: no more of them than keep every CU busy */
+    const int blocks = (int)std::min<long long>((c->Z + LAW_THREADS - 1) / LAW_THREADS, 2048);
+    const size_t lds = law_lds_bytes(n_edges);
+    if (privatised)
+        hipLaunchKernelGGL((k_law_observed<true>), dim3(blocks), dim3(LAW_THREADS), lds, c->stream, c->crow, c->cc, c->Z, l.rec, l.edges, n_edges,
+                           l.out + LAW_OUT_OBS, l.out + LAW_OUT_OSC, c->rank, c->world);
+    else
+        hipLaunchKernelGGL((k_law_observed<false>), dim3(blocks), dim3(LAW_THREADS), lds, c->stream, c->crow, c->cc, c->Z, l.rec, l.edges, n_edges,
+                           l.out + LAW_OUT_OBS, l.out + LAW_OUT_OSC, c->rank, c->world);
+    return 0;
+}
+
+/* zero + the pairs pass */
+static int law_enqueue_pairs(ig_ctx* c, int T, int n_edges, bool brute)
+{
+    LawBuf& l = c->law;
+    HIPCK(hipMemsetAsync(l.out + LAW_OUT_PAIRS, 0, (size_t)(LAW_MAX_BINS + LAW_NS) * sizeof(unsigned long long), c->stream));
+    HIPCK(hipMemsetAsync(l.flag, 0, sizeof(int), c->stream));
+    if (T == 0) return 0;
+    const int blocks = (T + LAW_THREADS - 1) / LAW_THREADS;
+    const size_t lds = law_lds_bytes(n_edges);
+    if (brute)
+        hipLaunchKernelGGL((k_law_pairs<true>), dim3(blocks), dim3(LAW_THREADS), lds, c->stream, l.ds, l.meta, T, l.edges, n_edges, l.out + LAW_OUT_PAIRS,
+                           l.out + LAW_OUT_PSC, l.flag);
+    else
+        hipLaunchKernelGGL((k_law_pairs<false>), dim3(blocks), dim3(LAW_THREADS), lds, c->stream, l.ds, l.meta, T, l.edges, n_edges, l.out + LAW_OUT_PAIRS,
+                           l.out + LAW_OUT_PSC, l.flag);
+    return 0;
+}
+
+/* the pairs pass; should dist decrease somewhere inside a contig (the run form's assumption), once more by brute force */
+static int law_run_pairs(ig_ctx* c, int T, int n_edges)
+{
+    if (law_enqueue_pairs(c, T, n_edges, false)) return -1;
+    int flag = 0;
+    HIPCK(hipMemcpyAsync(&flag, c->law.flag, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPCK(hipStreamSynchronize(c->stream));
+    if (flag) {
+        if (law_enqueue_pairs(c, T, n_edges, true)) return -1;
+        HIPCK(hipStreamSynchronize(c->stream));
+    }
+    return 0;
+}
+
+extern "C" int ig_distance_law(ig_ctx* c, const float* edges, int32_t n_edges, int64_t* observed, int64_t* pairs, int64_t scalars[8])
+{
+    IG_JOIN(c);
+    HIPCK(hipSetDevice(c->device));
+    if (!observed || !scalars) return fail("ig_distance_law: NULL output");
+    int T = 0;
+    if (law_prepare(c, "ig_distance_law", edges, n_edges, pairs != nullptr, &T)) return -1;
+    if (law_enqueue_observed(c, n_edges, true)) return -1;
+    if (pairs && law_run_pairs(c, T, n_edges)) return -1;
+    std::vector<long long> h(LAW_OUT_WORDS, 0);
+    HIPCK(hipMemcpyAsync(h.data(), c->law.out, (size_t)(pairs ? LAW_OUT_WORDS : LAW_MAX_BINS + LAW_NS) * sizeof(long long), hipMemcpyDeviceToHost, c->stream));
+    HIPCK(hipStreamSynchronize(c->stream));
+    const int nb = n_edges - 1;
+    for (int b = 0; b < nb; b++) observed[b] = h[LAW_OUT_OBS + b];
+    if (pairs)
+        for (int b = 0; b < nb; b++) pairs[b] = h[LAW_OUT_PAIRS + b];
+    for (int k = 0; k < LAW_NS; k++) scalars[k] = h[LAW_OUT_OSC + k];
+    for (int k : {LAW_OOR_PAIRS, LAW_TRANS_PAIRS, LAW_RING_PAIRS, LAW_PLACED_PAIRS}) scalars[k] = pairs ? h[LAW_OUT_PSC + k] : -1;
+    if (pairs) scalars[LAW_TRANS_PAIRS] = (long long)T * (long long)(T - 1) / 2 - scalars[LAW_PLACED_PAIRS];
+    return 0;
+}
+
+extern "C" int ig_debug_distance_law_time(ig_ctx* c, const float* edges, int32_t n_edges, int32_t privatised, int32_t n, float* ms_observed_n,
+                                          float* ms_pairs_n, int64_t* checksum)
+{
+    IG_JOIN(c);
+    HIPCK(hipSetDevice(c->device));
+    if (n < 1 || !ms_observed_n) return fail("ig_debug_distance_law_time: bad arguments");
+    int T = 0;
+    if (law_prepare(c, "ig_debug_distance_law_time", edges, n_edges, ms_pairs_n != nullptr, &T)) return -1;
+    hipEvent_t a, b;
+    HIPCK(hipEventCreate(&a));
+    HIPCK(hipEventCreate(&b));
+    int rc = 0;
+    for (int pass = 0; pass < 2 && !rc; pass++) {
+        float* ms = pass ? ms_pairs_n : ms_observed_n;
+        if (!ms) continue;
+        for (int r = 0; r < n && !rc; r++) {
+            hipError_t e = hipEventRecord(a, c->stream);
+            rc = pass ? law_enqueue_pairs(c, T, n_edges, false) : law_enqueue_observed(c, n_edges, privatised != 0);
+            if (e == hipSuccess) e = hipEventRecord(b, c->stream);
+            if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+            if (e == hipSuccess) e = hipEventElapsedTime(&ms[r], a, b);
+            if (e != hipSuccess && !rc) rc = fail("ig_debug_distance_law_time: %s", hipGetErrorString(e));
+        }
+    }
+    hipEventDestroy(a);
+    hipEventDestroy(b);
+    if (rc) return rc;
+    if (checksum) { /* of the last observed pass, every word weighted by its place: both forms of the kernel must agree on it */
+        std::vector<long long> h(LAW_MAX_BINS + LAW_NS);
+        HIPCK(hipMemcpy(h.data(), c->law.out, h.size() * sizeof(long long), hipMemcpyDeviceToHost));
+        unsigned long long s = 0;
+        for (int b2 = 0; b2 < n_edges - 1; b2++) s += (unsigned long long)h[LAW_OUT_OBS + b2] * (unsigned long long)(b2 + 1);
+        for (int k = 0; k < LAW_NS; k++) s += (unsigned long long)h[LAW_OUT_OSC + k] * (unsigned long long)(LAW_MAX_BINS + 1 + k);
+        *checksum = (long long)s;
+    }
+    return 0;
+}

@@ -18,8 +18,8 @@ SRC = os.path.join(HERE, "csrc", "ig_hip.hip")
 SRC_HOST = os.path.join(HERE, "csrc", "ig_draw.cpp")  # host-only part: the candidate draw
 DEPS = [SRC, SRC_HOST] + [os.path.join(HERE, "csrc", f) for f in ("ig_ops.cuh", "ig_common.cuh", "ig_model.cuh", "ig_kernels_setup.cuh",
                                                           "ig_kernels_score.cuh", "ig_kernels_screen.cuh", "ig_kernels_commit.cuh",
-                                                          "ig_kernels_nuis.cuh", "ig_kernels_map.cuh", "ig_host_core.inc", "ig_host_upload.inc",
-                                                          "ig_host_map.inc",
+                                                          "ig_kernels_nuis.cuh", "ig_kernels_map.cuh", "ig_kernels_law.cuh", "ig_host_core.inc", "ig_host_upload.inc",
+                                                          "ig_host_map.inc", "ig_host_law.inc",
                                                           "ig_host_batch.inc", "ig_host_nuis.inc", "ig_host_debug.inc")] + \
        [os.path.join(ROOT, "include", f) for f in ("ig_detmath.h", "ig_detmath_tables.h", "instagraal_hip.h")]
 
@@ -651,6 +651,33 @@ class Context:
         _ck(lib().ig_debug_contact_map_time(self._h, C.c_int32(int(max_side)), C.c_int32(int(bool(combine))), C.c_int32(int(n)), _p(ms),
                                             C.byref(tot)))
         return ms, int(tot.value)
+
+    # ---- the distance law of the current genome (the rule: distance_law.py)
+    def distance_law(self, edges, pairs=True):
+        """observed contacts and sub-fragment pairs per bin of separation under ``edges`` (ascending f32, kb) -> dict: edges,
+        observed, pairs (int64 [len(edges) - 1]; None with ``pairs=False``) and the int64 scalars of ``distance_law.SCALARS``"""
+        from .distance_law import SCALARS
+
+        e = np.ascontiguousarray(edges, np.float32).ravel()
+        nb = max(int(e.size) - 1, 1)
+        obs = np.zeros(nb, np.int64)
+        prs = np.zeros(nb, np.int64) if pairs else None
+        sc = np.zeros(8, np.int64)
+        _ck(lib().ig_distance_law(self._h, _p(e), C.c_int32(int(e.size)), _p(obs), _p(prs), _p(sc)))
+        out = dict(edges=e, observed=obs, pairs=prs)
+        out.update((k, int(v)) for k, v in zip(SCALARS, sc))
+        return out
+
+    def debug_distance_law_time(self, edges, privatised=True, n=1, pairs=True):
+        """the law's passes n times each with hipEvents around each -> (ms observed [n], ms pairs [n] or None, checksum of the
+        last observed pass)"""
+        e = np.ascontiguousarray(edges, np.float32).ravel()
+        ms_o = np.zeros(int(n), np.float32)
+        ms_p = np.zeros(int(n), np.float32) if pairs else None
+        ck = C.c_int64()
+        _ck(lib().ig_debug_distance_law_time(self._h, _p(e), C.c_int32(int(e.size)), C.c_int32(int(bool(privatised))), C.c_int32(int(n)),
+                                             _p(ms_o), _p(ms_p), C.byref(ck)))
+        return ms_o, ms_p, int(ck.value)
 
     # ---- bookkeeping
     def renumber_contigs(self):

@@ -79,6 +79,23 @@ def estimate_rippe_host(sparse_matrix, np_sub_frags_2_frags, S_o_A_frags, n_frag
     return bins_upd, mean_contacts_upd, p, y_estim, mvt, opti.estimate_max_dist_intra(p, mvt)
 
 
+def fit_law(law, mean_value_trans):
+    """The fit of ``estimate_rippe_host`` (its last lines) on a law of the current genome (``distance_law.law_host`` or the
+    device's): x = the upper edges of the bins, as there; y = observed / pairs + the trans level for the bins whose mean is not
+    zero.  -> (bins_upd, mean_contacts_upd, p, y_estim, mean_value_trans / 10, d_max)"""
+    from .distance_law import mean_per_pair
+
+    bins = np.asarray(law["edges"][1:], np.float64)
+    mean = mean_per_pair(law)
+    mean_contacts = np.where(np.isnan(mean) | (mean == 0), np.nan, mean + mean_value_trans).astype(np.float32)
+    good = ~np.isnan(mean_contacts)
+    bins_upd = np.array(bins[good])
+    mean_contacts_upd = np.array(mean_contacts[good])
+    p, y_estim = opti.estimate_param_rippe(mean_contacts_upd, bins_upd)
+    mvt = mean_value_trans / 10.0  # CL:2338
+    return bins_upd, mean_contacts_upd, p, y_estim, mvt, opti.estimate_max_dist_intra(p, mvt)
+
+
 def problem_to_context(prob, params=None, device_id=0, rank=0, world=1):
     """Upload a synth.SynthProblem (contacts, sub-fragment table, state, fixed parameters)."""
     ctx = hip_lib.Context(device_id)
@@ -219,6 +236,9 @@ class sampler:  # noqa: N801 - the reference's class name
     def estimate_parameters_rippe(self, max_dist_kb, size_bin_kb, display_graph=False):
         """CL:2239-2372: binned mean cis contacts of the first n_frags/10 sub-fragment rows, leastsq fit,
         cis/trans cut-off; then the initial likelihood."""
+        if self.sparse_matrix is None:
+            raise ValueError("estimate_parameters_rippe walks the rows of the input matrix, which a sampler built from coo= does not "
+                             "keep: use estimate_parameters_from_genome (the law of the current genome, from the device)")
         self.bins = np.arange(size_bin_kb, max_dist_kb + size_bin_kb, size_bin_kb)
         self.bins_upd, self.mean_contacts_upd, p, self.y_estim, self.mean_value_trans, estim_max_dist = estimate_rippe_host(
             self.sparse_matrix, self.np_sub_frags_2_frags, self.S_o_A_frags, self.n_frags, self.mean_value_trans, max_dist_kb,
@@ -779,6 +799,74 @@ class sampler:  # noqa: N801 - the reference's class name
         ax.axis("off")
         fig.savefig(filename, dpi=200, bbox_inches="tight")
         return full_order, dict_contig, full_order_high
+
+    # ----------------------------------------------------------- distance law
+    def distance_law(self, edges_kb=None):
+        """The distance law P(s) of the current genome as the data shows it (``ig_distance_law``; the rule: ``distance_law.py``) next
+        to the model curve the sampler is using.  ``edges_kb``: ascending bin edges in kb, default ``distance_law.default_edges``
+        (geometric, from half a mean sub-fragment to beyond the longest contig).  -> the law's dict (edges, observed, pairs, the
+        scalars) plus ``mean_per_pair`` (observed / pairs, nan where a bin holds no pair), ``centres_kb``, ``model`` (the Rippe curve
+        under ``param_simu`` at the bin centres, the trans level beyond d_max: what a move is scored against; None without
+        parameters) and ``mean_value_trans_observed`` (trans_observed / trans_pairs, nan without trans pairs).  No reference
+        counterpart."""
+        from . import distance_law as dlaw
+
+        if edges_kb is None:
+            d = self.ctx.debug_tables()[0]  # kb from the start of the contig: its maximum bounds every separation
+            edges_kb = dlaw.default_edges(self.mean_kb(), float(d.max()) if d.size else 0.0)
+        law = self.ctx.distance_law(dlaw.check_edges(edges_kb))
+        law["mean_per_pair"] = dlaw.mean_per_pair(law)
+        law["centres_kb"] = dlaw.bin_centres(law["edges"])
+        law["model"] = None
+        if self.param_simu is not None:
+            kuhn, lm, c1, slope, d, d_max, fact, d_nuc = self.param_simu[0]
+            with np.errstate(all="ignore"):
+                y = np.asarray(opti.peval(law["centres_kb"], [kuhn, lm, slope, d, fact]), np.float64)
+            law["model"] = np.where(law["centres_kb"] < d_max, y, np.float64(d_nuc))
+        law["mean_value_trans_observed"] = law["trans_observed"] / law["trans_pairs"] if law["trans_pairs"] > 0 else float("nan")
+        return law
+
+    def display_distance_law(self, filename, edges_kb=None):
+        """Writes a log-log plot of the observed per-pair means and of the model curve; returns what ``distance_law`` returns."""
+        law = self.distance_law(edges_kb)
+        # matplotlib only here, and without pyplot (as display_current_matrix)
+        from matplotlib.backends.backend_agg import FigureCanvasAgg
+        from matplotlib.figure import Figure
+
+        fig = Figure(figsize=(8, 6))
+        FigureCanvasAgg(fig)
+        ax = fig.subplots()
+        x, y = law["centres_kb"], law["mean_per_pair"]
+        ok = np.isfinite(y) & (y > 0) & (x > 0)
+        ax.loglog(x[ok], y[ok], "o", ms=3, label="observed contacts per pair")
+        if law["model"] is not None:
+            okm = (x > 0) & np.isfinite(law["model"]) & (law["model"] > 0)
+            ax.loglog(x[okm], law["model"][okm], "-", label="model (param_simu)")
+        if np.isfinite(law["mean_value_trans_observed"]) and law["mean_value_trans_observed"] > 0:
+            ax.axhline(law["mean_value_trans_observed"], ls=":", color="grey", label="observed trans level")
+        ax.set_xlabel("genomic separation s (kb)")
+        ax.set_ylabel("contacts per sub-fragment pair")
+        ax.legend()
+        fig.savefig(filename, dpi=150, bbox_inches="tight")
+        return law
+
+    def estimate_parameters_from_genome(self, max_dist_kb, size_bin_kb):
+        """``estimate_parameters_rippe`` on the law of the CURRENT genome instead of the first rows of the input matrix: works on a
+        sampler built from ``coo=`` and at any point of a run.  Linear edges ``arange(0, max_dist_kb + size_bin_kb, size_bin_kb)``;
+        the per-pair means of the bins that hold contacts, plus the trans level, at the bins' upper edges go through
+        ``opti.estimate_param_rippe`` and ``opti.estimate_max_dist_intra`` the way ``estimate_rippe_host`` composes them (the trans
+        level lowered tenfold before the cut-off is solved, CL:2338); then both parameter sets and the initial likelihood.  The
+        trans level is the sampler's ``mean_value_trans``."""
+        from . import distance_law as dlaw
+
+        edges = np.arange(0, max_dist_kb + size_bin_kb, size_bin_kb).astype(np.float32)
+        law = self.ctx.distance_law(dlaw.check_edges(edges))
+        self.bins_upd, self.mean_contacts_upd, p, self.y_estim, self.mean_value_trans, estim_max_dist = fit_law(law, self.mean_value_trans)
+        self.bins = np.array(law["edges"][1:], np.float64)
+        self.set_param_simu(self.setup_rippe_parameters(p, estim_max_dist), 0)
+        self.set_param_simu(self.param_simu, 1)
+        self.eval_likelihood_init()
+        return law
 
     def free_gpu(self):  # CL:3167-3177
         self.ctx.close()

@@ -193,7 +193,7 @@ class instagraal_class:
         self.collect_id_fB_sampled.append(id_f_sampled)
         self.collect_id_fA_sampled.append(id_frag)
 
-    def full_em(self, n_cycles, n_neighbours, bomb, id_start_sample_param, save_matrix=False):  # IG:196-291
+    def full_em(self, n_cycles, n_neighbours, bomb, id_start_sample_param, save_matrix=False, save_law=False):  # IG:196-291
         sampler = self.simulation.sampler
         if bomb:
             sampler.bomb_the_genome()
@@ -232,6 +232,10 @@ class instagraal_class:
                 import warnings
 
                 warnings.warn("could not write the matrix at cycle %d: %s" % (j, e))
+            if save_law:  # (no reference counterpart: the distance law of the genome behind this cycle)
+                from . import distance_law as dlaw
+
+                dlaw.write_law(self._out("distance_law_cycle_%d.txt" % j), sampler.distance_law())
         self.save_behaviour_to_txt()
 
     def save_behaviour_to_txt(self):  # IG:293-330
@@ -246,13 +250,15 @@ class instagraal_class:
 
 
 def run_instagraal(hic_folder, reference_fa, output_folder=None, level=4, cycles=100, coverage_std=1, neighborhood=5, device=0,
-                   circular=False, bomb=False, pyramid_only=False, save_pickle=False, save_matrix=False, simple=False):
+                   circular=False, bomb=False, pyramid_only=False, save_pickle=False, save_matrix=False, simple=False, save_law=False):
     """IG:502-581 (defaults of cli/main.py: level 4, 100 cycles, 5 neighbours, 1 std).  The three trailing switches of the
     reference's signature (IG:512-514) are accepted: ``save_pickle`` dumps the run object to ``graal.pkl`` as the reference
     tries to (IG:589-594: a warning when it cannot be pickled -- device handles here, h5py handles there); ``save_matrix``
     writes the contact map of the genome after every cycle to ``matrix_cycle_<j>.png`` (``display_current_matrix``, IG:279-284;
     built on the GPU, binned to at most 2048 pixels a side: DESIGN 4.10); ``simple`` calls ``instagraal_class.simple_start``, a
-    method the reference does not define (IG:582 raises AttributeError): refused."""
+    method the reference does not define (IG:582 raises AttributeError): refused.  ``save_law`` (an addition: the reference has
+    nothing like it) writes the distance law of the genome after every cycle to ``distance_law_cycle_<j>.txt`` (columns edge_lo,
+    edge_hi, observed, pairs: ``sampler.distance_law``)."""
     import warnings
 
     if simple and not pyramid_only:
@@ -271,7 +277,7 @@ def run_instagraal(hic_folder, reference_fa, output_folder=None, level=4, cycles
         warnings.warn("--circular has no effect on the assembly (as in the reference: instagraal.py:569-570 sets the flag "
                       "after the sampler copied the fragment arrays)")
         p2.simulation.level.S_o_A_frags["circ"] += 1
-    p2.full_em(n_cycles=cycles, n_neighbours=neighborhood, bomb=bomb, id_start_sample_param=4, save_matrix=save_matrix)
+    p2.full_em(n_cycles=cycles, n_neighbours=neighborhood, bomb=bomb, id_start_sample_param=4, save_matrix=save_matrix, save_law=save_law)
     if save_pickle:  # IG:589-594
         import pickle
 
