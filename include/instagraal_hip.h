@@ -149,6 +149,9 @@ int ig_set_batch_width(int w);                        /* W in 1..64 (default 24,
  * lies behind its first conflict: rounds 1 - 4); w in 2..64: slots of the window (default 48, env IG_WINDOW). */
 int ig_set_window(int w);
 int ig_batch_stats(ig_ctx* ctx, int64_t out4[4]);     /* {batches, moves committed in-batch, one-move tails, predicted deltas used} */
+/* {contacts in the CSR rows the slice kernel walked (every touched contig of a move slot once), contacts in the rows a walk per
+ * candidate would have read} since the handle was created */
+int ig_slice_walk_stats(ig_ctx* ctx, int64_t out2[2]);
 int ig_scratch_bytes(ig_ctx* ctx, int64_t out3[3]);   /* move buffers: {per-window arrays, slice pool, per-slot records and lists} */
 
 /* ---- a move and the nuisance step behind it, in flight together (instagraal.py:217-262 for cycles > 4: step_sampler, then

@@ -71,6 +71,7 @@ struct CandMeta {
     int flags[12], pos_up[6], pos_down[6];
     /* slice windows (KA:530-548) */
     int pos_fa, pos_fb, up_fa, down_fa, up_fb, down_fb;
+    int rows_a; /* contacts in the CSR rows of the focal contig (k_mutate, with the row ranges): k_offsets' count of the rows k_slice walks */
 };
 
 struct ColMeta {
@@ -101,6 +102,9 @@ struct Glob {
     long long scr_cols, scr_cont; /* two-tier scoring: columns screened, columns scored exactly */
     long long scr_void_cols; /* columns whose screening bound was void */
     long long scr_terms, scr_terms_exact; /* ... and the (contact, column) terms in them */
+    /* contacts in the rows k_slice's planes walk (every touched contig of a slot once), and in the rows a plan with a walk of
+     * its own per candidate in the focal contig and per candidate of another contig would have walked (k_offsets) */
+    long long slice_walked, slice_walked_per_cand;
     int dbg[8]; /* what raised Glob.error (diagnostics: printed with a consistency failure) */
 };
 

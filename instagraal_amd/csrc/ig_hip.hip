@@ -12,7 +12,7 @@
  *   k_mutate        W x C x 25 WGs  one candidate genome per workgroup, operators applied in place on the local window,
  *                                   coordinate columns + zero-pixel sums
  *   k_offsets       1 workgroup     slice-list starts in the pool
- *   k_slice         row-parallel    CSR rows of the touched contigs -> compacted slice lists (the focal contig's rows once per move)
+ *   k_slice         row-parallel    CSR rows of the touched contigs -> compacted slice lists (every touched contig's rows once per move slot)
  *   k_screen_tail   the hot kernel  two tiers, first: every (contact, column) term in float with a rigorous bound; its first
  *                                   workgroups: quirk Q5, the last S_c mod 64 contacts of every list (k_tail on a second
  *                                   stream where a batch is not screened)

@@ -193,25 +193,27 @@ static void enqueue_score(ig_ctx* c, int move0, int W, int max_c, int force_slot
         if (force_slot < 0 && nW > 0) {
             if (!par_only) {
                 TimedLaunch t(c, T_SLICE);
-                hipLaunchKernelGGL(k_offsets, dim3(1), dim3(OFFSETS_THREADS), 0, c->stream, c->mb, W, w_begin, w_end, max_c);
+                hipLaunchKernelGGL(k_offsets, dim3(1), dim3(OFFSETS_THREADS), 0, c->stream, c->mb, c->glob, W, w_begin, w_end, max_c);
                 /* a wave walks a row (a workgroup 4 rows at a time).  Measured at cfg3 (us per launch of 24 slots): 32 workgroups per
                  * candidate 193, 64: 156, 96: 148, 128: 136, 256 with the chunks of a row dealt to several waves: 146 */
                 /* ... and with the lists in 8 segments (round 3), workgroups per plane -> moves/s: cfg3 24: 43.1 k, 32: 44.2, 40: 45.5, 48: 45.2 - 45.7,
                  * 64: 45.4, 80: 45.3, 96: 44.6, 128: 43.9; cfg2 32: 57.3 k, 48: 55.9, 96: 55.5; cfg5 32: 28.4 k, 48: 29.9, 96: 30.1; bigctg 32: 5.3 k,
-                 * 48: 5.75, 96: 5.93 -- the count follows the contacts a plane holds (two contigs' rows: 2 Z / contigs of the last batch) */
+                 * 48: 5.75, 96: 5.93 -- the count follows the contacts a plane holds (two contigs' rows: 2 Z / contigs of the last batch);
+                 * those sweeps predate the shared walks of k_slice (every touched contig once per slot: the planes of a slot now share the rows of
+                 * 3.7 contigs instead of 6 at cfg3); SLICE_RB_CONTACTS has not been swept again since */
                 const int rb_auto = c->n_contigs_seen > 0
-                                        ? std::min(SLICE_RB, std::max(32, (int)(2.0 * (double)c->Z / (double)c->n_contigs_seen / 2100.0)))
+                                        ? std::min(SLICE_RB, std::max(32, (int)(2.0 * (double)c->Z / (double)c->n_contigs_seen / SLICE_RB_CONTACTS)))
                                         : SLICE_RB;
                 /* (a batch of ONE -- ig_step_draw -- is six planes: 32 - 96 workgroups each leave most of the 256 CUs idle and a long row
                  * to one wave.  Workgroups per plane at that width -> median of a call at cfg3: auto 147 us, 96: 146, 192: 143, 384: 144) */
                 const int rb = nW == 1 ? std::max(rb_auto, 192) : rb_auto;
-                const int s_share = 1, s_maxj = 1 << 20; /* A's rows once per move */
+                const int s_maxj = 1 << 20;
                 if (c->mb.packed)
                     hipLaunchKernelGGL(k_slice<true>, dim3(rb, max_c + 1, nW), dim3(256), 0, c->stream, c->rowptr, c->cc, c->tab, c->glob, c->mb, c->rank,
-                                       c->world, w_begin, s_share, s_maxj);
+                                       c->world, w_begin, s_maxj);
                 else
                     hipLaunchKernelGGL(k_slice<false>, dim3(rb, max_c + 1, nW), dim3(256), 0, c->stream, c->rowptr, c->cc, c->tab, c->glob, c->mb, c->rank,
-                                       c->world, w_begin, s_share, s_maxj);
+                                       c->world, w_begin, s_maxj);
             }
             if (par_only && nWp > 0)
                 hipLaunchKernelGGL(k_rescore_prepare, dim3(NSLOT, max_c, nWp), dim3(256), 0, c->stream, c->glob, c->mb, pz, pb);
@@ -1011,6 +1013,19 @@ extern "C" int ig_batch_stats(ig_ctx* c, int64_t out3[4])
     out3[1] = c->n_batch_committed;
     out3[2] = c->n_batch_pending;
     out3[3] = c->n_batch_predicted;
+    return 0;
+}
+
+/* {contacts in the CSR rows k_slice walked, contacts in the rows a walk per candidate would have read} since the handle was created */
+extern "C" int ig_slice_walk_stats(ig_ctx* c, int64_t out2[2])
+{
+    IG_JOIN(c);
+    HIPCK(hipSetDevice(c->device));
+    HIPCK(hipStreamSynchronize(c->stream));
+    long long h[2] = {0, 0};
+    HIPCK(hipMemcpy(h, (const char*)c->glob + offsetof(Glob, slice_walked), sizeof h, hipMemcpyDeviceToHost));
+    out2[0] = h[0];
+    out2[1] = h[1];
     return 0;
 }
 

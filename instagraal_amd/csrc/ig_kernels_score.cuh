@@ -368,7 +368,9 @@ __device__ __forceinline__ void mutate_one(const State& st, const Tables& tab, c
     int* subs = mb.subs + (size_t)cw * M;
     long long hi = 0, lo = 0, ni = 0;
     __shared__ long long seg_bound[SLICE_SEG];
+    __shared__ int rows_a; /* (k == 0) contacts in the focal contig's rows */
     if (threadIdx.x < SLICE_SEG) seg_bound[threadIdx.x] = 0;
+    if (threadIdx.x == 0) rows_a = 0;
     __syncthreads();
     for (int x = threadIdx.x; x < n; x += blockDim.x) {
         const int f = S.gid[x];
@@ -399,6 +401,7 @@ __device__ __forceinline__ void mutate_one(const State& st, const Tables& tab, c
                 /* upper bound of the slice segment this row appends to; the row's range for k_slice */
                 const long long rb = rowptr[s], re = rowptr[s + 1];
                 atomicAdd((unsigned long long*)&seg_bound[ls & (mb.nseg - 1)], (unsigned long long)(re - rb));
+                if (ls < m.SLA) atomicAdd(&rows_a, (int)(re - rb));
                 mb.rowbe[(size_t)cw * M + ls] = make_int4((int)(unsigned)rb, (int)(rb >> 32), (int)(re - rb), s);
             }
             if (npos == 0) ni += ((long long)SLc * (long long)(SLc - 1)) / 2;
@@ -433,6 +436,7 @@ __device__ __forceinline__ void mutate_one(const State& st, const Tables& tab, c
         q[Q_NI + k] = s2;
     }
     if (k == 0 && threadIdx.x < SLICE_SEG) mb.slbound[(size_t)cw * SLICE_SEG + threadIdx.x] = seg_bound[threadIdx.x];
+    if (k == 0 && threadIdx.x == 0) mb.meta[cw].rows_a = rows_a;
 }
 
 /* k_mutate: the 25 genomes of every candidate of the move slots [w_begin, w_begin + gridDim.z) */
@@ -462,7 +466,7 @@ __global__ void __launch_bounds__(256) k_mutate_winners(State st, Tables tab, co
 /* k_offsets: where each candidate's slice list starts in the pool = exclusive prefix sum of the upper bounds
  * (one small workgroup; a slot whose lists do not fit is flagged and re-run at the head of the next batch) */
 #define OFFSETS_THREADS 1024
-__global__ void __launch_bounds__(OFFSETS_THREADS) k_offsets(MoveBuf mb, int W, int w_begin, int w_end, int max_c)
+__global__ void __launch_bounds__(OFFSETS_THREADS) k_offsets(MoveBuf mb, Glob* g, int W, int w_begin, int w_end, int max_c)
 {
     /* entries = (slot, candidate, segment) in this order; thread t owns `per` consecutive entries; exclusive scan of the
      * per-thread sums across the workgroup (wave scans + one LDS step) */
@@ -473,9 +477,16 @@ __global__ void __launch_bounds__(OFFSETS_THREADS) k_offsets(MoveBuf mb, int W, 
     const int n_idx = (w_end - w_begin) * max_c;
     const bool can_order = n_idx <= IG_MAX_BATCH * IG_MAX_CANDIDATES && n_idx <= (int)OFFSETS_THREADS;
     long long my_tot = 0;
+    int my_ctgA = -1, my_ctgB = -1, my_rows_a = 0; /* (for the count of the rows k_slice walks, at the end) */
     if (can_order && tid < n_idx) {
         const int w = w_begin + tid / max_c, c = tid % max_c;
         const bool used = c < mb.ctl[PS(w)].C && !KEPT(w);
+        if (c < mb.capC) {
+            const CandMeta& mt = mb.meta[CW(w, c)]; /* (stale behind the slot's last candidate, in bounds: `used` decides) */
+            my_ctgA = mt.ctgA;
+            my_ctgB = used ? mt.ctgB : -1;
+            my_rows_a = mt.rows_a;
+        }
         for (int sg = 0; sg < SLICE_SEG; sg++) {
             const long long b = mb.slbound[(size_t)CW(w, c) * SLICE_SEG + sg]; /* (requested whether used or not: no wait in front of the scan) */
             my_tot += (used && b > 0) ? b : 0;
@@ -542,8 +553,35 @@ __global__ void __launch_bounds__(OFFSETS_THREADS) k_offsets(MoveBuf mb, int W, 
      * candidate's lists (two grown contigs: ten times the median), and the long ones handed out last were the launch's tail
      * (the totals were requested at the top: their round trips ran next to the scan's) */
     if (can_order) {
-        if (tid < n_idx) s_tot[tid] = my_tot;
+        __shared__ int s_cB[IG_MAX_BATCH * IG_MAX_CANDIDATES];
+        if (tid < n_idx) {
+            s_tot[tid] = my_tot;
+            s_cB[tid] = my_ctgB;
+        }
         __syncthreads();
+        /* the contacts in the rows k_slice walks for this launch (Glob.slice_walked): a thread per slot -- its first candidate's --
+         * adds the focal contig's rows and those of every other contig once; next to it what a walk per candidate would have read */
+        if (tid < n_idx && tid % max_c == 0 && my_ctgB >= 0 && !s_over[(w_begin + tid / max_c)]) {
+            long long walked = my_rows_a, per_cand = 0;
+            bool other = false;
+            for (int c = 0; c < max_c; c++) {
+                const int cB = s_cB[tid + c];
+                if (cB < 0) continue;
+                if (cB == my_ctgA) {
+                    per_cand += my_rows_a;
+                    continue;
+                }
+                other = true;
+                const long long rows_b = s_tot[tid + c] - my_rows_a;
+                per_cand += rows_b;
+                bool first = true;
+                for (int c2 = 0; c2 < c; c2++) first = first && (s_cB[tid + c2] != cB);
+                if (first) walked += rows_b;
+            }
+            if (other) per_cand += my_rows_a;
+            atomic_add_ll(&g->slice_walked, walked);
+            atomic_add_ll(&g->slice_walked_per_cand, per_cand);
+        }
         if (tid < n_idx) {
             int rank = 0;
             for (int u = 0; u < n_idx; u++) rank += (s_tot[u] > my_tot) || (s_tot[u] == my_tot && u < tid);
@@ -578,95 +616,112 @@ __global__ void __launch_bounds__(OFFSETS_THREADS) k_offsets(MoveBuf mb, int W, 
 #ifndef SLICE_RB
 #define SLICE_RB 96 /* workgroups (of 4 rows at a time) per candidate plane (with the one-bit partner filter: 64 .. 128 within 3 %, 32: +15 %, 256: +20 %) */
 #endif
+#ifndef SLICE_RB_CONTACTS
+#define SLICE_RB_CONTACTS 2100.0 /* contacts of a plane's two contigs per workgroup of the plane (rb_auto, ig_host_batch.inc) */
+#endif
 #ifndef SLICE_UNROLL
 #define SLICE_UNROLL 4
 #endif
 #ifndef SLICE_MIN_WAVES
 #define SLICE_MIN_WAVES 8 /* eight workgroups per CU need <= 80 SGPRs (81 admit seven: MI355X_MICROARCH.md, residency) */
 #endif
-/* grid: (workgroups, candidates + 1, slots).  The rows of the focal contig A are the same for every candidate of a move whose
- * partner lies in another contig, and so are the contacts read from them and the partners' records gathered: the first plane
- * walks A's rows ONCE for all those candidates (a contact inside A goes to every list, one into B_c to candidate c's), the
- * candidates' planes walk the rows of B_c only (all rows where A and B_c are one contig: the windowed predicate of
- * KA:565-586 is the candidate's own).  40 % fewer (row, contact chunk) chains per move at five candidates.
+/* grid: (workgroups, candidates + 1, slots).  Every touched contig's rows are walked ONCE per slot, whatever the number of candidates
+ * that read them: the contacts of a row and the partners' records gathered for them are the same for all of them, only the keep
+ * test is the candidate's own.
+ *   - the focal contig A's rows serve EVERY candidate of the slot: a candidate in another contig B_c keeps a contact whose partner
+ *     lies in A or B_c; a candidate in A itself keeps the partners in A, under its own window where CandMeta.windowed is set (the
+ *     ca || cb test of slice_keep: the four bounds are staged per candidate in LDS).  Local row and column are the rank in A for
+ *     all of them.
+ *   - the rows of another contig B serve every candidate whose partner lies in B (the lowest one's row ranges are read; they are
+ *     the same in every such window: A's sub-fragments first, then B's).
+ * Each candidate still appends to its own lists and segment cursors and adds its own row counts.  The grid keeps a plane per
+ * candidate in front of the focal one (y == 0): the planes whose candidate is served by another plane's rows (a candidate in A; the
+ * second candidate of a contig B) share that contig's (row, chunk) items with it, so that as many row chains are in flight as
+ * there are waves -- too few of them is what sank the variants below.
  * Measured and dropped: several shared planes (slower), the cursors one per 128-byte line (no change), write-through / non-temporal
  * list stores (no change / slower), one workgroup per (segment, slot) with the cursors in LDS (190 us: too few chains in
  * flight), counting pass + writing pass without atomics (178 us: the rows are read twice). */
 template <bool PACKED>
 __global__ void __launch_bounds__(256, SLICE_MIN_WAVES) k_slice(const long long* __restrict__ rowptr, const int2* __restrict__ cc, Tables tab,
-                                                                 Glob* g, MoveBuf mb, int rank, int world, int w_begin, int share_rows, int max_j)
+                                                                 Glob* g, MoveBuf mb, int rank, int world, int w_begin, int max_j)
 {
     const int w = mb.order[mb.capC * mb.capW + blockIdx.z]; /* (the slots with the longest rows first: k_offsets; w_begin + z without it) */
     if (KEPT(w)) return;
-    const bool shared_plane = (blockIdx.y == 0); /* first: its waves write every kept contact once per candidate */
-    const int cand_plane = (int)blockIdx.y - 1;
+    const int cand_plane = (int)blockIdx.y - 1; /* -1: the focal plane */
     __shared__ long long seg_off[IG_MAX_CANDIDATES][SLICE_SEG];
-    __shared__ int s_cw[IG_MAX_CANDIDATES], s_ctgB[IG_MAX_CANDIDATES], s_idx[IG_MAX_CANDIDATES], s_nc;
-    __shared__ int a_same[IG_MAX_CANDIDATES], a_ctgB[IG_MAX_CANDIDATES], a_SLA, a_ctgA, a_mloc[IG_MAX_CANDIDATES];
+    __shared__ int s_cw[IG_MAX_CANDIDATES], s_ctgB[IG_MAX_CANDIDATES], s_idx[IG_MAX_CANDIDATES], s_won[IG_MAX_CANDIDATES];
+    __shared__ int4 s_win[IG_MAX_CANDIDATES]; /* {up_fa, down_fa, up_fb, down_fb} of a windowed candidate */
+    __shared__ int s_nc, s_focal, s_share, s_part, s_rows, a_SLA, a_ctgA;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const unsigned long long lt_mask = (1ull << lane) - 1ull;
     /* ONE round trip for everything the prologue needs (this launch is tens of thousands of short waves: every dependent load in
-     * front of the rows counts): the slot's candidate count, the few fields of every candidate's window, every list start */
+     * front of the rows counts): the slot's candidate count, the few fields of every candidate's window, every list start.  The
+     * first wave then lays out the plane with ballots, lane c speaking for candidate c: which contig's rows the plane walks,
+     * which candidates they serve, and which share of the (row, chunk) items is this plane's */
     const int C = mb.ctl[PS(w)].C;
     const int capC = min(mb.capC, IG_MAX_CANDIDATES);
-    if ((int)threadIdx.x < capC) {
-        const CandMeta& mt = mb.meta[CW(w, threadIdx.x)]; /* (entries behind the slot's last candidate: stale but in bounds, not used) */
-        a_same[threadIdx.x] = mt.same;
-        a_ctgB[threadIdx.x] = mt.ctgB;
-        a_mloc[threadIdx.x] = mt.m_loc;
-        if (threadIdx.x == 0) {
-            a_SLA = mt.SLA; /* the focal contig is every candidate's */
-            a_ctgA = mt.ctgA;
+    if (wv == 0) {
+        const bool have = lane < capC && lane < C;
+        int same = 0, ctgB = -1, mloc = 0, won = 0, SLA = 0, ctgA = -1;
+        int4 win = make_int4(0, 0, 0, 0);
+        if (have) {
+            const CandMeta& mt = mb.meta[CW(w, lane)];
+            same = mt.same;
+            ctgB = mt.ctgB;
+            mloc = mt.m_loc;
+            won = mt.windowed;
+            win = make_int4(mt.up_fa, mt.down_fa, mt.up_fb, mt.down_fb);
+            SLA = mt.SLA; /* the focal contig is every candidate's */
+            ctgA = mt.ctgA;
+        }
+        const int cp = min(max(cand_plane, 0), 63);
+        const int p_same = __shfl(same, cp, 64), p_ctgB = __shfl(ctgB, cp, 64);
+        const bool focal = cand_plane < 0 || cand_plane >= C || p_same != 0; /* this plane walks A's rows (a plane behind the slot's last candidate helps there) */
+        const bool served = have && (focal || ctgB == p_ctgB);
+        const bool walker = lane < (int)gridDim.y - 1 && (focal ? (lane >= C || same != 0) : (have && ctgB == p_ctgB)); /* plane lane + 1 walks the same rows */
+        const unsigned long long m_served = __ballot(served), m_walker = __ballot(walker);
+        if (served) {
+            const int at = __popcll(m_served & lt_mask);
+            s_idx[at] = lane;
+            s_cw[at] = CW(w, lane);
+            s_ctgB[at] = ctgB;
+            s_won[at] = won;
+            s_win[at] = win;
+            if (at == 0) s_rows = focal ? SLA : mloc - SLA;
+        }
+        if (lane == 0) {
+            s_nc = __popcll(m_served);
+            s_focal = focal ? 1 : 0;
+            s_share = __popcll(m_walker) + (focal ? 1 : 0);
+            s_part = cand_plane < 0 ? 0 : __popcll(m_walker & ((1ull << cp) - 1ull)) + (focal ? 1 : 0);
+            a_SLA = SLA;
+            a_ctgA = ctgA;
         }
     }
     for (int i = threadIdx.x; i < capC * SLICE_SEG; i += blockDim.x) seg_off[i / SLICE_SEG][i % SLICE_SEG] = mb.sloff[(size_t)CW(w, i / SLICE_SEG) * SLICE_SEG + i % SLICE_SEG];
     __syncthreads();
-    if (threadIdx.x == 0) {
-        int nc = 0;
-        if (shared_plane) {
-            if (share_rows)
-                for (int c = 0; c < C; c++)
-                    if (!a_same[c]) {
-                        s_idx[nc] = c;
-                        s_cw[nc] = CW(w, c);
-                        s_ctgB[nc++] = a_ctgB[c];
-                    }
-        } else if (cand_plane < C) {
-            s_idx[0] = cand_plane;
-            s_cw[0] = CW(w, cand_plane);
-            s_ctgB[0] = a_ctgB[cand_plane];
-            nc = 1;
-        }
-        s_nc = nc;
-    }
-    __syncthreads();
     const int nc = s_nc;
     if (nc == 0) return;
     if (seg_off[0][0] < 0) return; /* slice pool exhausted (k_offsets flags all segments of a slot together) */
-    const int cw0 = s_cw[0], c0 = s_idx[0];
-    const CandMeta& m = mb.meta[cw0]; /* only the windowed predicate of a candidate in A's own contig reads it */
     const int M = mb.sM;
-    const bool m_same = a_same[c0] != 0;
-    /* the rows this plane walks: A's (shared plane), B's (a candidate in another contig, A's being walked by the shared plane), all */
-    const bool own_all = !shared_plane && (m_same || !share_rows);
+    const bool focal = s_focal != 0;
+    /* the rows this plane walks: A's, or those of the served candidates' contig B (behind A's in their windows) */
     const int SLA = a_SLA, ctgA = a_ctgA;
-    const int row_lo = (shared_plane || own_all) ? 0 : SLA;
-    const int n_rows = shared_plane ? SLA : (a_mloc[c0] - row_lo);
-    const int4* rowbe = mb.rowbe + (size_t)cw0 * M;
-    const int ctgB0 = s_ctgB[0];
+    const int row_lo = focal ? 0 : SLA;
+    const int n_rows = s_rows;
+    const int4* rowbe = mb.rowbe + (size_t)s_cw[0] * M;
     /* work items = (row, j): wave j of a row takes the row's contact chunks j, j + J, ... (J waves per row: a row of thousands
-     * of contacts is a chain of dependent round trips per chunk, and the launch waits for the longest chain) */
-    const int nrw = gridDim.x * 4;
+     * of contacts is a chain of dependent round trips per chunk, and the launch waits for the longest chain); the planes that
+     * walk the same rows deal the items out among all their waves */
+    const int nrw = gridDim.x * 4 * s_share;
     const int J = min(max_j, max(1, nrw / max(n_rows, 1)));
-    for (int item = blockIdx.x * 4 + wv; item < n_rows * J; item += nrw) {
+    for (int item = (s_part * gridDim.x + blockIdx.x) * 4 + wv; item < n_rows * J; item += nrw) {
         const int r = row_lo + item % n_rows, j = item / n_rows;
         const int seg = r & (mb.nseg - 1);
         /* the row's range, written by k_mutate next to the window's sub-fragment list: ONE round trip in front of the contacts;
          * its (contig, rank) follows from its place in the window (A's sub-fragments first, by rank, then B's) */
         const int4 be = rowbe[r];
         const long long b = (long long)(unsigned)be.x | ((long long)be.y << 32), e = b + be.z;
-        const bool in_a = m_same || r < SLA;
-        const int2 cp1 = make_int2(in_a ? ctgA : ctgB0, in_a ? r : r - SLA);
         const bool mine = (world <= 1) || ((r % world) == rank);
         int rc = 0; /* lane k: contacts of this row kept for candidate k */
         if (b != e) {
@@ -686,11 +741,16 @@ __global__ void __launch_bounds__(256, SLICE_MIN_WAVES) k_slice(const long long*
                     bool keep[SLICE_UNROLL];
                     unsigned long long mask[SLICE_UNROLL];
                     int add = 0;
-                    const int ctgB = s_ctgB[k];
+                    const int ctgB = s_ctgB[k]; /* (a candidate in A: ctgB == ctgA) */
+                    const bool won = s_won[k] != 0; /* set for candidates in A only: the rows are A's */
+                    const int4 wn = s_win[k];
 #pragma unroll
                     for (int u = 0; u < SLICE_UNROLL; u++) {
-                        if (own_all) keep[u] = (v[u].x >= 0) && slice_keep(m, cp1.x, cp2[u].x, cp1.y, cp2[u].y, v[u].y, false);
-                        else keep[u] = (v[u].x >= 0) && (v[u].y > 0) && ((cp2[u].x == ctgA) || (cp2[u].x == ctgB)); /* slice_keep, two contigs */
+                        keep[u] = (v[u].x >= 0) && (v[u].y > 0) && ((cp2[u].x == ctgA) || (cp2[u].x == ctgB)); /* slice_keep */
+                        if (won) { /* ... and its window (row and partner in A: rank r and cp2.y) */
+                            const int px = min(r, cp2[u].y), py = max(r, cp2[u].y);
+                            keep[u] = keep[u] && (((px <= wn.y) && (py >= wn.x)) || ((py >= wn.z) && (px <= wn.w)));
+                        }
                         mask[u] = __ballot(keep[u]);
                         add += __popcll(mask[u]);
                     }
@@ -706,7 +766,7 @@ __global__ void __launch_bounds__(256, SLICE_MIN_WAVES) k_slice(const long long*
                     for (int u = 0; u < SLICE_UNROLL; u++) {
                         if (keep[u]) {
                             const long long at = off + (long long)base + o2 + __popcll(mask[u] & lt_mask);
-                            const int lj = ((m_same || cp2[u].x == ctgA) ? 0 : SLA) + cp2[u].y;
+                            const int lj = ((cp2[u].x == ctgA) ? 0 : SLA) + cp2[u].y;
                             if (PACKED) {
                                 mb.sl_pk[at] = (unsigned long long)r | ((unsigned long long)lj << 20) | ((unsigned long long)v[u].y << 40);
                             } else {

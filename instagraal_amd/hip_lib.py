@@ -611,7 +611,10 @@ class Context:
     def batch_stats(self):
         o = np.zeros(4, np.int64)
         _ck(lib().ig_batch_stats(self._h, _p(o)))
-        return dict(batches=int(o[0]), committed_in_batch=int(o[1]), one_move_tails=int(o[2]), predicted_deltas=int(o[3]))
+        w = np.zeros(2, np.int64)  # contacts in the CSR rows the slice kernel walked / that a walk per candidate would have read
+        _ck(lib().ig_slice_walk_stats(self._h, _p(w)))
+        return dict(batches=int(o[0]), committed_in_batch=int(o[1]), one_move_tails=int(o[2]), predicted_deltas=int(o[3]),
+                    slice_contacts_walked=int(w[0]), slice_contacts_walked_per_candidate=int(w[1]))
 
     def scratch_bytes(self):
         """bytes of the move buffers: (per-window arrays, slice pool, the rest)"""
