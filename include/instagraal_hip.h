@@ -263,6 +263,28 @@ int ig_contact_map(ig_ctx* ctx, int32_t max_side, int64_t* image, int64_t image_
  * shard's rows to observed and the observed scalars -- the ranks' results sum to the whole -- and computes the pairs whole. */
 int ig_distance_law(ig_ctx* ctx, const float* edges, int32_t n_edges, int64_t* observed, int64_t* pairs, int64_t scalars[8]);
 
+/* ---- the junction support profile of the current genome (no reference counterpart; the rule: instagraal_amd/junction_profile.py) --
+ * Positions: the contact map's -- the placed sub-fragments in the order of ig_contact_map_order, 0 .. T - 1.  Junction j, 1 <= j <= T - 1,
+ * lies between the positions j - 1 and j; the arrays have T entries indexed by j, entry 0 is 0.  window: 1 .. 1024 positions.
+ * observed[j]: sum of the counts of the uploaded contacts with both ends placed in one contig that is not a ring, at positions
+ * pa < pb with pb - pa <= window and pa < j <= pb.  pairs[j]: the number of pairs of positions (i, k) of that contig with
+ * i < j <= k and k - i <= window, with or without a contact.  expected_q[j]: the sum over the same pairs of the model's value at
+ * s = fabsf(dist_i - dist_k) under the parameter set moves are scored under (set 0) -- ig_detmath.h's Rippe curve, quantised as every
+ * exact sum of the library is -- in units of 2^-32.
+ * At a contig boundary and inside a ring all three are 0.  pairs and expected_q may BOTH be NULL: the model pass is skipped.
+ * scalars: {0 in_window_observed, 1 beyond_window_observed (same linear contig, pb - pa > window), 2 trans_observed, 3 ring_observed,
+ * 4 unplaced_observed, 5 internal_junctions (both positions in one contig that is not a ring), 6 spanned_observed = sum(observed),
+ * 7 unused (0)}.  By construction scalars[0] + .. + [4] = sum of all counts and sum(observed) = sum of count * (pb - pa) over the
+ * in-window contacts.  64-bit integer sums: exact, the same from run to run, whatever the launch shapes.
+ * capacity: entries of room in each array; *n_placed = T is set first, then capacity < T is an error and nothing is written.
+ * An error too, with nothing written: a parameter set under which the largest quantised model value times window (window + 1) / 2
+ * reaches 2^62 ("model value too large for this window": the sum could overflow).
+ * Guards and effects as ig_contact_map: reads the CURRENT coordinates, changes nothing a move reads, synchronous, an error while a
+ * nuisance step or a chain is in flight.  A sharded handle (ig_set_shard) adds its shard's rows to observed and the observed scalars
+ * -- the ranks' results sum to the whole -- and computes pairs and expected_q whole. */
+int ig_junction_profile(ig_ctx* ctx, int32_t window, int64_t* observed, int64_t* pairs, int64_t* expected_q, int64_t capacity,
+                        int32_t* n_placed, int64_t scalars[8]);
+
 /* ---- multi-GPU (contact shards) -------------------------- */
 /* Two-phase move: partial sums over this handle's contact shard are left in a device buffer of
  * ig_partials_count() int64 values; the caller all-reduces (SUM) it across ranks, then finishes. */
@@ -335,6 +357,12 @@ int ig_debug_contact_map_time(ig_ctx* ctx, int32_t max_side, int32_t combine, in
  * *checksum (may be NULL): the last observed pass's words, each weighted by its place: both forms must agree on it */
 int ig_debug_distance_law_time(ig_ctx* ctx, const float* edges, int32_t n_edges, int32_t privatised, int32_t n, float* ms_observed_n,
                                float* ms_pairs_n, int64_t* checksum);
+/* the junction profile's passes n times each, hipEvents around each: ms_observed_n[n] (zero + kernel) -- combine = 1: equal + ends
+ * summed inside the wave first, 0: one atomic per contact end (the yardstick) --, ms_model_n[n] (may be NULL: not run) and
+ * ms_scan_n[n] (may be NULL: the scan runs once, untimed); *checksum (may be NULL): the observed profile behind the last pass and
+ * its five scalars, each word weighted by its place: both forms must agree on it */
+int ig_debug_junction_profile_time(ig_ctx* ctx, int32_t window, int32_t combine, int32_t n, float* ms_observed_n, float* ms_model_n,
+                                   float* ms_scan_n, int64_t* checksum);
 #ifdef __cplusplus
 }
 #endif

@@ -351,6 +351,15 @@ struct LawBuf {
     int M = 0;
 };
 
+/* the junction support profile of the current genome (ig_kernels_junc.cuh): buffers kept from call to call */
+struct JuncBuf {
+    unsigned long long* diff = nullptr; /* [3][M + 1] difference words: observed, pairs, expected_q */
+    unsigned long long* prof = nullptr; /* [3][M + 1] their prefix sums: the profile */
+    unsigned long long* tot = nullptr;  /* [3][chunks] the scan's chunk totals */
+    unsigned long long* sc = nullptr;   /* JUNC_NS scalars */
+    int M = 0;
+};
+
 struct ig_ctx {
     int device;
     hipStream_t stream;
@@ -455,6 +464,7 @@ struct ig_ctx {
     MoveBuf mb;
     MapBuf map;
     LawBuf law;
+    JuncBuf junc;
     int* batch_out; /* committed moves, pending slot, (unused), candidates, predicted deltas used, contigs */
     int *host_bo, *host_bo_dev; /* the same in mapped host memory (+ [7] = sequence number of the decide launch), and its device address */
     int bo_seq;

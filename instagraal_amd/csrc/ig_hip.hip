@@ -25,7 +25,8 @@
  * from-scratch pass over all contacts: k_pack_tab_sig / k_nuis_prepare, k_tile_trans, k_full_nz_tiled; the
  * nuisance step's screened pass: k_hist_build / k_hist_walk / k_hist_eval (tier 0), k_full_diff_tiled (tier 1);
  * the contact map of the current genome: k_map_pixels, k_contact_map, k_map_mirror; its distance law:
- * k_law_records, k_law_sorted, k_law_observed, k_law_pairs.
+ * k_law_records, k_law_sorted, k_law_observed, k_law_pairs; its junction support profile: k_junc_observed,
+ * k_junc_count, k_junc_model, k_junc_scan_totals / _tops / _apply.
  *
  * Environment knobs (tests, fault injection and tuning only; the table in INTEGRATION.md section 4 is the reference): IG_BATCH_W, IG_WINDOW
  * (widths), IG_POOL_ENTRIES, IG_WIDE_LISTS, IG_NO_HOST_FLAG, IG_POISON_ALLOC / IG_POISON_ONLY (force the rare paths), IG_SCREEN,
@@ -47,12 +48,14 @@
 #include "ig_kernels_nuis.cuh"
 #include "ig_kernels_map.cuh"
 #include "ig_kernels_law.cuh"
+#include "ig_kernels_junc.cuh"
 
-/* ================================================================== host side (one translation unit, seven parts) */
+/* ================================================================== host side (one translation unit, eight parts) */
 #include "ig_host_core.inc"
 #include "ig_host_upload.inc"
 #include "ig_host_map.inc"
 #include "ig_host_law.inc"
+#include "ig_host_junc.inc"
 #include "ig_host_batch.inc"
 #include "ig_host_nuis.inc"
 #include "ig_host_debug.inc"

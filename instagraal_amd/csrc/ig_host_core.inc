@@ -3,6 +3,7 @@
 /* ================================================================== host side */
 static void free_map_buffers(ig_ctx* c);   /* ig_host_map.inc */
 static void free_law_buffers(ig_ctx* c);   /* ig_host_law.inc */
+static void free_junc_buffers(ig_ctx* c);  /* ig_host_junc.inc */
 static void flush_pending_sums(ig_ctx* c); /* behind a decisively accepted nuisance step: see k_nuis_promote */
 
 /* ---- the launches of a run's NEXT step on a helper thread ------------------------------------------------------------------
@@ -451,6 +452,7 @@ extern "C" void ig_destroy(ig_ctx* c)
     free_move_buffers(c);
     free_map_buffers(c);
     free_law_buffers(c);
+    free_junc_buffers(c);
     hipFree(c->st_block);
     hipFree(c->tab.dist);
     hipFree(c->tab_prev.dist);

@@ -20,20 +20,16 @@ static void free_law_buffers(ig_ctx* c)
     c->law = LawBuf{};
 }
 
-/* Argument checks, the guards of the map (map_prepare), then on the device: the genome order, the records of both passes, the
- * edges.  T: placed sub-fragments. */
-static int law_prepare(ig_ctx* c, const char* who, const float* edges, int n_edges, bool want_pairs, int* T_out)
+/* The records both passes read, without the edges (the junction profile shares them, ig_host_junc.inc): the guards of the map
+ * (map_prepare), the genome order, then on the library's stream k_law_records and, want_sorted, k_law_sorted.  Not waited for.
+ * T: placed sub-fragments. */
+static int law_records(ig_ctx* c, const char* who, bool want_sorted, int* T_out)
 {
-    if (!edges) return fail("%s: edges is NULL", who);
-    if (n_edges < 2 || n_edges > LAW_MAX_EDGES) return fail("%s: 2 <= n_edges <= %d (got %d)", who, LAW_MAX_EDGES, n_edges);
-    for (int i = 0; i < n_edges; i++) {
-        if (!(edges[i] - edges[i] == 0.0f)) return fail("%s: edge %d is not finite", who, i);
-        if (i && edges[i] < edges[i - 1]) return fail("%s: the edges are not sorted (edge %d < edge %d)", who, i, i - 1);
-    }
     if (!c->have_contacts) return fail("%s: upload the contacts first", who);
     int T = 0, bin = 1, side = 0;
-    if (map_prepare(c, who, 1, true, &T, &bin, &side)) return -1;
-    LawBuf& l = c->law;
+    /* max_side = M >= T: one position per pixel, so rec.w is the position itself (the law reads its sign only, the junction
+     * profile the position) */
+    if (map_prepare(c, who, std::max(c->M, 1), true, &T, &bin, &side)) return -1;    LawBuf& l = c->law;
     const int M = c->M;
     if (l.M != M) {
         free_law_buffers(c);
@@ -45,11 +41,24 @@ static int law_prepare(ig_ctx* c, const char* who, const float* edges, int n_edg
         DALLOC(l.flag, 1);
         l.M = M;
     }
-    HIPCK(hipMemcpyAsync(l.edges, edges, (size_t)n_edges * sizeof(float), hipMemcpyHostToDevice, c->stream));
     hipLaunchKernelGGL(k_law_records, dim3((M + 255) / 256), dim3(256), 0, c->stream, c->tab, c->map.pix, M, l.rec);
-    if (want_pairs && T > 0) hipLaunchKernelGGL(k_law_sorted, dim3((T + 255) / 256), dim3(256), 0, c->stream, c->tab, c->map.order, M, T, l.ds, l.meta);
-    HIPCK(hipStreamSynchronize(c->stream)); /* (`edges` is the caller's pageable memory) */
+    if (want_sorted && T > 0) hipLaunchKernelGGL(k_law_sorted, dim3((T + 255) / 256), dim3(256), 0, c->stream, c->tab, c->map.order, M, T, l.ds, l.meta);
     *T_out = T;
+    return 0;
+}
+
+/* Argument checks, then the records of both passes and the edges on the device. */
+static int law_prepare(ig_ctx* c, const char* who, const float* edges, int n_edges, bool want_pairs, int* T_out)
+{
+    if (!edges) return fail("%s: edges is NULL", who);
+    if (n_edges < 2 || n_edges > LAW_MAX_EDGES) return fail("%s: 2 <= n_edges <= %d (got %d)", who, LAW_MAX_EDGES, n_edges);
+    for (int i = 0; i < n_edges; i++) {
+        if (!(edges[i] - edges[i] == 0.0f)) return fail("%s: edge %d is not finite", who, i);
+        if (i && edges[i] < edges[i - 1]) return fail("%s: the edges are not sorted (edge %d < edge %d)", who, i, i - 1);
+    }
+    if (law_records(c, who, want_pairs, T_out)) return -1;
+    HIPCK(hipMemcpyAsync(c->law.edges, edges, (size_t)n_edges * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIPCK(hipStreamSynchronize(c->stream)); /* (`edges` is the caller's pageable memory) */
     return 0;
 }
 

@@ -18,8 +18,8 @@ SRC = os.path.join(HERE, "csrc", "ig_hip.hip")
 SRC_HOST = os.path.join(HERE, "csrc", "ig_draw.cpp")  # host-only part: the candidate draw
 DEPS = [SRC, SRC_HOST] + [os.path.join(HERE, "csrc", f) for f in ("ig_ops.cuh", "ig_common.cuh", "ig_model.cuh", "ig_kernels_setup.cuh",
                                                           "ig_kernels_score.cuh", "ig_kernels_screen.cuh", "ig_kernels_commit.cuh",
-                                                          "ig_kernels_nuis.cuh", "ig_kernels_map.cuh", "ig_kernels_law.cuh", "ig_host_core.inc", "ig_host_upload.inc",
-                                                          "ig_host_map.inc", "ig_host_law.inc",
+                                                          "ig_kernels_nuis.cuh", "ig_kernels_map.cuh", "ig_kernels_law.cuh", "ig_kernels_junc.cuh", "ig_host_core.inc", "ig_host_upload.inc",
+                                                          "ig_host_map.inc", "ig_host_law.inc", "ig_host_junc.inc",
                                                           "ig_host_batch.inc", "ig_host_nuis.inc", "ig_host_debug.inc")] + \
        [os.path.join(ROOT, "include", f) for f in ("ig_detmath.h", "ig_detmath_tables.h", "instagraal_hip.h")]
 
@@ -681,6 +681,37 @@ class Context:
         _ck(lib().ig_debug_distance_law_time(self._h, _p(e), C.c_int32(int(e.size)), C.c_int32(int(bool(privatised))), C.c_int32(int(n)),
                                              _p(ms_o), _p(ms_p), C.byref(ck)))
         return ms_o, ms_p, int(ck.value)
+
+    # ---- the junction support profile of the current genome (the rule: junction_profile.py)
+    def junction_profile(self, window, model=True):
+        """per junction of the genome order the contacts that span it inside ``window`` positions, the pairs that could and the
+        model's quantised expectation -> dict: window, n_placed, observed, pairs, expected_q (int64 [n_placed]; the last two None
+        with ``model=False``) and the int64 scalars of ``junction_profile.SCALARS``"""
+        from .junction_profile import SCALARS
+
+        cap = max(self.M, 1)
+        obs = np.zeros(cap, np.int64)
+        prs = np.zeros(cap, np.int64) if model else None
+        exq = np.zeros(cap, np.int64) if model else None
+        sc = np.zeros(8, np.int64)
+        n = C.c_int32()
+        _ck(lib().ig_junction_profile(self._h, C.c_int32(int(window)), _p(obs), _p(prs), _p(exq), C.c_int64(cap), C.byref(n), _p(sc)))
+        T = n.value
+        out = dict(window=int(window), n_placed=T, observed=obs[:T].copy(), pairs=prs[:T].copy() if model else None,
+                   expected_q=exq[:T].copy() if model else None)
+        out.update((k, int(v)) for k, v in zip(SCALARS, sc))
+        return out
+
+    def debug_junction_profile_time(self, window, combine=True, n=1, model=True, scan=True):
+        """the profile's passes n times each with hipEvents around each -> (ms observed [n], ms model [n] or None, ms scan [n] or
+        None, checksum of the observed profile behind the last pass)"""
+        ms_o = np.zeros(int(n), np.float32)
+        ms_m = np.zeros(int(n), np.float32) if model else None
+        ms_s = np.zeros(int(n), np.float32) if scan else None
+        ck = C.c_int64()
+        _ck(lib().ig_debug_junction_profile_time(self._h, C.c_int32(int(window)), C.c_int32(int(bool(combine))), C.c_int32(int(n)), _p(ms_o),
+                                                 _p(ms_m), _p(ms_s), C.byref(ck)))
+        return ms_o, ms_m, ms_s, int(ck.value)
 
     # ---- bookkeeping
     def renumber_contigs(self):

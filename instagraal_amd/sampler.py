@@ -868,5 +868,74 @@ class sampler:  # noqa: N801 - the reference's class name
         self.eval_likelihood_init()
         return law
 
+    # ------------------------------------------------------- junction profile
+    def junction_profile(self, window=None, window_kb=None):
+        """The junction support profile of the current genome (``ig_junction_profile``; the rule: ``junction_profile.py``): per
+        junction between two neighbouring positions of the genome order the contacts that span it inside a window, the pairs that
+        could, and what the model in use (``param_simu``) expects of them.  ``window``: in positions (default 64), or ``window_kb``:
+        in kb, converted with the mean sub-fragment length.  -> the device's dict (window, n_placed, observed, pairs, expected_q,
+        the scalars) plus ``expected`` (f64), ``ratio`` (observed / expected, nan where expected is 0), ``kind`` (per junction:
+        ``junction_profile.KIND_*``), ``order`` (the sub-fragment at every position) and ``bins``: the table of the internal
+        junctions at which the parent bin changes -- the joins the moves made or could break -- with the columns
+        ``junction_profile.BIN_COLUMNS``.  No reference counterpart."""
+        from . import junction_profile as jp
+
+        if window is not None and window_kb is not None:
+            raise ValueError("junction_profile: window or window_kb, not both")
+        if window_kb is not None:
+            window = jp.window_from_kb(window_kb, self.mean_kb())
+        w = jp.check_window(jp.DEFAULT_WINDOW if window is None else window)
+        prof = self.ctx.junction_profile(w)
+        order = self.ctx.contact_map_order()
+        _, _, stot, _, _ = self.ctx.debug_tables()
+        parent = self.np_sub_frags_2_frags["x"].astype(np.int64)
+        contig = self.gpu_vect_frags.copy_from_gpu().id_c.astype(np.int64)[parent]
+        position = np.full(parent.size, -1, np.int64)
+        position[order] = np.arange(order.size)
+        prof["order"] = order
+        prof["kind"] = jp.junction_kinds(stot, contig, position)
+        prof["expected"] = jp.expected(prof)
+        prof["ratio"] = jp.ratio(prof)
+        prof["bins"] = jp.bin_table(prof, prof["kind"], parent[order], contig[order])
+        return prof
+
+    def weakest_junctions(self, n=20, min_pairs=None, window=None, window_kb=None, profile=None):
+        """The ``n`` bin-level junctions (rows of ``junction_profile()["bins"]``) with the lowest observed / expected: where to look
+        for a misjoin.  Only junctions whose window is at least half full count -- ``min_pairs`` defaults to half of
+        w (w + 1) / 2 -- so that the ends of the contigs, which have few pairs, do not crowd the list."""
+        from . import junction_profile as jp
+
+        prof = self.junction_profile(window, window_kb) if profile is None else profile
+        return jp.weakest(prof["bins"], n, jp.default_min_pairs(prof["window"]) if min_pairs is None else int(min_pairs))
+
+    def display_junction_profile(self, filename, window=None, window_kb=None):
+        """Writes a plot of observed / expected along the genome (log scale), the contig boundaries marked; returns what
+        ``junction_profile`` returns."""
+        from . import junction_profile as jp
+
+        prof = self.junction_profile(window, window_kb)
+        # matplotlib only here, and without pyplot (as display_current_matrix)
+        from matplotlib.backends.backend_agg import FigureCanvasAgg
+        from matplotlib.figure import Figure
+
+        fig = Figure(figsize=(14, 5))
+        FigureCanvasAgg(fig)
+        ax = fig.subplots()
+        y = np.where(prof["kind"] == jp.KIND_INTERNAL, prof["ratio"], np.nan)
+        ok = np.isfinite(y) & (y > 0)
+        x = np.arange(y.size)
+        if ok.any():
+            ax.semilogy(x[ok], y[ok], ".", ms=2, label="observed / expected (window of %d positions)" % prof["window"])
+        edges = np.nonzero(prof["kind"] == jp.KIND_BOUNDARY)[0]
+        for j in (edges if edges.size <= 2000 else edges[:0]):  # (beyond that the boundaries would be the picture)
+            ax.axvline(j, color="grey", lw=0.3)
+        ax.axhline(1.0, ls=":", color="black")
+        ax.set_xlabel("position in the genome order (sub-fragments)")
+        ax.set_ylabel("contacts across the junction: observed / expected")
+        if ok.any():
+            ax.legend()
+        fig.savefig(filename, dpi=150, bbox_inches="tight")
+        return prof
+
     def free_gpu(self):  # CL:3167-3177
         self.ctx.close()
