@@ -285,6 +285,32 @@ int ig_distance_law(ig_ctx* ctx, const float* edges, int32_t n_edges, int64_t* o
 int ig_junction_profile(ig_ctx* ctx, int32_t window, int64_t* observed, int64_t* pairs, int64_t* expected_q, int64_t capacity,
                         int32_t* n_placed, int64_t scalars[8]);
 
+/* ---- the contacts in the coordinates of the current genome (no reference counterpart on the device: the reference lifts the raw
+ * pairs over on the host; the rule: instagraal_amd/assembly_contacts.py) ---------------------------------------------------------
+ * Every uploaded contact (row, col, count) re-indexed to UNITS of the genome order and sorted: level 0, a unit is a position of
+ * ig_contact_map_order (n_units = T); level 1, a unit is a placed bin, numbered in genome order (the sub-fragments of a bin are
+ * neighbours in the order: the unit changes where the parent bin does).  A contact with both ends placed becomes the entry
+ * (lo, hi) = (min, max) of its ends' units; level 1 sums the counts of equal entries, entries with lo == hi (two sub-fragments of
+ * one bin) included.  The result is the CSR form of the upper triangle: rowptr[n_units + 1], and per entry the column hi (strictly
+ * ascending inside a row) and the count as a 64-bit sum -- the arrays of the rule byte for byte, whatever the launch shapes and
+ * the order in which atomics land, and the same from run to run.
+ * scalars: {0 entries_in (contacts of this handle's shard), 1 entries_kept, 2 contacts_kept (sum of their counts), 3 entries_unplaced
+ * (an end in a contig that is not placed), 4 contacts_unplaced, 5 n_placed = T, 6 n_units, 7 entries_out = *n_entries}.  By
+ * construction [2] + [4] = sum of all counts, the counts of the result sum to [2], and at level 0 [7] = [1].
+ * ig_assembly_contacts_build leaves the result ON THE DEVICE, a snapshot: moves made afterwards do not change it.  It is released by
+ * ig_assembly_contacts_release, by the next build (also one that fails: no stale result is ever visible), by ig_upload_contacts
+ * and by ig_destroy.  ig_assembly_contacts_rows copies rowptr (capacity: words of room, n_units + 1 needed),
+ * ig_assembly_contacts_fetch the entries first .. first + n - 1 (so that a host takes 5 10^8 entries in pieces); without a built
+ * result, out of range, or with a level other than 0 and 1 they return an error and write nothing.
+ * Device memory: 8 bytes per kept entry while the result lives (level 1: 12 per summed entry), 16 during a build that has long rows.
+ * Guards and effects as ig_contact_map: reads the CURRENT coordinates, changes nothing a move reads, synchronous, an error while a
+ * nuisance step or a chain is in flight.  A sharded handle (ig_set_shard) takes its shard's rows: the ranks' results, merged entry by
+ * entry, are the whole. */
+int ig_assembly_contacts_build(ig_ctx* ctx, int32_t level, int64_t* n_units, int64_t* n_entries, int64_t scalars[8]);
+int ig_assembly_contacts_rows(ig_ctx* ctx, int64_t* rowptr, int64_t capacity);
+int ig_assembly_contacts_fetch(ig_ctx* ctx, int64_t first, int64_t n, int32_t* col, int64_t* count);
+int ig_assembly_contacts_release(ig_ctx* ctx);
+
 /* ---- multi-GPU (contact shards) -------------------------- */
 /* Two-phase move: partial sums over this handle's contact shard are left in a device buffer of
  * ig_partials_count() int64 values; the caller all-reduces (SUM) it across ranks, then finishes. */
@@ -363,6 +389,24 @@ int ig_debug_distance_law_time(ig_ctx* ctx, const float* edges, int32_t n_edges,
  * its five scalars, each word weighted by its place: both forms must agree on it */
 int ig_debug_junction_profile_time(ig_ctx* ctx, int32_t window, int32_t combine, int32_t n, float* ms_observed_n, float* ms_model_n,
                                    float* ms_scan_n, int64_t* checksum);
+/* the contacts in genome coordinates: every row of the build is sorted by the form its length picks -- up to short_max entries a
+ * wave per row, up to lds_max a workgroup per row in LDS, beyond that runs of lds_max entries merged through a scratch buffer.  The
+ * limits of THIS handle: 0 = the compiled default (64, 1024), a value above a form's capacity (64, 1024) counts as the capacity;
+ * (1, 1) sends every row through the long form.  For the tests and the bench: the result does not depend on the limits. */
+int ig_debug_assembly_contacts_limits(ig_ctx* ctx, int32_t short_max, int32_t lds_max);
+/* the two passes over the contacts of THIS handle's builds: combine = 1 (the default): a run of a wave's lanes with the same row
+ * issues one atomic; 0: one atomic per contact, the yardstick the combined form is measured against.  The result is the same. */
+int ig_debug_assembly_contacts_combine(ig_ctx* ctx, int32_t combine);
+/* the last build's work lists: {rows, entries} of the short, the lds and the long form, the runs the long rows were cut into, the
+ * longest long row (rows of fewer than two entries are on no list) */
+int ig_debug_assembly_contacts_forms(ig_ctx* ctx, int64_t out8[8]);
+/* tests: the `activ` flag of one bin on the device (ig_upload_state refuses a state with an inactive bin, as the reference's moves
+ * cannot handle one).  Only the genome order reads the flag: a contig with an inactive bin is not placed -- left out of the contact
+ * map, the distance law, the junction profile and the contacts in genome coordinates, and counted there as unplaced */
+int ig_debug_set_bin_active(ig_ctx* ctx, int32_t bin, int32_t active);
+/* the build n times, hipEvents around each pass: ms_n[n][7] = {count, scan, scatter, sort short, sort lds, sort long, reduce (level 1)};
+ * the last result stays built; *checksum (may be NULL): its rows, columns and counts, each word weighted by its place */
+int ig_debug_assembly_contacts_time(ig_ctx* ctx, int32_t level, int32_t n, float* ms_n, int64_t* checksum);
 #ifdef __cplusplus
 }
 #endif

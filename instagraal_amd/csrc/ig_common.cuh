@@ -360,6 +360,38 @@ struct JuncBuf {
     int M = 0;
 };
 
+/* the contacts in the coordinates of the current genome (ig_kernels_lift.cuh): work buffers kept from call to call, the lists of a
+ * build (freed behind it), and the built result: a snapshot that stays on the device until it is released */
+struct LiftBuf {
+    int* key = nullptr;                  /* [M] unit of every sub-fragment, -1: not placed */
+    unsigned long long* head = nullptr;  /* [M + 1] level 1: 1 where the parent bin changes along the order */
+    unsigned long long* incl = nullptr;  /* [M + 1] ... and their running sum */
+    unsigned long long* count = nullptr; /* [M + 1] kept contacts per row; level 1, later: heads per row */
+    unsigned long long* cursor = nullptr; /* [M + 1] the scatter's cursors */
+    unsigned long long* tot = nullptr;   /* the scans' chunk totals over M + 2 words */
+    unsigned long long* sc = nullptr;    /* LIFT_SC_WORDS (ig_host_lift.inc) */
+    int M = 0;
+    /* one build's */
+    unsigned long long* rowstart = nullptr; /* [U + 1] first entry of every row behind the scatter */
+    int* short_rows = nullptr;
+    struct LiftItem *lds_items = nullptr, *run_items = nullptr;
+    struct LiftLong* long_rows = nullptr;
+    unsigned long long* scratch = nullptr; /* the long rows' entries once more */
+    unsigned* bits = nullptr;              /* level 1: a bit per entry, set where a row starts */
+    unsigned long long* rtot = nullptr;    /* level 1: heads per chunk of entries */
+    /* the snapshot */
+    unsigned long long* rowptr = nullptr; /* [n_units + 1] */
+    unsigned long long* ent = nullptr;    /* level 0: [n_entries] column << 32 | count */
+    int* out_col = nullptr;               /* level 1: [n_entries] */
+    unsigned long long* out_cnt = nullptr;
+    bool valid = false;
+    int level = 0;
+    long long n_placed = 0, n_units = 0, n_entries = 0;
+    long long forms[8] = {0, 0, 0, 0, 0, 0, 0, 0}; /* the last build's LIFT_C_* words */
+    int short_max = 0, lds_max = 0;       /* ig_debug_assembly_contacts_limits, 0: the default */
+    bool no_combine = false;              /* ig_debug_assembly_contacts_combine(0): one atomic per contact in the two passes */
+};
+
 struct ig_ctx {
     int device;
     hipStream_t stream;
@@ -465,6 +497,7 @@ struct ig_ctx {
     MapBuf map;
     LawBuf law;
     JuncBuf junc;
+    LiftBuf lift;
     int* batch_out; /* committed moves, pending slot, (unused), candidates, predicted deltas used, contigs */
     int *host_bo, *host_bo_dev; /* the same in mapped host memory (+ [7] = sequence number of the decide launch), and its device address */
     int bo_seq;

@@ -26,7 +26,9 @@
  * nuisance step's screened pass: k_hist_build / k_hist_walk / k_hist_eval (tier 0), k_full_diff_tiled (tier 1);
  * the contact map of the current genome: k_map_pixels, k_contact_map, k_map_mirror; its distance law:
  * k_law_records, k_law_sorted, k_law_observed, k_law_pairs; its junction support profile: k_junc_observed,
- * k_junc_count, k_junc_model, k_junc_scan_totals / _tops / _apply.
+ * k_junc_count, k_junc_model, k_junc_scan_totals / _tops / _apply; the contacts in its coordinates: k_lift_heads,
+ * k_lift_keys, k_lift_pass, k_lift_classify, k_lift_sort_wave / _lds, k_lift_merge, k_lift_row_bits, k_lift_head_totals, k_lift_reduce
+ * (DESIGN.md 4.13).
  *
  * Environment knobs (tests, fault injection and tuning only; the table in INTEGRATION.md section 4 is the reference): IG_BATCH_W, IG_WINDOW
  * (widths), IG_POOL_ENTRIES, IG_WIDE_LISTS, IG_NO_HOST_FLAG, IG_POISON_ALLOC / IG_POISON_ONLY (force the rare paths), IG_SCREEN,
@@ -49,13 +51,15 @@
 #include "ig_kernels_map.cuh"
 #include "ig_kernels_law.cuh"
 #include "ig_kernels_junc.cuh"
+#include "ig_kernels_lift.cuh"
 
-/* ================================================================== host side (one translation unit, eight parts) */
+/* ================================================================== host side (one translation unit, nine parts) */
 #include "ig_host_core.inc"
 #include "ig_host_upload.inc"
 #include "ig_host_map.inc"
 #include "ig_host_law.inc"
 #include "ig_host_junc.inc"
+#include "ig_host_lift.inc"
 #include "ig_host_batch.inc"
 #include "ig_host_nuis.inc"
 #include "ig_host_debug.inc"

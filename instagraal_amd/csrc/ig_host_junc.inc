@@ -80,15 +80,23 @@ static int junc_enqueue_model(ig_ctx* c, int T, int window)
     return 0;
 }
 
+/* The 64-bit inclusive prefix sums of n_arrays arrays of n words each, `stride` words apart: in -> out (in stays as it is), in three
+ * steps on the library's stream; tot: n_arrays * junc_chunks(n) words of scratch.  Shared with the contacts in genome coordinates
+ * (ig_host_lift.inc). */
+static void scan64_enqueue(ig_ctx* c, const unsigned long long* in, unsigned long long* out, long long stride, int n, int n_arrays,
+                           unsigned long long* tot)
+{
+    const int chunks = junc_chunks(n);
+    hipLaunchKernelGGL(k_junc_scan_totals, dim3(chunks, n_arrays), dim3(JUNC_THREADS), 0, c->stream, in, stride, n, tot);
+    hipLaunchKernelGGL(k_junc_scan_tops, dim3(n_arrays), dim3(JUNC_THREADS), 0, c->stream, tot, chunks);
+    hipLaunchKernelGGL(k_junc_scan_apply, dim3(chunks, n_arrays), dim3(JUNC_THREADS), 0, c->stream, in, out, stride, n, tot);
+}
+
 /* the prefix sums of the first n_arrays difference arrays: diff -> prof (diff stays as it is: the scan can be repeated) */
 static int junc_enqueue_scan(ig_ctx* c, int T, int n_arrays)
 {
     JuncBuf& j = c->junc;
-    const long long stride = (long long)j.M + 1;
-    const int n = T + 1, chunks = junc_chunks(n);
-    hipLaunchKernelGGL(k_junc_scan_totals, dim3(chunks, n_arrays), dim3(JUNC_THREADS), 0, c->stream, j.diff, stride, n, j.tot);
-    hipLaunchKernelGGL(k_junc_scan_tops, dim3(n_arrays), dim3(JUNC_THREADS), 0, c->stream, j.tot, chunks);
-    hipLaunchKernelGGL(k_junc_scan_apply, dim3(chunks, n_arrays), dim3(JUNC_THREADS), 0, c->stream, j.diff, j.prof, stride, n, j.tot);
+    scan64_enqueue(c, j.diff, j.prof, (long long)j.M + 1, T + 1, n_arrays, j.tot);
     return 0;
 }
 

@@ -18,12 +18,13 @@ SRC = os.path.join(HERE, "csrc", "ig_hip.hip")
 SRC_HOST = os.path.join(HERE, "csrc", "ig_draw.cpp")  # host-only part: the candidate draw
 DEPS = [SRC, SRC_HOST] + [os.path.join(HERE, "csrc", f) for f in ("ig_ops.cuh", "ig_common.cuh", "ig_model.cuh", "ig_kernels_setup.cuh",
                                                           "ig_kernels_score.cuh", "ig_kernels_screen.cuh", "ig_kernels_commit.cuh",
-                                                          "ig_kernels_nuis.cuh", "ig_kernels_map.cuh", "ig_kernels_law.cuh", "ig_kernels_junc.cuh", "ig_host_core.inc", "ig_host_upload.inc",
-                                                          "ig_host_map.inc", "ig_host_law.inc", "ig_host_junc.inc",
+                                                          "ig_kernels_nuis.cuh", "ig_kernels_map.cuh", "ig_kernels_law.cuh", "ig_kernels_junc.cuh", "ig_kernels_lift.cuh", "ig_host_core.inc", "ig_host_upload.inc",
+                                                          "ig_host_map.inc", "ig_host_law.inc", "ig_host_junc.inc", "ig_host_lift.inc",
                                                           "ig_host_batch.inc", "ig_host_nuis.inc", "ig_host_debug.inc")] + \
        [os.path.join(ROOT, "include", f) for f in ("ig_detmath.h", "ig_detmath_tables.h", "instagraal_hip.h")]
 
 N_TMP_STRUCT = 24
+ASSEMBLY_CONTACTS_PASSES = ("count", "scan", "scatter", "sort_short", "sort_lds", "sort_long", "reduce")  # ig_debug_assembly_contacts_time
 MAX_CANDIDATES = 16
 
 FRAG_FIELDS = ("pos", "sub_pos", "id_c", "start_bp", "len_bp", "sub_len", "circ", "id", "prev", "next", "l_cont",
@@ -712,6 +713,61 @@ class Context:
         _ck(lib().ig_debug_junction_profile_time(self._h, C.c_int32(int(window)), C.c_int32(int(bool(combine))), C.c_int32(int(n)), _p(ms_o),
                                                  _p(ms_m), _p(ms_s), C.byref(ck)))
         return ms_o, ms_m, ms_s, int(ck.value)
+
+    # ---- the contacts in the coordinates of the current genome (the rule: assembly_contacts.py)
+    def assembly_contacts(self, level="sub"):
+        """builds the contacts re-indexed to the units of the genome order (``"sub"``: positions, ``"bin"``: placed bins) and
+        sorted, as a snapshot on the device -> dict: level, rowptr (int64 [n_units + 1]), n_entries and the int64 scalars of
+        ``assembly_contacts.SCALARS``; the entries come through ``assembly_contacts_fetch``"""
+        from .assembly_contacts import LEVELS, SCALARS
+
+        lv = LEVELS.index(level) if level in LEVELS else int(level)
+        nu, ne = C.c_int64(), C.c_int64()
+        sc = np.zeros(8, np.int64)
+        _ck(lib().ig_assembly_contacts_build(self._h, C.c_int32(lv), C.byref(nu), C.byref(ne), _p(sc)))
+        rowptr = np.zeros(nu.value + 1, np.int64)
+        _ck(lib().ig_assembly_contacts_rows(self._h, _p(rowptr), C.c_int64(rowptr.size)))
+        out = dict(level=LEVELS[lv], rowptr=rowptr, n_entries=int(ne.value))
+        out.update((k, int(v)) for k, v in zip(SCALARS, sc))
+        return out
+
+    def assembly_contacts_fetch(self, first, n):
+        """entries first .. first + n - 1 of the built result -> (col int32 [n], count int64 [n])"""
+        n = int(n)
+        col, cnt = np.zeros(max(n, 0), np.int32), np.zeros(max(n, 0), np.int64)
+        _ck(lib().ig_assembly_contacts_fetch(self._h, C.c_int64(int(first)), C.c_int64(n), _p(col), _p(cnt)))
+        return col, cnt
+
+    def assembly_contacts_release(self):
+        _ck(lib().ig_assembly_contacts_release(self._h))
+
+    def debug_assembly_contacts_limits(self, short_max=0, lds_max=0):
+        """the row lengths up to which the build sorts a row with a wave / with a workgroup in LDS (0: the default)"""
+        _ck(lib().ig_debug_assembly_contacts_limits(self._h, C.c_int32(int(short_max)), C.c_int32(int(lds_max))))
+
+    def debug_assembly_contacts_combine(self, combine=True):
+        """the two passes over the contacts: one atomic per run of a wave's lanes with the same row (True, the default) or one per
+        contact (False, the yardstick)"""
+        _ck(lib().ig_debug_assembly_contacts_combine(self._h, C.c_int32(int(bool(combine)))))
+
+    def debug_assembly_contacts_forms(self):
+        """the last build's work lists -> dict of (rows, entries) per sort form, the runs of the long rows, the longest long row"""
+        o = np.zeros(8, np.int64)
+        _ck(lib().ig_debug_assembly_contacts_forms(self._h, _p(o)))
+        return dict(short=(int(o[0]), int(o[1])), lds=(int(o[2]), int(o[3])), long=(int(o[4]), int(o[5])), runs=int(o[6]), longest=int(o[7]))
+
+    def debug_set_bin_active(self, bin_id, active):
+        """tests: the ``activ`` flag of one bin on the device (a contig with an inactive bin is not placed in the genome order)"""
+        _ck(lib().ig_debug_set_bin_active(self._h, C.c_int32(int(bin_id)), C.c_int32(int(bool(active)))))
+
+    def debug_assembly_contacts_time(self, level="sub", n=1):
+        """the build n times with hipEvents around each pass -> (ms [n, 7]: ``ASSEMBLY_CONTACTS_PASSES``, checksum of the last result)"""
+        from .assembly_contacts import LEVELS
+
+        ms = np.zeros((int(n), len(ASSEMBLY_CONTACTS_PASSES)), np.float32)
+        ck = C.c_int64()
+        _ck(lib().ig_debug_assembly_contacts_time(self._h, C.c_int32(LEVELS.index(level)), C.c_int32(int(n)), _p(ms), C.byref(ck)))
+        return ms, int(ck.value)
 
     # ---- bookkeeping
     def renumber_contigs(self):

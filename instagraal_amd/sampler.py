@@ -937,5 +937,62 @@ class sampler:  # noqa: N801 - the reference's class name
         fig.savefig(filename, dpi=150, bbox_inches="tight")
         return prof
 
+    # ------------------------------------------------------ assembly contacts
+    def _assembly_contacts_frame(self, level, diagonal):
+        """what the two methods below share: the device build, the order, the bins table, the diagonal per unit (or None)"""
+        from . import assembly_contacts as ac
+
+        ac.check_level(level)
+        res = self.ctx.assembly_contacts(level)
+        order = self.ctx.contact_map_order().astype(np.int64)
+        parent = self.np_sub_frags_2_frags["x"].astype(np.int64)
+        g = self.gpu_vect_frags.copy_from_gpu()
+        table = ac.bins_table(order, parent, g.id_c, g.ori, self.S_o_A_sub_frags["len_bp"], level)
+        diag, total = None, 0
+        if diagonal and self.sparse_matrix is not None:
+            d = np.asarray(self.sparse_matrix.diagonal()).astype(np.int64)
+            unit = np.arange(order.size, dtype=np.int64) if level == "sub" else ac.units_along(parent[order])
+            diag = np.zeros(res["n_units"], np.int64)
+            np.add.at(diag, unit, d[order])
+            total = int(diag.sum())
+        return res, order, table, diag, total
+
+    def assembly_contacts(self, level="sub", diagonal=True):
+        """The contacts in the coordinates of the current genome (``ig_assembly_contacts_build``; the rule: ``assembly_contacts.py``):
+        every contact re-indexed to the units of the genome order -- ``level="sub"``: the positions of the contact map, ``"bin"``:
+        the placed bins -- and sorted, as CSR arrays.  -> dict: ``rowptr`` (int64 [n_units + 1]), ``col`` (int32), ``count`` (int64),
+        the scalars of ``assembly_contacts.SCALARS`` (they describe the device's result), ``order`` (the sub-fragment at every
+        position), ``bins`` (``assembly_contacts.bins_table``: scaffold, start, end, parent bin, orientation per unit) and
+        ``chrom_sizes`` ((contig ids, sizes)).  The device holds the strict upper triangle only: with ``diagonal=True`` and a
+        sampler that has ``sparse_matrix`` (not one built from ``coo=``) the diagonal of the symmetrised input is merged in here as
+        entries (u, u), first in their rows, as ``contact_map`` adds it to its image; their total is ``contacts_diagonal``.
+        No reference counterpart on the device (post.py lifts the raw pairs over)."""
+        from . import assembly_contacts as ac
+
+        res, order, table, diag, total = self._assembly_contacts_frame(level, diagonal)
+        col, count = self.ctx.assembly_contacts_fetch(0, res["n_entries"])
+        self.ctx.assembly_contacts_release()
+        rowptr = res.pop("rowptr")
+        if diag is not None:
+            rowptr, col, count = ac.merge_diagonal(0, rowptr, col, count, diag)
+        res.pop("n_entries")
+        res.update(rowptr=rowptr, col=col, count=count, order=order, bins=table, chrom_sizes=ac.chrom_sizes(table), contacts_diagonal=total)
+        return res
+
+    def write_assembly_contacts(self, folder, level="sub", diagonal=True, block_rows=None):
+        """Writes ``bins.bed``, ``pixels.tsv`` and ``chrom.sizes`` into ``folder``: what ``cooler load -f coo bins.bed pixels.tsv``
+        takes.  The entries are fetched from the device and written by blocks of ``block_rows`` rows.  -> the scalars (plus
+        ``contacts_diagonal`` and ``pixels_written``)."""
+        from . import assembly_contacts as ac
+
+        res, _, table, diag, total = self._assembly_contacts_frame(level, diagonal)
+        try:
+            n = ac.write_all(folder, table, res["rowptr"], self.ctx.assembly_contacts_fetch, ac.DEFAULT_BLOCK_ROWS if block_rows is None else block_rows, diag)
+        finally:
+            self.ctx.assembly_contacts_release()
+        out = {k: res[k] for k in ac.SCALARS}
+        out.update(level=level, contacts_diagonal=total, pixels_written=n)
+        return out
+
     def free_gpu(self):  # CL:3167-3177
         self.ctx.close()
