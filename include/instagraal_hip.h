@@ -311,6 +311,40 @@ int ig_assembly_contacts_rows(ig_ctx* ctx, int64_t* rowptr, int64_t capacity);
 int ig_assembly_contacts_fetch(ig_ctx* ctx, int64_t first, int64_t n, int32_t* col, int64_t* count);
 int ig_assembly_contacts_release(ig_ctx* ctx);
 
+/* ---- join support: which scaffold ends the contacts would link (no reference counterpart; the rule:
+ * instagraal_amd/join_support.py) -----------------------------------------------------------------------------------------------
+ * The junction profile for junctions that do not exist yet.  The placed contigs that are not rings are the runs k = 0 .. K - 1 of
+ * ig_contact_map_order; contig k has the ENDS 2 k (its head: its first position) and 2 k + 1 (its tail).  A contact between two
+ * different such contigs counts, for each of the four pairs of their ends, for the LINK (lo, hi) = (min, max) of the two end ids
+ * if the separation in positions the two sub-fragments would have with those ends joined -- depth + depth + 1 -- is at most
+ * `window` (1 .. 1024).  The result lists the links with at least one contact as CSR over the 2 K ends: rowptr[2 K + 1], and per link
+ * the column hi (strictly ascending inside a row), observed (the sum of the counts), pairs (the position pairs within the window)
+ * and expected_q (the sum over those pairs of the model's value under parameter set 0 at the separation the coordinates would give
+ * with no gap between the scaffolds, quantised to 2^-32 and added as 64-bit integers) -- the arrays of the rule byte for byte,
+ * whatever the launch shapes and the order in which atomics land.  model = 0 skips the model pass: no pairs, no expected_q.
+ * scalars: {0 in_reach_observed (trans contacts between linear placed contigs that count for a link, each once), 1
+ * out_of_reach_observed, 2 cis_observed, 3 ring_observed (an end in a ring), 4 unplaced_observed (an end in a contig that is not
+ * placed; checked first, then the ring, then cis), 5 contributions (sum of count x links counted for), 6 n_contigs = K, 7 n_links}.
+ * [0] + .. + [4] = the sum of all counts; the observed of the result sum to [5].  *n_ends = 2 K.
+ * ig_join_support_build leaves the result ON THE DEVICE, a snapshot: moves made afterwards do not change it.  It is released by
+ * ig_join_support_release, by the next build (first thing, also one that fails), by ig_upload_contacts and by ig_destroy.
+ * ig_join_support_ends copies the first position and the positions of every contig k (capacity: entries of room, K needed),
+ * ig_join_support_rows copies rowptr (capacity: words of room, 2 K + 1 needed), ig_join_support_fetch the links first ..
+ * first + n - 1 (pairs and expected_q may both be NULL; they must be for a result built with model = 0); without a built result or
+ * out of range they return an error and write nothing.
+ * Device memory: 28 bytes per link while the result lives; during a build 8 bytes per (contact, link) entry -- behind a bomb up to
+ * four per contact -- and as much again for long rows.  A build whose entries do not fit the free device memory fails before it
+ * allocates them and names the bytes it needs; so does one whose model values could overflow the 64-bit sum ("model value too
+ * large for this window").
+ * Guards and effects as ig_contact_map: reads the CURRENT coordinates, changes nothing a move reads, synchronous, an error while a
+ * nuisance step or a chain is in flight.  A sharded handle (ig_set_shard) takes its shard's rows: the ranks' results, merged link
+ * by link (observed summed, pairs and expected_q the same on every rank that has the link), are the whole. */
+int ig_join_support_build(ig_ctx* ctx, int32_t window, int32_t model, int64_t* n_ends, int64_t* n_links, int64_t scalars[8]);
+int ig_join_support_ends(ig_ctx* ctx, int32_t* first_position, int32_t* n_positions, int64_t capacity); /* per contig k */
+int ig_join_support_rows(ig_ctx* ctx, int64_t* rowptr, int64_t capacity);
+int ig_join_support_fetch(ig_ctx* ctx, int64_t first, int64_t n, int32_t* col, int64_t* observed, int64_t* pairs, int64_t* expected_q);
+int ig_join_support_release(ig_ctx* ctx);
+
 /* ---- multi-GPU (contact shards) -------------------------- */
 /* Two-phase move: partial sums over this handle's contact shard are left in a device buffer of
  * ig_partials_count() int64 values; the caller all-reduces (SUM) it across ranks, then finishes. */
@@ -407,6 +441,16 @@ int ig_debug_set_bin_active(ig_ctx* ctx, int32_t bin, int32_t active);
 /* the build n times, hipEvents around each pass: ms_n[n][7] = {count, scan, scatter, sort short, sort lds, sort long, reduce (level 1)};
  * the last result stays built; *checksum (may be NULL): its rows, columns and counts, each word weighted by its place */
 int ig_debug_assembly_contacts_time(ig_ctx* ctx, int32_t level, int32_t n, float* ms_n, int64_t* checksum);
+/* join support: the form of the two passes over the contacts of THIS handle's builds: 1 a run of a wave's lanes with the same row
+ * issues one atomic per emission, 0 one atomic per emission (the yardstick), negative: the form the library ships.  The result is
+ * the same.  The limits of ig_debug_assembly_contacts_limits hold for this feature's sorts too. */
+int ig_debug_join_support_combine(ig_ctx* ctx, int32_t combine);
+/* the last join support build's work lists, as ig_debug_assembly_contacts_forms */
+int ig_debug_join_support_forms(ig_ctx* ctx, int64_t out8[8]);
+/* the build n times (with the model pass if parameters are set), hipEvents around each pass: ms_n[n][9] = {ends, count, scan,
+ * scatter, sort short, sort lds, sort long, reduce, model}; the last result stays built; *checksum (may be NULL): its rows, columns
+ * and observed, each word weighted by its place */
+int ig_debug_join_support_time(ig_ctx* ctx, int32_t window, int32_t n, float* ms_n, int64_t* checksum);
 #ifdef __cplusplus
 }
 #endif

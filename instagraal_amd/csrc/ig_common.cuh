@@ -360,6 +360,17 @@ struct JuncBuf {
     int M = 0;
 };
 
+/* the lists and the scratch of one sort of the rows and one reduction of their equal columns (lift_sort_rows, lift_reduce_rows in
+ * ig_host_lift.inc), freed behind the build (lift_work_free): the contacts in genome coordinates and the join support have one each */
+struct LiftWork {
+    int* short_rows = nullptr;
+    struct LiftItem *lds_items = nullptr, *run_items = nullptr;
+    struct LiftLong* long_rows = nullptr;
+    unsigned long long* scratch = nullptr; /* the long rows' entries once more */
+    unsigned* bits = nullptr;              /* the reduction: a bit per entry, set where a row starts */
+    unsigned long long* rtot = nullptr;    /* the reduction: heads per chunk of entries */
+};
+
 /* the contacts in the coordinates of the current genome (ig_kernels_lift.cuh): work buffers kept from call to call, the lists of a
  * build (freed behind it), and the built result: a snapshot that stays on the device until it is released */
 struct LiftBuf {
@@ -373,12 +384,7 @@ struct LiftBuf {
     int M = 0;
     /* one build's */
     unsigned long long* rowstart = nullptr; /* [U + 1] first entry of every row behind the scatter */
-    int* short_rows = nullptr;
-    struct LiftItem *lds_items = nullptr, *run_items = nullptr;
-    struct LiftLong* long_rows = nullptr;
-    unsigned long long* scratch = nullptr; /* the long rows' entries once more */
-    unsigned* bits = nullptr;              /* level 1: a bit per entry, set where a row starts */
-    unsigned long long* rtot = nullptr;    /* level 1: heads per chunk of entries */
+    LiftWork work;
     /* the snapshot */
     unsigned long long* rowptr = nullptr; /* [n_units + 1] */
     unsigned long long* ent = nullptr;    /* level 0: [n_entries] column << 32 | count */
@@ -390,6 +396,34 @@ struct LiftBuf {
     long long forms[8] = {0, 0, 0, 0, 0, 0, 0, 0}; /* the last build's LIFT_C_* words */
     int short_max = 0, lds_max = 0;       /* ig_debug_assembly_contacts_limits, 0: the default */
     bool no_combine = false;              /* ig_debug_assembly_contacts_combine(0): one atomic per contact in the two passes */
+};
+
+/* join support (ig_kernels_join.cuh): every buffer of the feature, freed by free_join_buffers (ig_host_join.inc) -- what a build
+ * needs (gone behind it) and the built result: a snapshot that stays on the device until it is released */
+struct JoinBuf {
+    /* one build's */
+    unsigned long long* head = nullptr;   /* [T + 1] 1 at the first position of a linear placed contig */
+    unsigned long long* incl = nullptr;   /* [T + 1] ... and their running sum */
+    int4* rec = nullptr;                  /* [M] (depth from the head, depth from the tail, run index, 0) per sub-fragment */
+    unsigned long long* count = nullptr;  /* [2 K + 2] emissions per row; later: links per row */
+    unsigned long long* cursor = nullptr; /* [2 K + 2] the scatter's cursors */
+    unsigned long long* tot = nullptr;    /* the scans' chunk totals */
+    unsigned long long* sc = nullptr;     /* JOIN_SC_WORDS (ig_host_join.inc) */
+    unsigned long long* rowstart = nullptr; /* [2 K + 1] first entry of every row behind the scatter */
+    unsigned long long* ent = nullptr;    /* [entries] upper end << 32 | count */
+    LiftWork work;
+    /* the snapshot */
+    struct JoinEnd* ends = nullptr;       /* [K] first position, positions, length in kb per contig */
+    unsigned long long* rowptr = nullptr; /* [2 K + 1] */
+    int* out_col = nullptr;               /* [n_links] */
+    unsigned long long* out_cnt = nullptr; /* [n_links] observed */
+    unsigned long long* pairs = nullptr;  /* [n_links] (a build with the model) */
+    unsigned long long* expq = nullptr;   /* [n_links] */
+    bool valid = false, model = false;
+    int window = 0;
+    long long n_placed = 0, n_contigs = 0, n_links = 0, n_entries = 0;
+    long long forms[8] = {0, 0, 0, 0, 0, 0, 0, 0}; /* the last build's LIFT_C_* words */
+    int combine = -1; /* ig_debug_join_support_combine: 1 / 0, -1: the form the library ships (JOIN_SHIP_COMBINE) */
 };
 
 struct ig_ctx {
@@ -498,6 +532,7 @@ struct ig_ctx {
     LawBuf law;
     JuncBuf junc;
     LiftBuf lift;
+    JoinBuf join;
     int* batch_out; /* committed moves, pending slot, (unused), candidates, predicted deltas used, contigs */
     int *host_bo, *host_bo_dev; /* the same in mapped host memory (+ [7] = sequence number of the decide launch), and its device address */
     int bo_seq;

@@ -28,7 +28,8 @@
  * k_law_records, k_law_sorted, k_law_observed, k_law_pairs; its junction support profile: k_junc_observed,
  * k_junc_count, k_junc_model, k_junc_scan_totals / _tops / _apply; the contacts in its coordinates: k_lift_heads,
  * k_lift_keys, k_lift_pass, k_lift_classify, k_lift_sort_wave / _lds, k_lift_merge, k_lift_row_bits, k_lift_head_totals, k_lift_reduce
- * (DESIGN.md 4.13).
+ * (DESIGN.md 4.13); the join support of its scaffold ends: k_join_heads, k_join_ends, k_join_records, k_join_emit, k_join_model, with
+ * the sorts and the reduction of 4.13.
  *
  * Environment knobs (tests, fault injection and tuning only; the table in INTEGRATION.md section 4 is the reference): IG_BATCH_W, IG_WINDOW
  * (widths), IG_POOL_ENTRIES, IG_WIDE_LISTS, IG_NO_HOST_FLAG, IG_POISON_ALLOC / IG_POISON_ONLY (force the rare paths), IG_SCREEN,
@@ -52,14 +53,16 @@
 #include "ig_kernels_law.cuh"
 #include "ig_kernels_junc.cuh"
 #include "ig_kernels_lift.cuh"
+#include "ig_kernels_join.cuh"
 
-/* ================================================================== host side (one translation unit, nine parts) */
+/* ================================================================== host side (one translation unit, ten parts) */
 #include "ig_host_core.inc"
 #include "ig_host_upload.inc"
 #include "ig_host_map.inc"
 #include "ig_host_law.inc"
 #include "ig_host_junc.inc"
 #include "ig_host_lift.inc"
+#include "ig_host_join.inc"
 #include "ig_host_batch.inc"
 #include "ig_host_nuis.inc"
 #include "ig_host_debug.inc"

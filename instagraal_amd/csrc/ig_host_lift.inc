@@ -16,25 +16,25 @@
 #define LIFT_P_REDUCE 6
 #define LIFT_PASSES 7
 
+static void lift_work_free(LiftWork& w)
+{
+    hipFree(w.short_rows);
+    hipFree(w.lds_items);
+    hipFree(w.run_items);
+    hipFree(w.long_rows);
+    hipFree(w.scratch);
+    hipFree(w.bits);
+    hipFree(w.rtot);
+    w = LiftWork{};
+}
+
 /* what one build needed and its result does not */
 static void lift_free_temp(ig_ctx* c)
 {
     LiftBuf& l = c->lift;
     hipFree(l.rowstart);
-    hipFree(l.short_rows);
-    hipFree(l.lds_items);
-    hipFree(l.run_items);
-    hipFree(l.long_rows);
-    hipFree(l.scratch);
-    hipFree(l.bits);
-    hipFree(l.rtot);
     l.rowstart = nullptr;
-    l.short_rows = nullptr;
-    l.lds_items = l.run_items = nullptr;
-    l.long_rows = nullptr;
-    l.scratch = nullptr;
-    l.bits = nullptr;
-    l.rtot = nullptr;
+    lift_work_free(l.work);
 }
 
 static void lift_release_snapshot(ig_ctx* c)
@@ -71,15 +71,15 @@ static void free_lift_buffers(ig_ctx* c)
     l.no_combine = no_combine;
 }
 
-/* hipEvents around a pass where its time was asked for (ms: LIFT_PASSES floats, or null) */
+/* hipEvents around a pass where its time was asked for (ms: n_passes floats, or null) */
 struct LiftTimer {
     ig_ctx* c;
     float* ms;
     hipEvent_t a = nullptr, b = nullptr;
-    LiftTimer(ig_ctx* ctx, float* out) : c(ctx), ms(out)
+    LiftTimer(ig_ctx* ctx, float* out, int n_passes = LIFT_PASSES) : c(ctx), ms(out)
     {
         if (!ms) return;
-        for (int p = 0; p < LIFT_PASSES; p++) ms[p] = 0.0f;
+        for (int p = 0; p < n_passes; p++) ms[p] = 0.0f;
         if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess) ms = nullptr;
     }
     ~LiftTimer()
@@ -101,6 +101,91 @@ struct LiftTimer {
 };
 
 static inline int lift_blocks(long long n) { return (int)std::min<long long>((n + LIFT_THREADS - 1) / LIFT_THREADS, 4096); }
+
+/* The sort of every row by column in one of three forms, shared with the join support (ig_host_join.inc): k_lift_classify builds
+ * the work lists in `w`, then one launch per form.  rowstart: [U + 1]; ent: [K] entries; short_max, lds_max: the handle's limits (0:
+ * the default); cls, cur: LIFT_C_WORDS and 5 zeroed words on the device; forms: the LIFT_C_* words for the host.  The times go to
+ * the passes pass0 (short), pass0 + 1 (lds), pass0 + 2 (long). */
+static int lift_sort_rows(ig_ctx* c, const char* who, LiftTimer& timer, int pass0, const unsigned long long* rowstart, int Ui, unsigned long long* ent,
+                          long long K, int short_set, int lds_set, unsigned long long* d_cls, unsigned long long* d_cur, long long forms[8], LiftWork& w)
+{
+    const long long U = Ui;
+    const int short_max = std::min(short_set > 0 ? short_set : LIFT_SHORT_CAP, LIFT_SHORT_CAP);
+    const int lds_max = std::min(lds_set > 0 ? lds_set : LIFT_LDS_CAP, LIFT_LDS_CAP);
+    const dim3 rows_grid((unsigned)((U + LIFT_THREADS - 1) / LIFT_THREADS));
+    hipLaunchKernelGGL((k_lift_classify<false>), rows_grid, dim3(LIFT_THREADS), 0, c->stream, rowstart, Ui, short_max, lds_max, d_cls, d_cur, nullptr, nullptr, nullptr,
+                       nullptr);
+    unsigned long long cls[LIFT_C_WORDS];
+    HIPCK(hipMemcpyAsync(cls, d_cls, sizeof(cls), hipMemcpyDeviceToHost, c->stream));
+    HIPCK(hipStreamSynchronize(c->stream));
+    for (int k = 0; k < LIFT_C_WORDS; k++) forms[k] = (long long)cls[k];
+    const long long n_short = forms[LIFT_C_SHORT_ROWS], n_lds = forms[LIFT_C_LDS_ROWS], n_long = forms[LIFT_C_LONG_ROWS];
+    const long long n_runs = forms[LIFT_C_RUNS], long_ent = forms[LIFT_C_LONG_ENT], max_long = forms[LIFT_C_MAX_LONG];
+    if (n_short < 0 || n_lds < 0 || n_long < 0 || n_runs < 0 || long_ent < 0 || max_long < 0 || n_short + n_lds + n_long > U || long_ent > K || n_runs > K || max_long > K)
+        return fail("%s: the work lists do not add up (device error)", who);
+    DALLOC(w.short_rows, (size_t)n_short);
+    DALLOC(w.lds_items, (size_t)n_lds);
+    DALLOC(w.run_items, (size_t)n_runs);
+    DALLOC(w.long_rows, (size_t)n_long);
+    DALLOC(w.scratch, (size_t)long_ent);
+    hipLaunchKernelGGL((k_lift_classify<true>), rows_grid, dim3(LIFT_THREADS), 0, c->stream, rowstart, Ui, short_max, lds_max, d_cls, d_cur, w.short_rows, w.lds_items,
+                       w.run_items, w.long_rows);
+    /* one launch per form */
+    timer.begin();
+    if (n_short > 0)
+        hipLaunchKernelGGL(k_lift_sort_wave, dim3((unsigned)((n_short + LIFT_THREADS / 64 - 1) / (LIFT_THREADS / 64))), dim3(LIFT_THREADS), 0, c->stream, w.short_rows,
+                           (int)n_short, rowstart, ent);
+    timer.end(pass0);
+    timer.begin();
+    if (n_lds > 0) hipLaunchKernelGGL(k_lift_sort_lds, dim3((unsigned)n_lds), dim3(LIFT_THREADS), 0, c->stream, w.lds_items, ent);
+    timer.end(pass0 + 1);
+    timer.begin();
+    if (n_long > 0) {
+        if (n_runs > 0) hipLaunchKernelGGL(k_lift_sort_lds, dim3((unsigned)n_runs), dim3(LIFT_THREADS), 0, c->stream, w.run_items, ent);
+        const dim3 grid((unsigned)n_long, (unsigned)std::min<long long>(std::max<long long>((max_long + 4 * LIFT_THREADS - 1) / (4 * LIFT_THREADS), 1), 1024));
+        int to_scratch = 1;
+        for (long long width = lds_max; width < max_long; width *= 2, to_scratch ^= 1)
+            hipLaunchKernelGGL(k_lift_merge, grid, dim3(LIFT_THREADS), 0, c->stream, w.long_rows, ent, w.scratch, width, to_scratch);
+        if (!to_scratch) /* the merged rows are in the scratch buffer: a step with nothing left to merge copies them back */
+            hipLaunchKernelGGL(k_lift_merge, grid, dim3(LIFT_THREADS), 0, c->stream, w.long_rows, ent, w.scratch, max_long, 0);
+    }
+    timer.end(pass0 + 2);
+    return 0;
+}
+
+/* The runs of equal columns inside a row become one entry each, shared with the join support: heads per chunk, their scan, the
+ * sums; the heads per row, their scan.  d_heads: a zeroed word on the device; count: [U + 1] words, tot: the scan's totals (both
+ * scratch).  Allocates the result (*out_col, *out_cnt: [*n_out]; *rowptr: [U + 1]); everything is enqueued, the caller waits. */
+static int lift_reduce_rows(ig_ctx* c, const char* who, LiftTimer& timer, int pass, const unsigned long long* rowstart, int Ui, const unsigned long long* ent,
+                            long long K, unsigned long long* d_heads, unsigned long long* count, unsigned long long* tot, LiftWork& w, int** out_col,
+                            unsigned long long** out_cnt, unsigned long long** rowptr, long long* n_out)
+{
+    const long long U = Ui;
+    const long long chunks = (K + JUNC_CHUNK - 1) / JUNC_CHUNK;
+    DALLOC(w.bits, (size_t)(K + 31) / 32);
+    DALLOC(w.rtot, (size_t)chunks);
+    timer.begin();
+    HIPCK(hipMemsetAsync(w.bits, 0, ((size_t)(K + 31) / 32) * sizeof(unsigned), c->stream));
+    hipLaunchKernelGGL(k_lift_row_bits, dim3((unsigned)((U + LIFT_THREADS - 1) / LIFT_THREADS)), dim3(LIFT_THREADS), 0, c->stream, rowstart, Ui, w.bits);
+    hipLaunchKernelGGL(k_lift_head_totals, dim3((unsigned)chunks), dim3(JUNC_THREADS), 0, c->stream, ent, w.bits, K, w.rtot, d_heads);
+    hipLaunchKernelGGL(k_junc_scan_tops, dim3(1), dim3(JUNC_THREADS), 0, c->stream, w.rtot, (int)chunks);
+    unsigned long long heads = 0;
+    HIPCK(hipMemcpyAsync(&heads, d_heads, sizeof(heads), hipMemcpyDeviceToHost, c->stream));
+    HIPCK(hipStreamSynchronize(c->stream));
+    if (heads < 1 || heads > (unsigned long long)K) return fail("%s: %llu distinct entries of %lld (device error)", who, heads, K);
+    *n_out = (long long)heads;
+    DALLOC(*out_col, (size_t)*n_out);
+    DALLOC(*out_cnt, (size_t)*n_out);
+    DALLOC(*rowptr, (size_t)U + 1);
+    HIPCK(hipMemsetAsync(*out_cnt, 0, (size_t)*n_out * sizeof(unsigned long long), c->stream));
+    HIPCK(hipMemsetAsync(count, 0, ((size_t)U + 1) * sizeof(unsigned long long), c->stream));
+    hipLaunchKernelGGL(k_lift_reduce, dim3((unsigned)chunks), dim3(JUNC_THREADS), 0, c->stream, ent, w.bits, K, w.rtot, rowstart, Ui, (unsigned long long)*n_out,
+                       *out_col, *out_cnt, count);
+    HIPCK(hipMemsetAsync(*rowptr, 0, sizeof(unsigned long long), c->stream));
+    scan64_enqueue(c, count, *rowptr + 1, 0, Ui, 1, tot);
+    timer.end(pass);
+    return 0;
+}
 
 /* The build, up to the snapshot's fields.  The caller frees what it leaves behind (lift_free_temp) and, on an error, the half-built
  * snapshot. */
@@ -175,73 +260,15 @@ static int lift_build_impl(ig_ctx* c, const char* who, int level, float* ms)
             hipLaunchKernelGGL((k_lift_pass<true, true>), dim3(lift_blocks(c->Z)), dim3(LIFT_THREADS), 0, c->stream, c->crow, c->cc, c->Z, l.key, Ui, l.cursor, l.ent,
                                (unsigned long long)K, l.sc, c->rank, c->world);
         timer.end(LIFT_P_SCATTER);
-        /* the work lists of the three forms */
-        const int short_max = std::min(l.short_max > 0 ? l.short_max : LIFT_SHORT_CAP, LIFT_SHORT_CAP);
-        const int lds_max = std::min(l.lds_max > 0 ? l.lds_max : LIFT_LDS_CAP, LIFT_LDS_CAP);
-        const dim3 rows_grid((unsigned)((U + LIFT_THREADS - 1) / LIFT_THREADS));
-        hipLaunchKernelGGL((k_lift_classify<false>), rows_grid, dim3(LIFT_THREADS), 0, c->stream, l.rowstart, Ui, short_max, lds_max, l.sc + LIFT_SC_CLS,
-                           l.sc + LIFT_SC_CUR, nullptr, nullptr, nullptr, nullptr);
-        unsigned long long cls[LIFT_C_WORDS];
-        HIPCK(hipMemcpyAsync(cls, l.sc + LIFT_SC_CLS, sizeof(cls), hipMemcpyDeviceToHost, c->stream));
-        HIPCK(hipStreamSynchronize(c->stream));
-        for (int k = 0; k < LIFT_C_WORDS; k++) l.forms[k] = (long long)cls[k];
-        const long long n_short = l.forms[LIFT_C_SHORT_ROWS], n_lds = l.forms[LIFT_C_LDS_ROWS], n_long = l.forms[LIFT_C_LONG_ROWS];
-        const long long n_runs = l.forms[LIFT_C_RUNS], long_ent = l.forms[LIFT_C_LONG_ENT], max_long = l.forms[LIFT_C_MAX_LONG];
-        if (n_short + n_lds + n_long > U || long_ent > K || n_runs > K) return fail("%s: the work lists do not add up (device error)", who);
-        DALLOC(l.short_rows, (size_t)n_short);
-        DALLOC(l.lds_items, (size_t)n_lds);
-        DALLOC(l.run_items, (size_t)n_runs);
-        DALLOC(l.long_rows, (size_t)n_long);
-        DALLOC(l.scratch, (size_t)long_ent);
-        hipLaunchKernelGGL((k_lift_classify<true>), rows_grid, dim3(LIFT_THREADS), 0, c->stream, l.rowstart, Ui, short_max, lds_max, l.sc + LIFT_SC_CLS,
-                           l.sc + LIFT_SC_CUR, l.short_rows, l.lds_items, l.run_items, l.long_rows);
-        /* one launch per form */
-        timer.begin();
-        if (n_short > 0)
-            hipLaunchKernelGGL(k_lift_sort_wave, dim3((unsigned)((n_short + LIFT_THREADS / 64 - 1) / (LIFT_THREADS / 64))), dim3(LIFT_THREADS), 0, c->stream, l.short_rows,
-                               (int)n_short, l.rowstart, l.ent);
-        timer.end(LIFT_P_SORT_SHORT);
-        timer.begin();
-        if (n_lds > 0) hipLaunchKernelGGL(k_lift_sort_lds, dim3((unsigned)n_lds), dim3(LIFT_THREADS), 0, c->stream, l.lds_items, l.ent);
-        timer.end(LIFT_P_SORT_LDS);
-        timer.begin();
-        if (n_long > 0) {
-            if (n_runs > 0) hipLaunchKernelGGL(k_lift_sort_lds, dim3((unsigned)n_runs), dim3(LIFT_THREADS), 0, c->stream, l.run_items, l.ent);
-            const dim3 grid((unsigned)n_long, (unsigned)std::min<long long>(std::max<long long>((max_long + 4 * LIFT_THREADS - 1) / (4 * LIFT_THREADS), 1), 1024));
-            int to_scratch = 1;
-            for (long long width = lds_max; width < max_long; width *= 2, to_scratch ^= 1)
-                hipLaunchKernelGGL(k_lift_merge, grid, dim3(LIFT_THREADS), 0, c->stream, l.long_rows, l.ent, l.scratch, width, to_scratch);
-            if (!to_scratch) /* the merged rows are in the scratch buffer: a step with nothing left to merge copies them back */
-                hipLaunchKernelGGL(k_lift_merge, grid, dim3(LIFT_THREADS), 0, c->stream, l.long_rows, l.ent, l.scratch, max_long, 0);
-        }
-        timer.end(LIFT_P_SORT_LONG);
+        if (lift_sort_rows(c, who, timer, LIFT_P_SORT_SHORT, l.rowstart, Ui, l.ent, K, l.short_max, l.lds_max, l.sc + LIFT_SC_CLS, l.sc + LIFT_SC_CUR, l.forms,
+                           l.work))
+            return -1;
     }
     long long n_out = K;
     if (level == 1 && K > 0) {
-        /* the runs of equal columns: heads per chunk, their scan, the sums; the heads per row, their scan */
-        const long long chunks = (K + JUNC_CHUNK - 1) / JUNC_CHUNK;
-        DALLOC(l.bits, (size_t)(K + 31) / 32);
-        DALLOC(l.rtot, (size_t)chunks);
-        timer.begin();
-        HIPCK(hipMemsetAsync(l.bits, 0, ((size_t)(K + 31) / 32) * sizeof(unsigned), c->stream));
-        hipLaunchKernelGGL(k_lift_row_bits, dim3((unsigned)((U + LIFT_THREADS - 1) / LIFT_THREADS)), dim3(LIFT_THREADS), 0, c->stream, l.rowstart, Ui, l.bits);
-        hipLaunchKernelGGL(k_lift_head_totals, dim3((unsigned)chunks), dim3(JUNC_THREADS), 0, c->stream, l.ent, l.bits, K, l.rtot, l.sc + LIFT_SC_HEADS);
-        hipLaunchKernelGGL(k_junc_scan_tops, dim3(1), dim3(JUNC_THREADS), 0, c->stream, l.rtot, (int)chunks);
-        unsigned long long heads = 0;
-        HIPCK(hipMemcpyAsync(&heads, l.sc + LIFT_SC_HEADS, sizeof(heads), hipMemcpyDeviceToHost, c->stream));
-        HIPCK(hipStreamSynchronize(c->stream));
-        if (heads < 1 || heads > (unsigned long long)K) return fail("%s: %llu distinct entries of %lld (device error)", who, heads, K);
-        n_out = (long long)heads;
-        DALLOC(l.out_col, (size_t)n_out);
-        DALLOC(l.out_cnt, (size_t)n_out);
-        DALLOC(l.rowptr, (size_t)U + 1);
-        HIPCK(hipMemsetAsync(l.out_cnt, 0, (size_t)n_out * sizeof(unsigned long long), c->stream));
-        HIPCK(hipMemsetAsync(l.count, 0, ((size_t)U + 1) * sizeof(unsigned long long), c->stream));
-        hipLaunchKernelGGL(k_lift_reduce, dim3((unsigned)chunks), dim3(JUNC_THREADS), 0, c->stream, l.ent, l.bits, K, l.rtot, l.rowstart, Ui,
-                           (unsigned long long)n_out, l.out_col, l.out_cnt, l.count);
-        HIPCK(hipMemsetAsync(l.rowptr, 0, sizeof(unsigned long long), c->stream));
-        scan64_enqueue(c, l.count, l.rowptr + 1, 0, Ui, 1, l.tot);
-        timer.end(LIFT_P_REDUCE);
+        if (lift_reduce_rows(c, who, timer, LIFT_P_REDUCE, l.rowstart, Ui, l.ent, K, l.sc + LIFT_SC_HEADS, l.count, l.tot, l.work, &l.out_col, &l.out_cnt,
+                             &l.rowptr, &n_out))
+            return -1;
         HIPCK(hipStreamSynchronize(c->stream));
         hipFree(l.ent);
         l.ent = nullptr;

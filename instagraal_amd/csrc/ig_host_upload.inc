@@ -11,6 +11,7 @@ extern "C" int ig_upload_contacts(ig_ctx* c, const int32_t* row, const int32_t* 
     c->nh_valid = false;
     c->nh_pending_slot = -1;
     free_lift_buffers(c); /* (a built ig_assembly_contacts result is of the contacts that go away now) */
+    free_join_buffers(c, false); /* (and so is a built ig_join_support result) */
     std::vector<long long> rp((size_t)M + 1, 0);
     std::vector<int2> cc((size_t)Z);
     int max_count = 0;

@@ -18,13 +18,14 @@ SRC = os.path.join(HERE, "csrc", "ig_hip.hip")
 SRC_HOST = os.path.join(HERE, "csrc", "ig_draw.cpp")  # host-only part: the candidate draw
 DEPS = [SRC, SRC_HOST] + [os.path.join(HERE, "csrc", f) for f in ("ig_ops.cuh", "ig_common.cuh", "ig_model.cuh", "ig_kernels_setup.cuh",
                                                           "ig_kernels_score.cuh", "ig_kernels_screen.cuh", "ig_kernels_commit.cuh",
-                                                          "ig_kernels_nuis.cuh", "ig_kernels_map.cuh", "ig_kernels_law.cuh", "ig_kernels_junc.cuh", "ig_kernels_lift.cuh", "ig_host_core.inc", "ig_host_upload.inc",
-                                                          "ig_host_map.inc", "ig_host_law.inc", "ig_host_junc.inc", "ig_host_lift.inc",
+                                                          "ig_kernels_nuis.cuh", "ig_kernels_map.cuh", "ig_kernels_law.cuh", "ig_kernels_junc.cuh", "ig_kernels_lift.cuh", "ig_kernels_join.cuh", "ig_host_core.inc", "ig_host_upload.inc",
+                                                          "ig_host_map.inc", "ig_host_law.inc", "ig_host_junc.inc", "ig_host_lift.inc", "ig_host_join.inc",
                                                           "ig_host_batch.inc", "ig_host_nuis.inc", "ig_host_debug.inc")] + \
        [os.path.join(ROOT, "include", f) for f in ("ig_detmath.h", "ig_detmath_tables.h", "instagraal_hip.h")]
 
 N_TMP_STRUCT = 24
 ASSEMBLY_CONTACTS_PASSES = ("count", "scan", "scatter", "sort_short", "sort_lds", "sort_long", "reduce")  # ig_debug_assembly_contacts_time
+JOIN_SUPPORT_PASSES = ("ends", "count", "scan", "scatter", "sort_short", "sort_lds", "sort_long", "reduce", "model")  # ig_debug_join_support_time
 MAX_CANDIDATES = 16
 
 FRAG_FIELDS = ("pos", "sub_pos", "id_c", "start_bp", "len_bp", "sub_len", "circ", "id", "prev", "next", "l_cont",
@@ -767,6 +768,57 @@ class Context:
         ms = np.zeros((int(n), len(ASSEMBLY_CONTACTS_PASSES)), np.float32)
         ck = C.c_int64()
         _ck(lib().ig_debug_assembly_contacts_time(self._h, C.c_int32(LEVELS.index(level)), C.c_int32(int(n)), _p(ms), C.byref(ck)))
+        return ms, int(ck.value)
+
+    # ---- join support: which scaffold ends the contacts would link (the rule: join_support.py)
+    def join_support(self, window, model=True):
+        """builds the links between the ends of the placed linear contigs inside ``window`` positions as a snapshot on the device
+        -> dict: window, model, rowptr (int64 [2 K + 1]), first_position, n_positions (int32 [K]: per contig), n_links and the int64
+        scalars of ``join_support.SCALARS``; the links come through ``join_support_fetch``"""
+        from .join_support import SCALARS
+
+        ne, nl = C.c_int64(), C.c_int64()
+        sc = np.zeros(8, np.int64)
+        _ck(lib().ig_join_support_build(self._h, C.c_int32(int(window)), C.c_int32(int(bool(model))), C.byref(ne), C.byref(nl), _p(sc)))
+        K = ne.value // 2
+        rowptr = np.zeros(ne.value + 1, np.int64)
+        _ck(lib().ig_join_support_rows(self._h, _p(rowptr), C.c_int64(rowptr.size)))
+        first, n = np.zeros(K, np.int32), np.zeros(K, np.int32)
+        _ck(lib().ig_join_support_ends(self._h, _p(first), _p(n), C.c_int64(K)))
+        out = dict(window=int(window), model=bool(model), rowptr=rowptr, first_position=first, n_positions=n)
+        out.update((k, int(v)) for k, v in zip(SCALARS, sc))
+        return out
+
+    def join_support_fetch(self, first, n, model=True):
+        """links first .. first + n - 1 of the built result -> (col int32 [n], observed, pairs, expected_q int64 [n]; the last two
+        None with ``model=False``: a result built without the model has none)"""
+        n = int(n)
+        col, obs = np.zeros(max(n, 0), np.int32), np.zeros(max(n, 0), np.int64)
+        prs = np.zeros(max(n, 0), np.int64) if model else None
+        exq = np.zeros(max(n, 0), np.int64) if model else None
+        _ck(lib().ig_join_support_fetch(self._h, C.c_int64(int(first)), C.c_int64(n), _p(col), _p(obs), _p(prs), _p(exq)))
+        return col, obs, prs, exq
+
+    def join_support_release(self):
+        _ck(lib().ig_join_support_release(self._h))
+
+    def debug_join_support_combine(self, combine=True):
+        """the two passes over the contacts of the join support: one atomic per run of a wave's lanes with the same row (True) or
+        one per emission (False, the yardstick); None: the form the library ships"""
+        _ck(lib().ig_debug_join_support_combine(self._h, C.c_int32(-1 if combine is None else int(bool(combine)))))
+
+    def debug_join_support_forms(self):
+        """the last join support build's work lists, as ``debug_assembly_contacts_forms``"""
+        o = np.zeros(8, np.int64)
+        _ck(lib().ig_debug_join_support_forms(self._h, _p(o)))
+        return dict(short=(int(o[0]), int(o[1])), lds=(int(o[2]), int(o[3])), long=(int(o[4]), int(o[5])), runs=int(o[6]), longest=int(o[7]))
+
+    def debug_join_support_time(self, window, n=1):
+        """the build n times with hipEvents around each pass -> (ms [n, 9]: ``JOIN_SUPPORT_PASSES``, checksum of the observed part
+        of the last result)"""
+        ms = np.zeros((int(n), len(JOIN_SUPPORT_PASSES)), np.float32)
+        ck = C.c_int64()
+        _ck(lib().ig_debug_join_support_time(self._h, C.c_int32(int(window)), C.c_int32(int(n)), _p(ms), C.byref(ck)))
         return ms, int(ck.value)
 
     # ---- bookkeeping

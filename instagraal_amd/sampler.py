@@ -994,5 +994,45 @@ class sampler:  # noqa: N801 - the reference's class name
         out.update(level=level, contacts_diagonal=total, pixels_written=n)
         return out
 
+    # ----------------------------------------------------------- join support
+    def join_support(self, window=None, window_kb=None):
+        """Which scaffold ends the contacts would link (``ig_join_support_build``; the rule: ``join_support.py``): the junction
+        profile for the joins the sampler did NOT make.  For every pair of ends of the placed linear contigs with at least one
+        contact inside the window: the contacts that would span the join, the pairs that could, and what the model in use
+        (``param_simu``) would expect of them with the two ends adjacent.  ``window``: in positions (default 64), or ``window_kb``.
+        -> dict: ``rowptr`` (int64 [2 K + 1], CSR over the ends e = 2 k + side), ``col`` (int32), ``observed``, ``pairs``,
+        ``expected_q`` (int64 per link), the scalars of ``join_support.SCALARS``, ``expected`` (f64), ``ratio`` (observed / expected,
+        nan where expected is 0), ``ends`` (``join_support.ends_table``: scaffold, side, bin, sub-fragment, positions, bp per end),
+        ``first_position`` / ``n_positions`` per contig and ``order``.  No reference counterpart."""
+        from . import join_support as js
+
+        if window is not None and window_kb is not None:
+            raise ValueError("join_support: window or window_kb, not both")
+        if window_kb is not None:
+            window = js.window_from_kb(window_kb, self.mean_kb())
+        w = js.check_window(js.DEFAULT_WINDOW if window is None else window)
+        res = self.ctx.join_support(w)
+        try:
+            res["col"], res["observed"], res["pairs"], res["expected_q"] = self.ctx.join_support_fetch(0, res["n_links"])
+        finally:
+            self.ctx.join_support_release()
+        order = self.ctx.contact_map_order().astype(np.int64)
+        parent = self.np_sub_frags_2_frags["x"].astype(np.int64)
+        g = self.gpu_vect_frags.copy_from_gpu()
+        res["order"] = order
+        res["ends"] = js.ends_table(res["first_position"], res["n_positions"], order, parent, g.id_c, self.S_o_A_sub_frags["len_bp"])
+        res["expected"] = js.expected(res)
+        res["ratio"] = js.ratio(res)
+        return res
+
+    def best_joins(self, n=20, min_pairs=None, window=None, window_kb=None, result=None):
+        """The ``n`` links of ``join_support()`` with the highest observed / expected among those with at least ``min_pairs`` pairs
+        (default: half a full window, as ``weakest_junctions``), each with the runner-up ratio of both of its ends
+        (``join_support.best_joins``): a join is convincing when its ends have no close second."""
+        from . import join_support as js
+
+        res = self.join_support(window, window_kb) if result is None else result
+        return js.best_joins(res, n, min_pairs)
+
     def free_gpu(self):  # CL:3167-3177
         self.ctx.close()

@@ -194,7 +194,7 @@ class instagraal_class:
         self.collect_id_fA_sampled.append(id_frag)
 
     def full_em(self, n_cycles, n_neighbours, bomb, id_start_sample_param, save_matrix=False, save_law=False, save_junctions=False,
-                save_contacts=False):  # IG:196-291
+                save_contacts=False, save_joins=False):  # IG:196-291
         sampler = self.simulation.sampler
         if bomb:
             sampler.bomb_the_genome()
@@ -243,6 +243,10 @@ class instagraal_class:
                 jprof.write_profile(self._out("junctions_cycle_%d.txt" % j), sampler.junction_profile())
         if save_contacts:  # (once, behind the last cycle: the table is large)
             sampler.write_assembly_contacts(self._out("assembly_contacts"), level="sub")
+        if save_joins:  # (once, behind the last cycle: behind a bomb the table has up to four lines per contact)
+            from . import join_support as jsup
+
+            jsup.write_joins(self._out("joins.txt"), sampler.join_support())
         self.save_behaviour_to_txt()
 
     def save_behaviour_to_txt(self):  # IG:293-330
@@ -258,7 +262,7 @@ class instagraal_class:
 
 def run_instagraal(hic_folder, reference_fa, output_folder=None, level=4, cycles=100, coverage_std=1, neighborhood=5, device=0,
                    circular=False, bomb=False, pyramid_only=False, save_pickle=False, save_matrix=False, simple=False, save_law=False,
-                   save_junctions=False, save_contacts=False):
+                   save_junctions=False, save_contacts=False, save_joins=False):
     """IG:502-581 (defaults of cli/main.py: level 4, 100 cycles, 5 neighbours, 1 std).  The three trailing switches of the
     reference's signature (IG:512-514) are accepted: ``save_pickle`` dumps the run object to ``graal.pkl`` as the reference
     tries to (IG:589-594: a warning when it cannot be pickled -- device handles here, h5py handles there); ``save_matrix``
@@ -272,7 +276,10 @@ def run_instagraal(hic_folder, reference_fa, output_folder=None, level=4, cycles
     (``sampler.junction_profile``); ``save_contacts`` (an addition as well) writes the contacts in the coordinates of the
     final genome once, behind the last cycle, to ``assembly_contacts/bins.bed``, ``pixels.tsv`` and ``chrom.sizes`` -- sub-fragment
     resolution, sorted, upper-triangular: what ``cooler load -f coo bins.bed pixels.tsv`` takes -- with the scaffold names of
-    ``genome.fasta`` (``sampler.write_assembly_contacts``; not per cycle: the table has one line per contact)."""
+    ``genome.fasta`` (``sampler.write_assembly_contacts``, DESIGN 4.13; not per cycle: the table has one line per contact);
+    ``save_joins`` (an addition too) writes ``joins.txt`` once, behind the last cycle: one line per pair of scaffold ends that the
+    contacts link inside a window of 64 sub-fragments -- the joins the sampler did not make -- with the contacts observed, the pairs,
+    the model's expectation and their ratio (``sampler.join_support``)."""
     import warnings
 
     if simple and not pyramid_only:
@@ -292,7 +299,7 @@ def run_instagraal(hic_folder, reference_fa, output_folder=None, level=4, cycles
                       "after the sampler copied the fragment arrays)")
         p2.simulation.level.S_o_A_frags["circ"] += 1
     p2.full_em(n_cycles=cycles, n_neighbours=neighborhood, bomb=bomb, id_start_sample_param=4, save_matrix=save_matrix, save_law=save_law,
-               save_junctions=save_junctions, save_contacts=save_contacts)
+               save_junctions=save_junctions, save_contacts=save_contacts, save_joins=save_joins)
     if save_pickle:  # IG:589-594
         import pickle
 
