@@ -345,6 +345,24 @@ int ig_join_support_rows(ig_ctx* ctx, int64_t* rowptr, int64_t capacity);
 int ig_join_support_fetch(ig_ctx* ctx, int64_t first, int64_t n, int32_t* col, int64_t* observed, int64_t* pairs, int64_t* expected_q);
 int ig_join_support_release(ig_ctx* ctx);
 
+/* ---- the expected contact map of the current genome (no reference counterpart) -------------------------------------------
+ * What the model in use predicts for the pixels of ig_contact_map's image (same positions, same binning under max_side, same
+ * convention: symmetric, a pair inside one pixel counted twice on the diagonal); the rule is instagraal_amd/expected_map.py.
+ * Three images of side x side int64 each (image_capacity: entries of room in EACH): cis_q, the sum of the model's value under
+ * parameter set 0 at s = |dist_i - dist_k| (f32), quantised as every term of the likelihood is (multiples of 2^-32), over the pairs
+ * of positions i < k of one placed contig that is not a ring; cis_pairs, the number of these pairs; ring_pairs, the number of pairs
+ * on a ring (they get no model value).  The trans pairs follow on the host: n_a n_b less the two counts, each worth the quantised
+ * v_inter.
+ * scalars: {n_placed, linear_cis_pairs, ring_pairs, max_q: the largest |quantised value| seen, tiles_evaluated, tiles_constant (both
+ * 0 under the row form), 0, 0}.  *side and *bin are set before the capacity is checked.  T == 0: side = 0 and success.
+ * Fails where parameters were never set, max_side < 1, a capacity is below side^2, or 2 bin^2 max(max_q, q_trans) >= 2^62 ("model
+ * value too large for this pixel size").
+ * Guards and effects as ig_contact_map: reads the CURRENT coordinates, changes nothing a move reads, synchronous, an error while a
+ * nuisance step or a chain is in flight.  No contact is read (none need be uploaded): the result is independent of the shard
+ * (ig_set_shard), whole on every rank.  Device memory: 24 bytes per pixel during the call, nothing behind it. */
+int ig_expected_map(ig_ctx* ctx, int32_t max_side, int64_t* cis_q, int64_t* cis_pairs, int64_t* ring_pairs, int64_t image_capacity,
+                    int32_t* side, int32_t* bin, int64_t scalars[8]);
+
 /* ---- multi-GPU (contact shards) -------------------------- */
 /* Two-phase move: partial sums over this handle's contact shard are left in a device buffer of
  * ig_partials_count() int64 values; the caller all-reduces (SUM) it across ranks, then finishes. */
@@ -451,6 +469,14 @@ int ig_debug_join_support_forms(ig_ctx* ctx, int64_t out8[8]);
  * scatter, sort short, sort lds, sort long, reduce, model}; the last result stays built; *checksum (may be NULL): its rows, columns
  * and observed, each word weighted by its place */
 int ig_debug_join_support_time(ig_ctx* ctx, int32_t window, int32_t n, float* ms_n, int64_t* checksum);
+/* the expected map: the form of THIS handle's builds: 0 the form the library ships, 1 rows (one thread per position, atomics: the
+ * yardstick), 2 tiles (one workgroup per pixel pair that can hold a cis pair, no atomics on the images), 3 tiles without the
+ * constant-tile shortcut.  With one position per pixel the row form runs whatever is set.  The images are the same. */
+int ig_debug_expected_map_form(ig_ctx* ctx, int32_t form);
+/* the build under that form (as above) n times, hipEvents around each (zero, the passes, the mirrors; the tile form's wait for the
+ * size of its list included): ms_n[n]; *checksum (may be NULL): the three images of the last build, the two pair counts and max_q,
+ * each word weighted by its place: every form must agree on it */
+int ig_debug_expected_map_time(ig_ctx* ctx, int32_t max_side, int32_t form, int32_t n, float* ms_n, int64_t* checksum);
 #ifdef __cplusplus
 }
 #endif

@@ -426,6 +426,19 @@ struct JoinBuf {
     int combine = -1; /* ig_debug_join_support_combine: 1 / 0, -1: the form the library ships (JOIN_SHIP_COMBINE) */
 };
 
+/* the expected contact map of the current genome (ig_kernels_emap.cuh): every buffer of the feature, freed by free_emap_buffers
+ * (ig_host_emap.inc) at the end of every call */
+struct EmapBuf {
+    unsigned long long* img = nullptr; /* [3][side^2] cis_q, cis_pairs, ring_pairs */
+    unsigned long long* sc = nullptr;  /* EMAP_NS words */
+    unsigned long long* cnt = nullptr; /* tile form: [side] listed tiles per pixel */
+    unsigned long long* off = nullptr; /* [side + 1] their exclusive prefix sums */
+    unsigned long long* tot = nullptr; /* the scan's chunk totals */
+    int2* list = nullptr;              /* [list_cap] the listed tiles (a, b) */
+    unsigned long long list_cap = 0;
+    int form = 0; /* ig_debug_expected_map_form: 0 the form the library ships (EMAP_TILE_MIN_BIN), 1 rows, 2 tiles, 3 tiles without the constant shortcut */
+};
+
 struct ig_ctx {
     int device;
     hipStream_t stream;
@@ -533,6 +546,7 @@ struct ig_ctx {
     JuncBuf junc;
     LiftBuf lift;
     JoinBuf join;
+    EmapBuf emap;
     int* batch_out; /* committed moves, pending slot, (unused), candidates, predicted deltas used, contigs */
     int *host_bo, *host_bo_dev; /* the same in mapped host memory (+ [7] = sequence number of the decide launch), and its device address */
     int bo_seq;

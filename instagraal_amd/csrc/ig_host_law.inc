@@ -20,16 +20,10 @@ static void free_law_buffers(ig_ctx* c)
     c->law = LawBuf{};
 }
 
-/* The records both passes read, without the edges (the junction profile shares them, ig_host_junc.inc): the guards of the map
- * (map_prepare), the genome order, then on the library's stream k_law_records and, want_sorted, k_law_sorted.  Not waited for.
- * T: placed sub-fragments. */
-static int law_records(ig_ctx* c, const char* who, bool want_sorted, int* T_out)
+/* the law's buffers, kept from call to call */
+static int law_ensure_buffers(ig_ctx* c)
 {
-    if (!c->have_contacts) return fail("%s: upload the contacts first", who);
-    int T = 0, bin = 1, side = 0;
-    /* max_side = M >= T: one position per pixel, so rec.w is the position itself (the law reads its sign only, the junction
-     * profile the position) */
-    if (map_prepare(c, who, std::max(c->M, 1), true, &T, &bin, &side)) return -1;    LawBuf& l = c->law;
+    LawBuf& l = c->law;
     const int M = c->M;
     if (l.M != M) {
         free_law_buffers(c);
@@ -41,8 +35,30 @@ static int law_records(ig_ctx* c, const char* who, bool want_sorted, int* T_out)
         DALLOC(l.flag, 1);
         l.M = M;
     }
-    hipLaunchKernelGGL(k_law_records, dim3((M + 255) / 256), dim3(256), 0, c->stream, c->tab, c->map.pix, M, l.rec);
-    if (want_sorted && T > 0) hipLaunchKernelGGL(k_law_sorted, dim3((T + 255) / 256), dim3(256), 0, c->stream, c->tab, c->map.order, M, T, l.ds, l.meta);
+    return 0;
+}
+
+/* ds and meta by position of the genome order (map_prepare with want_order has run), on the library's stream; the expected map
+ * (ig_host_emap.inc), which reads no contact and so needs no record, takes these alone */
+static void law_enqueue_sorted(ig_ctx* c, int T)
+{
+    if (T > 0) hipLaunchKernelGGL(k_law_sorted, dim3((T + 255) / 256), dim3(256), 0, c->stream, c->tab, c->map.order, c->M, T, c->law.ds, c->law.meta);
+}
+
+/* The records both passes read, without the edges (the junction profile shares them, ig_host_junc.inc): the guards of the map
+ * (map_prepare), the genome order, then on the library's stream k_law_records and, want_sorted, k_law_sorted.  Not waited for.
+ * T: placed sub-fragments. */
+static int law_records(ig_ctx* c, const char* who, bool want_sorted, int* T_out)
+{
+    if (!c->have_contacts) return fail("%s: upload the contacts first", who);
+    int T = 0, bin = 1, side = 0;
+    /* max_side = M >= T: one position per pixel, so rec.w is the position itself (the law reads its sign only, the junction
+     * profile the position) */
+    if (map_prepare(c, who, std::max(c->M, 1), true, &T, &bin, &side)) return -1;
+    if (law_ensure_buffers(c)) return -1;
+    const int M = c->M;
+    hipLaunchKernelGGL(k_law_records, dim3((M + 255) / 256), dim3(256), 0, c->stream, c->tab, c->map.pix, M, c->law.rec);
+    if (want_sorted) law_enqueue_sorted(c, T);
     *T_out = T;
     return 0;
 }

@@ -18,8 +18,8 @@ SRC = os.path.join(HERE, "csrc", "ig_hip.hip")
 SRC_HOST = os.path.join(HERE, "csrc", "ig_draw.cpp")  # host-only part: the candidate draw
 DEPS = [SRC, SRC_HOST] + [os.path.join(HERE, "csrc", f) for f in ("ig_ops.cuh", "ig_common.cuh", "ig_model.cuh", "ig_kernels_setup.cuh",
                                                           "ig_kernels_score.cuh", "ig_kernels_screen.cuh", "ig_kernels_commit.cuh",
-                                                          "ig_kernels_nuis.cuh", "ig_kernels_map.cuh", "ig_kernels_law.cuh", "ig_kernels_junc.cuh", "ig_kernels_lift.cuh", "ig_kernels_join.cuh", "ig_host_core.inc", "ig_host_upload.inc",
-                                                          "ig_host_map.inc", "ig_host_law.inc", "ig_host_junc.inc", "ig_host_lift.inc", "ig_host_join.inc",
+                                                          "ig_kernels_nuis.cuh", "ig_kernels_map.cuh", "ig_kernels_law.cuh", "ig_kernels_junc.cuh", "ig_kernels_lift.cuh", "ig_kernels_join.cuh", "ig_kernels_emap.cuh", "ig_host_core.inc", "ig_host_upload.inc",
+                                                          "ig_host_map.inc", "ig_host_law.inc", "ig_host_junc.inc", "ig_host_lift.inc", "ig_host_join.inc", "ig_host_emap.inc",
                                                           "ig_host_batch.inc", "ig_host_nuis.inc", "ig_host_debug.inc")] + \
        [os.path.join(ROOT, "include", f) for f in ("ig_detmath.h", "ig_detmath_tables.h", "instagraal_hip.h")]
 
@@ -714,6 +714,45 @@ class Context:
         _ck(lib().ig_debug_junction_profile_time(self._h, C.c_int32(int(window)), C.c_int32(int(bool(combine))), C.c_int32(int(n)), _p(ms_o),
                                                  _p(ms_m), _p(ms_s), C.byref(ck)))
         return ms_o, ms_m, ms_s, int(ck.value)
+
+    # ---- the expected contact map of the current genome (the rule: expected_map.py)
+    def expected_map(self, max_side):
+        """what the model in use predicts for the pixels of ``contact_map(max_side)`` -> dict: side, bin, the int64 [side, side]
+        images ``cis_q``, ``cis_pairs``, ``ring_pairs`` and the int64 scalars of ``expected_map.SCALARS``"""
+        from .contact_map import binning
+        from .expected_map import IMAGES, SCALARS
+
+        max_side = int(max_side)
+        if not 1 <= max_side <= 2 ** 31 - 1:
+            raise HipError("expected_map: max_side must be >= 1 (got %d)" % max_side)
+        cap = min(max_side, max(self.M, 1))  # side <= min(max_side, T), T <= M
+        if cap * cap > 1 << 24:  # (three buffers of that many entries only if the images really have them)
+            cap = max(binning(self.contact_map_order().size, max_side)[1], 1)
+        img = np.empty((3, cap * cap), np.int64)
+        side, b = C.c_int32(), C.c_int32()
+        sc = np.zeros(8, np.int64)
+        _ck(lib().ig_expected_map(self._h, C.c_int32(max_side), _p(img[0]), _p(img[1]), _p(img[2]), C.c_int64(cap * cap), C.byref(side), C.byref(b), _p(sc)))
+        n = side.value
+        out = dict(side=n, bin=b.value)
+        out.update((k, img[i, :n * n].reshape(n, n).copy()) for i, k in enumerate(IMAGES))
+        out.update((k, int(v)) for k, v in zip(SCALARS, sc))
+        return out
+
+    def debug_expected_map_form(self, form=0):
+        """the form of this handle's builds: 0 / "default", 1 / "rows", 2 / "tiles", 3 / "tiles_plain" (``expected_map.FORMS``)"""
+        from .expected_map import FORMS
+
+        _ck(lib().ig_debug_expected_map_form(self._h, C.c_int32(FORMS.index(form) if form in FORMS else int(form))))
+
+    def debug_expected_map_time(self, max_side, form=0, n=1):
+        """the build under ``form`` n times with hipEvents around each -> (milliseconds [n], checksum of the last build)"""
+        from .expected_map import FORMS
+
+        ms = np.zeros(int(n), np.float32)
+        ck = C.c_int64()
+        _ck(lib().ig_debug_expected_map_time(self._h, C.c_int32(int(max_side)), C.c_int32(FORMS.index(form) if form in FORMS else int(form)), C.c_int32(int(n)),
+                                             _p(ms), C.byref(ck)))
+        return ms, int(ck.value)
 
     # ---- the contacts in the coordinates of the current genome (the rule: assembly_contacts.py)
     def assembly_contacts(self, level="sub"):

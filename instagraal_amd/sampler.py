@@ -1034,5 +1034,64 @@ class sampler:  # noqa: N801 - the reference's class name
         res = self.join_support(window, window_kb) if result is None else result
         return js.best_joins(res, n, min_pairs)
 
+    # ----------------------------------------------------------- expected map
+    def expected_map(self, max_side=2048):
+        """What the model in use (``param_simu``) predicts for the pixels of ``contact_map(max_side)`` (``ig_expected_map``; the
+        rule: ``expected_map.py``): one model value for every pair of sub-fragments that share a linear contig, summed per pixel
+        on the device, the trans level for the pairs of different contigs.  -> the device's dict (side, bin, ``cis_q``,
+        ``cis_pairs``, ``ring_pairs``, the scalars) plus ``total``, ``trans_pairs``, ``expected_q`` (int64 images) and ``expected``
+        (f64: contacts).  Pixels that hold a pair on a ring get no model value for it (``ring_pairs`` says which).  No reference
+        counterpart."""
+        from . import expected_map as em
+
+        if self.param_simu is None:
+            raise ValueError("expected_map: set the parameters first (set_param_simu)")
+        return em.compose(self.ctx.expected_map(max_side), em.quantize(np.float32(self.param_simu["v_inter"][0])))
+
+    def residual_map(self, max_side=2048):
+        """The observed image of the current genome (the device's: without the input matrix's diagonal, self-contacts have no model
+        term) against ``expected_map``: -> dict: ``observed``, ``expected``, ``log2_ratio`` = log2(O / E), ``z`` = (O - E) / sqrt(E)
+        (both nan where E == 0 or the pixel holds a ring pair: ``mask``), side, bin, n_placed, total."""
+        from . import expected_map as em
+
+        result = self.expected_map(max_side)
+        observed, _ = self.ctx.contact_map(max_side)
+        res = em.residuals(observed, result)
+        res.update((k, result[k]) for k in em.SCALARS)
+        return res
+
+    def strongest_residuals(self, n=20, min_pairs=None, max_side=2048, residuals=None):
+        """The ``n`` pixels off the diagonal with the largest z (``expected_map.strongest``): where a block has far more contacts
+        with another than the model allows at their separation -- where it belongs.  ``min_pairs`` defaults to half of bin^2."""
+        from . import expected_map as em
+
+        res = self.residual_map(max_side) if residuals is None else residuals
+        order = self.ctx.contact_map_order().astype(np.int64)
+        parent = self.np_sub_frags_2_frags["x"].astype(np.int64)
+        contig = self.gpu_vect_frags.copy_from_gpu().id_c.astype(np.int64)[parent]
+        return em.strongest(res, n, min_pairs, contig[order])
+
+    def display_residual_matrix(self, filename, max_side=2048):
+        """Writes the picture of log2(observed / expected) of the current genome, clipped at +- 3, masked pixels grey; returns what
+        ``residual_map`` returns."""
+        from . import expected_map as em
+
+        res = self.residual_map(max_side)
+        # matplotlib only here, and without pyplot (as display_current_matrix)
+        from matplotlib.backends.backend_agg import FigureCanvasAgg
+        from matplotlib.figure import Figure
+
+        fig = Figure(figsize=(14, 14))
+        FigureCanvasAgg(fig)
+        ax = fig.subplots()
+        ax.set_facecolor("lightgrey")
+        shown = np.ma.masked_invalid(np.clip(res["log2_ratio"], -em.CLIP_LOG2, em.CLIP_LOG2))
+        im = ax.imshow(shown, cmap="RdBu_r", vmin=-em.CLIP_LOG2, vmax=em.CLIP_LOG2, interpolation="nearest")
+        ax.set_xticks([])
+        ax.set_yticks([])
+        fig.colorbar(im, ax=ax, shrink=0.6, label="log2(observed / expected)")
+        fig.savefig(filename, dpi=200, bbox_inches="tight")
+        return res
+
     def free_gpu(self):  # CL:3167-3177
         self.ctx.close()

@@ -194,7 +194,7 @@ class instagraal_class:
         self.collect_id_fA_sampled.append(id_frag)
 
     def full_em(self, n_cycles, n_neighbours, bomb, id_start_sample_param, save_matrix=False, save_law=False, save_junctions=False,
-                save_contacts=False, save_joins=False):  # IG:196-291
+                save_contacts=False, save_joins=False, save_residuals=False):  # IG:196-291
         sampler = self.simulation.sampler
         if bomb:
             sampler.bomb_the_genome()
@@ -241,6 +241,11 @@ class instagraal_class:
                 from . import junction_profile as jprof
 
                 jprof.write_profile(self._out("junctions_cycle_%d.txt" % j), sampler.junction_profile())
+            if save_residuals:  # (no reference counterpart: this cycle's genome against what the model predicts of it)
+                from . import expected_map as emap
+
+                res = sampler.display_residual_matrix(self._out("residuals_cycle_%d.png" % j))
+                emap.write_residuals(self._out("residuals_cycle_%d.txt" % j), sampler.strongest_residuals(residuals=res), res)
         if save_contacts:  # (once, behind the last cycle: the table is large)
             sampler.write_assembly_contacts(self._out("assembly_contacts"), level="sub")
         if save_joins:  # (once, behind the last cycle: behind a bomb the table has up to four lines per contact)
@@ -262,7 +267,7 @@ class instagraal_class:
 
 def run_instagraal(hic_folder, reference_fa, output_folder=None, level=4, cycles=100, coverage_std=1, neighborhood=5, device=0,
                    circular=False, bomb=False, pyramid_only=False, save_pickle=False, save_matrix=False, simple=False, save_law=False,
-                   save_junctions=False, save_contacts=False, save_joins=False):
+                   save_junctions=False, save_contacts=False, save_joins=False, save_residuals=False):
     """IG:502-581 (defaults of cli/main.py: level 4, 100 cycles, 5 neighbours, 1 std).  The three trailing switches of the
     reference's signature (IG:512-514) are accepted: ``save_pickle`` dumps the run object to ``graal.pkl`` as the reference
     tries to (IG:589-594: a warning when it cannot be pickled -- device handles here, h5py handles there); ``save_matrix``
@@ -279,7 +284,10 @@ def run_instagraal(hic_folder, reference_fa, output_folder=None, level=4, cycles
     ``genome.fasta`` (``sampler.write_assembly_contacts``, DESIGN 4.13; not per cycle: the table has one line per contact);
     ``save_joins`` (an addition too) writes ``joins.txt`` once, behind the last cycle: one line per pair of scaffold ends that the
     contacts link inside a window of 64 sub-fragments -- the joins the sampler did not make -- with the contacts observed, the pairs,
-    the model's expectation and their ratio (``sampler.join_support``)."""
+    the model's expectation and their ratio (``sampler.join_support``); ``save_residuals`` (an addition too) writes after
+    every cycle ``residuals_cycle_<j>.png``, log2(observed / expected) of that genome's contact map against what the model in use
+    predicts for every pixel, and ``residuals_cycle_<j>.txt``, the 20 pixels off the diagonal with the largest excess
+    (``sampler.residual_map``, ``sampler.strongest_residuals``)."""
     import warnings
 
     if simple and not pyramid_only:
@@ -299,7 +307,7 @@ def run_instagraal(hic_folder, reference_fa, output_folder=None, level=4, cycles
                       "after the sampler copied the fragment arrays)")
         p2.simulation.level.S_o_A_frags["circ"] += 1
     p2.full_em(n_cycles=cycles, n_neighbours=neighborhood, bomb=bomb, id_start_sample_param=4, save_matrix=save_matrix, save_law=save_law,
-               save_junctions=save_junctions, save_contacts=save_contacts, save_joins=save_joins)
+               save_junctions=save_junctions, save_contacts=save_contacts, save_joins=save_joins, save_residuals=save_residuals)
     if save_pickle:  # IG:589-594
         import pickle
 
