@@ -363,6 +363,32 @@ int ig_join_support_release(ig_ctx* ctx);
 int ig_expected_map(ig_ctx* ctx, int32_t max_side, int64_t* cis_q, int64_t* cis_pairs, int64_t* ring_pairs, int64_t image_capacity,
                     int32_t* side, int32_t* bin, int64_t scalars[8]);
 
+/* ---- placement support: where the contacts say each bin belongs (no reference counterpart; the rule:
+ * instagraal_amd/placement_support.py) --------------------------------------------------------------------------------------------
+ * A GUEST is a placed bin of a linear contig (the runs k = 0 .. K - 1 of ig_contact_map_order, as the join support numbers them); its
+ * positions are consecutive, n_positions of them.  With the guest taken out of the order, a SITE (k, u) is the gap in front of
+ * offset u of contig k (u = 0: off the head, u = the contig's remaining positions: off the tail); its window is the up to `window`
+ * (1 .. 1024) positions on its left and on its right, `hosts` in all.  The guest's contacts with other bins (both ends in linear placed
+ * contigs) inside the two halves are *_left and *_right.  home: the site where the guest sits (contig, offset).  best: among the
+ * sites with hosts >= min_hosts (1 .. 2 window) whose window is disjoint from home's (another contig, or at least 2 window sites
+ * away) the one with the highest (left + right) / hosts, compared with exact integers, the lowest (contig, offset) among equals;
+ * best_contig = -1: no such site has a contact.  second: the same among the sites in another contig than the best or at least
+ * 2 window sites from it.  Every array has N entries (the bins) and belongs to the caller; status: 0 guest, 1 not placed, 2 on a
+ * ring -- the rows of bins that are no guests are 0, their contig fields -1.  The arrays are the rule's byte for byte, whatever the
+ * launch shapes, the form of the scan and the order in which atomics land.
+ * scalars: {0 unplaced_observed (an end in a contig that is not placed; checked first), 1 ring_observed (then: an end on a ring), 2
+ * within_bin_observed (then: both ends in one bin), 3 counted_observed, 4 entries (two per counted contact), 5 n_contigs = K, 6
+ * n_guests}.  [0] + .. + [3] = the sum of all counts.
+ * Device memory: during the call 8 bytes per entry and as much again for long rows, 20 bytes per summed entry, 140 bytes per bin;
+ * nothing behind it (also not behind a call that fails).  A call whose entries do not fit the free device memory fails before it
+ * allocates them and names the bytes it needs; so does one with 2 window sum(counts) >= 2^62 ("counts too large for this window").
+ * Guards and effects as ig_contact_map: reads the CURRENT coordinates, changes nothing a move reads, synchronous, an error while a
+ * nuisance step or a chain is in flight.  A sharded handle (ig_set_shard) is refused: the maximum needs the whole profile. */
+int ig_placement_support(ig_ctx* ctx, int32_t window, int32_t min_hosts, int32_t* status, int32_t* contig, int32_t* offset, int32_t* n_positions,
+                         int32_t* home_hosts, int32_t* best_contig, int32_t* best_offset, int32_t* best_hosts, int32_t* second_contig,
+                         int32_t* second_offset, int32_t* second_hosts, int64_t* home_left, int64_t* home_right, int64_t* best_left,
+                         int64_t* best_right, int64_t* second_left, int64_t* second_right, int64_t scalars[7]);
+
 /* ---- multi-GPU (contact shards) -------------------------- */
 /* Two-phase move: partial sums over this handle's contact shard are left in a device buffer of
  * ig_partials_count() int64 values; the caller all-reduces (SUM) it across ranks, then finishes. */
@@ -477,6 +503,15 @@ int ig_debug_expected_map_form(ig_ctx* ctx, int32_t form);
  * size of its list included): ms_n[n]; *checksum (may be NULL): the three images of the last build, the two pair counts and max_q,
  * each word weighted by its place: every form must agree on it */
 int ig_debug_expected_map_time(ig_ctx* ctx, int32_t max_side, int32_t form, int32_t n, float* ms_n, int64_t* checksum);
+/* placement support: the form of the scan of THIS handle's calls: 0 the form the library ships (a wave per row of more than
+ * PLACE_WAVE_ENTRIES summed entries, a thread per shorter row), 1 a thread per row (the yardstick), 2 a wave per row.  The arrays are
+ * the same.  The limits of ig_debug_assembly_contacts_limits hold for this feature's sorts too. */
+int ig_debug_placement_support_form(ig_ctx* ctx, int32_t form);
+/* the last placement support call's work lists, as ig_debug_assembly_contacts_forms */
+int ig_debug_placement_support_forms(ig_ctx* ctx, int64_t out8[8]);
+/* the call n times, hipEvents around each pass: ms_n[n][10] = {records, count, rows, scatter, sort short, sort lds, sort long, reduce,
+ * prefix, scan}; *checksum (may be NULL): the arrays of the last call, each word weighted by its place: every form must agree on it */
+int ig_debug_placement_support_time(ig_ctx* ctx, int32_t window, int32_t min_hosts, int32_t n, float* ms_n, int64_t* checksum);
 #ifdef __cplusplus
 }
 #endif

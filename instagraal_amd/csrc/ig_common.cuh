@@ -426,6 +426,32 @@ struct JoinBuf {
     int combine = -1; /* ig_debug_join_support_combine: 1 / 0, -1: the form the library ships (JOIN_SHIP_COMBINE) */
 };
 
+/* placement support (ig_kernels_place.cuh): every buffer of the feature, freed by free_place_buffers (ig_host_place.inc) at the end
+ * of every call -- no snapshot stays on the device */
+struct PlaceBuf {
+    unsigned long long* head = nullptr;   /* [T + 1] the join support's heads ... */
+    unsigned long long* incl = nullptr;   /* [T + 1] ... their running sum */
+    int4* rec = nullptr;                  /* [M] ... and records: (depth, depth, run index, position) per sub-fragment */
+    struct JoinEnd* ends = nullptr;       /* [K] */
+    unsigned long long* tot = nullptr;    /* the scans' chunk totals */
+    int4* bins = nullptr;                 /* [N] (first position, positions, run index, 0) per bin */
+    unsigned long long* count = nullptr;  /* [N + 2] emissions per row; later: summed entries per row */
+    unsigned long long* cursor = nullptr; /* [N + 2] the scatter's cursors */
+    unsigned long long* sc = nullptr;     /* PLACE_SC_WORDS (ig_host_place.inc) */
+    unsigned long long* rowstart = nullptr; /* [N + 1] first entry of every row behind the scatter */
+    unsigned long long* ent = nullptr;    /* [entries] position << 32 | count */
+    LiftWork work;
+    unsigned long long* rowptr = nullptr; /* [N + 1] the rows of the summed entries */
+    int* out_col = nullptr;               /* [n_summed] positions */
+    unsigned long long* out_cnt = nullptr; /* [n_summed] counts */
+    unsigned long long* pre = nullptr;    /* [n_summed + 1] their exclusive prefix sums */
+    unsigned long long* ptot = nullptr;   /* that scan's chunk totals */
+    int* out_i = nullptr;                 /* [PLACE_NI][N] */
+    long long* out_l = nullptr;           /* [PLACE_NL][N] */
+    long long forms[8] = {0, 0, 0, 0, 0, 0, 0, 0}; /* the last call's LIFT_C_* words */
+    int form = 0; /* ig_debug_placement_support_form: 0 the form the library ships (PLACE_WAVE_ENTRIES), 1 a thread per row, 2 a wave per row */
+};
+
 /* the expected contact map of the current genome (ig_kernels_emap.cuh): every buffer of the feature, freed by free_emap_buffers
  * (ig_host_emap.inc) at the end of every call */
 struct EmapBuf {
@@ -547,6 +573,7 @@ struct ig_ctx {
     LiftBuf lift;
     JoinBuf join;
     EmapBuf emap;
+    PlaceBuf place;
     int* batch_out; /* committed moves, pending slot, (unused), candidates, predicted deltas used, contigs */
     int *host_bo, *host_bo_dev; /* the same in mapped host memory (+ [7] = sequence number of the decide launch), and its device address */
     int bo_seq;

@@ -30,7 +30,8 @@
  * k_lift_keys, k_lift_pass, k_lift_classify, k_lift_sort_wave / _lds, k_lift_merge, k_lift_row_bits, k_lift_head_totals, k_lift_reduce
  * (DESIGN.md 4.13); the join support of its scaffold ends: k_join_heads, k_join_ends, k_join_records, k_join_emit, k_join_model, with
  * the sorts and the reduction of 4.13; its expected contact map: k_emap_count, k_emap_rows, k_emap_list,
- * k_emap_tiles, with the scan of 4.12 and the mirror of 4.10.
+ * k_emap_tiles, with the scan of 4.12 and the mirror of 4.10; the placement support of its bins: k_place_bins,
+ * k_place_emit, k_place_scan, with the records of 4.14, the sorts and the reduction of 4.13 and the scan of 4.12.
  *
  * Environment knobs (tests, fault injection and tuning only; the table in INTEGRATION.md section 4 is the reference): IG_BATCH_W, IG_WINDOW
  * (widths), IG_POOL_ENTRIES, IG_WIDE_LISTS, IG_NO_HOST_FLAG, IG_POISON_ALLOC / IG_POISON_ONLY (force the rare paths), IG_SCREEN,
@@ -56,8 +57,9 @@
 #include "ig_kernels_lift.cuh"
 #include "ig_kernels_join.cuh"
 #include "ig_kernels_emap.cuh"
+#include "ig_kernels_place.cuh"
 
-/* ================================================================== host side (one translation unit, eleven parts) */
+/* ================================================================== host side (one translation unit, twelve parts) */
 #include "ig_host_core.inc"
 #include "ig_host_upload.inc"
 #include "ig_host_map.inc"
@@ -66,6 +68,7 @@
 #include "ig_host_lift.inc"
 #include "ig_host_join.inc"
 #include "ig_host_emap.inc"
+#include "ig_host_place.inc"
 #include "ig_host_batch.inc"
 #include "ig_host_nuis.inc"
 #include "ig_host_debug.inc"

@@ -60,6 +60,38 @@ static void free_join_buffers(ig_ctx* c, bool keep_snapshot)
     j.combine = combine;
 }
 
+/* The ends and the records (pass 1), shared with the placement support (ig_host_place.inc): the heads of the linear placed contigs,
+ * their 64-bit scan, the table per contig and one record per sub-fragment, on the library's stream behind law_records (c->law.meta,
+ * c->map.pix, c->map.order of T placed positions).  Allocates head, incl: [T + 1]; tot: the scans' chunk totals over 2 M + 3 words;
+ * ends: [K]; rec: [M] -- the caller's buffers, freed by the caller whatever happens.  Waits once, for K. */
+static int join_enqueue_records(ig_ctx* c, const char* who, int T, unsigned long long*& head, unsigned long long*& incl, unsigned long long*& tot, int4*& rec,
+                                JoinEnd*& ends, long long* K_out)
+{
+    const int M = c->M;
+    long long K = 0;
+    DALLOC(rec, (size_t)M);
+    DALLOC(head, (size_t)T + 1);
+    DALLOC(incl, (size_t)T + 1);
+    DALLOC(tot, (size_t)junc_chunks(2 * M + 3));
+    if (T > 0) {
+        hipLaunchKernelGGL(k_join_heads, dim3((T + JOIN_THREADS - 1) / JOIN_THREADS), dim3(JOIN_THREADS), 0, c->stream, c->law.meta, T, head);
+        scan64_enqueue(c, head, incl, 0, T, 1, tot);
+        unsigned long long n_heads = 0;
+        HIPCK(hipMemcpyAsync(&n_heads, incl + (T - 1), sizeof(n_heads), hipMemcpyDeviceToHost, c->stream));
+        HIPCK(hipStreamSynchronize(c->stream));
+        if (n_heads > (unsigned long long)T) return fail("%s: %llu contigs over %d positions (inconsistent tables)", who, n_heads, T);
+        K = (long long)n_heads;
+    }
+    const int Ki = (int)K; /* K <= T <= M */
+    DALLOC(ends, (size_t)K);
+    if (K > 0)
+        hipLaunchKernelGGL(k_join_ends, dim3((T + JOIN_THREADS - 1) / JOIN_THREADS), dim3(JOIN_THREADS), 0, c->stream, c->law.meta, incl, T, Ki, c->map.order, M, c->sub_tab,
+                           c->st.LB, c->N, ends);
+    hipLaunchKernelGGL(k_join_records, dim3((M + JOIN_THREADS - 1) / JOIN_THREADS), dim3(JOIN_THREADS), 0, c->stream, c->map.pix, M, T, c->law.meta, incl, Ki, rec);
+    *K_out = K;
+    return 0;
+}
+
 /* The build, up to the snapshot's fields.  The caller frees what it leaves behind and, on an error, the half-built snapshot. */
 static int join_build_impl(ig_ctx* c, const char* who, int window, bool model, float* ms)
 {
@@ -68,32 +100,14 @@ static int join_build_impl(ig_ctx* c, const char* who, int window, bool model, f
     int T = 0;
     if (law_records(c, who, true, &T)) return -1; /* (the guards of the map under this entry point's name; max_side = M: pix is the position) */
     if (model && !c->have_params) return fail("%s: set parameters first", who);
-    const int M = c->M;
     LiftTimer timer(c, ms, JOIN_PASSES);
     DALLOC(j.sc, (size_t)JOIN_SC_WORDS);
     HIPCK(hipMemsetAsync(j.sc, 0, JOIN_SC_WORDS * sizeof(unsigned long long), c->stream));
     /* the ends */
     long long K = 0;
     timer.begin();
-    DALLOC(j.rec, (size_t)M);
-    DALLOC(j.head, (size_t)T + 1);
-    DALLOC(j.incl, (size_t)T + 1);
-    DALLOC(j.tot, (size_t)junc_chunks(2 * M + 3));
-    if (T > 0) {
-        hipLaunchKernelGGL(k_join_heads, dim3((T + JOIN_THREADS - 1) / JOIN_THREADS), dim3(JOIN_THREADS), 0, c->stream, c->law.meta, T, j.head);
-        scan64_enqueue(c, j.head, j.incl, 0, T, 1, j.tot);
-        unsigned long long n_heads = 0;
-        HIPCK(hipMemcpyAsync(&n_heads, j.incl + (T - 1), sizeof(n_heads), hipMemcpyDeviceToHost, c->stream));
-        HIPCK(hipStreamSynchronize(c->stream));
-        if (n_heads > (unsigned long long)T) return fail("%s: %llu contigs over %d positions (inconsistent tables)", who, n_heads, T);
-        K = (long long)n_heads;
-    }
+    if (join_enqueue_records(c, who, T, j.head, j.incl, j.tot, j.rec, j.ends, &K)) return -1;
     const int Ki = (int)K, Ui = 2 * Ki; /* K <= T <= M: the ends fit an int */
-    DALLOC(j.ends, (size_t)K);
-    if (K > 0)
-        hipLaunchKernelGGL(k_join_ends, dim3((T + JOIN_THREADS - 1) / JOIN_THREADS), dim3(JOIN_THREADS), 0, c->stream, c->law.meta, j.incl, T, Ki, c->map.order, M, c->sub_tab,
-                           c->st.LB, c->N, j.ends);
-    hipLaunchKernelGGL(k_join_records, dim3((M + JOIN_THREADS - 1) / JOIN_THREADS), dim3(JOIN_THREADS), 0, c->stream, c->map.pix, M, T, c->law.meta, j.incl, Ki, j.rec);
     timer.end(JOIN_P_ENDS);
     j.n_placed = T;
     j.n_contigs = K;

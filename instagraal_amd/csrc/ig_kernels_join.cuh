@@ -6,7 +6,8 @@
  *
  * The ends: k_join_heads flags the first position of every linear placed contig, the 64-bit scan of the junction profile numbers
  * them, k_join_ends writes the table per contig (first position, positions, length in kb) and k_join_records one 16-byte record
- * per sub-fragment: (depth from the head, depth from the tail, run index or JOIN_UNPLACED / JOIN_RING, 0).
+ * per sub-fragment: (depth from the head, depth from the tail, run index or JOIN_UNPLACED / JOIN_RING, the position or 0: the
+ * placement support, ig_kernels_place.cuh, reads the last).
  * The links: k_join_emit is the counting sort of the contacts in genome coordinates (k_lift_pass) with up to four emissions per
  * contact, entry = (row: the lower end, word: the upper end << 32 | count); the rows are sorted and the equal columns summed by
  * the kernels of ig_kernels_lift.cuh on this feature's own buffers.  Integer sums: the result does not depend on the launch
@@ -64,7 +65,7 @@ __global__ void __launch_bounds__(JOIN_THREADS) k_join_ends(const int2* __restri
     ends[k] = JoinEnd{r, min(m.y, T - r), (float)bp / 1000.0f, 0};
 }
 
-/* one record per sub-fragment, one gather per contact endpoint */
+/* one record per sub-fragment, one gather per contact endpoint (.w: the position of a placed sub-fragment, what the placement support reads) */
 __global__ void __launch_bounds__(JOIN_THREADS) k_join_records(const int* __restrict__ pix, int M, int T, const int2* __restrict__ meta,
                                                                const unsigned long long* __restrict__ incl, int K, int4* __restrict__ rec)
 {
@@ -77,6 +78,7 @@ __global__ void __launch_bounds__(JOIN_THREADS) k_join_records(const int* __rest
         const long long k = (long long)incl[p] - 1;
         if (m.y <= 0 || k < 0 || k >= K) out.z = JOIN_RING;
         else out = make_int4(p - m.x, m.x + m.y - 1 - p, (int)k, 0);
+        out.w = p;
     }
     rec[s] = out;
 }

@@ -18,14 +18,16 @@ SRC = os.path.join(HERE, "csrc", "ig_hip.hip")
 SRC_HOST = os.path.join(HERE, "csrc", "ig_draw.cpp")  # host-only part: the candidate draw
 DEPS = [SRC, SRC_HOST] + [os.path.join(HERE, "csrc", f) for f in ("ig_ops.cuh", "ig_common.cuh", "ig_model.cuh", "ig_kernels_setup.cuh",
                                                           "ig_kernels_score.cuh", "ig_kernels_screen.cuh", "ig_kernels_commit.cuh",
-                                                          "ig_kernels_nuis.cuh", "ig_kernels_map.cuh", "ig_kernels_law.cuh", "ig_kernels_junc.cuh", "ig_kernels_lift.cuh", "ig_kernels_join.cuh", "ig_kernels_emap.cuh", "ig_host_core.inc", "ig_host_upload.inc",
-                                                          "ig_host_map.inc", "ig_host_law.inc", "ig_host_junc.inc", "ig_host_lift.inc", "ig_host_join.inc", "ig_host_emap.inc",
+                                                          "ig_kernels_nuis.cuh", "ig_kernels_map.cuh", "ig_kernels_law.cuh", "ig_kernels_junc.cuh", "ig_kernels_lift.cuh", "ig_kernels_join.cuh", "ig_kernels_emap.cuh", "ig_kernels_place.cuh", "ig_host_core.inc", "ig_host_upload.inc",
+                                                          "ig_host_map.inc", "ig_host_law.inc", "ig_host_junc.inc", "ig_host_lift.inc", "ig_host_join.inc", "ig_host_emap.inc", "ig_host_place.inc",
                                                           "ig_host_batch.inc", "ig_host_nuis.inc", "ig_host_debug.inc")] + \
        [os.path.join(ROOT, "include", f) for f in ("ig_detmath.h", "ig_detmath_tables.h", "instagraal_hip.h")]
 
 N_TMP_STRUCT = 24
 ASSEMBLY_CONTACTS_PASSES = ("count", "scan", "scatter", "sort_short", "sort_lds", "sort_long", "reduce")  # ig_debug_assembly_contacts_time
 JOIN_SUPPORT_PASSES = ("ends", "count", "scan", "scatter", "sort_short", "sort_lds", "sort_long", "reduce", "model")  # ig_debug_join_support_time
+PLACEMENT_SUPPORT_PASSES = ("records", "count", "rows", "scatter", "sort_short", "sort_lds", "sort_long", "reduce", "prefix", "scan")  # ig_debug_placement_support_time
+PLACEMENT_SUPPORT_FORMS = ("default", "thread", "wave")  # ig_debug_placement_support_form
 MAX_CANDIDATES = 16
 
 FRAG_FIELDS = ("pos", "sub_pos", "id_c", "start_bp", "len_bp", "sub_len", "circ", "id", "prev", "next", "l_cont",
@@ -858,6 +860,46 @@ class Context:
         ms = np.zeros((int(n), len(JOIN_SUPPORT_PASSES)), np.float32)
         ck = C.c_int64()
         _ck(lib().ig_debug_join_support_time(self._h, C.c_int32(int(window)), C.c_int32(int(n)), _p(ms), C.byref(ck)))
+        return ms, int(ck.value)
+
+    # ---- placement support: where the contacts say each bin belongs (the rule: placement_support.py)
+    def placement_support(self, window, min_hosts=None):
+        """every placed bin of a linear contig against every other site of the genome inside ``window`` positions (``min_hosts``:
+        the fewest positions a site's window must hold, default the window) -> dict: window, min_hosts, the per-bin arrays of
+        ``placement_support.ARRAYS`` (int32 / int64 [N]) and the int64 scalars of ``placement_support.SCALARS``.  Nothing stays on
+        the device."""
+        from .placement_support import INT_ARRAYS, LONG_ARRAYS, SCALARS
+
+        window = int(window)
+        min_hosts = window if min_hosts is None else int(min_hosts)
+        out = dict(window=window, min_hosts=min_hosts)
+        out.update((k, np.zeros(max(self.N, 1), np.int32)) for k in INT_ARRAYS)
+        out.update((k, np.zeros(max(self.N, 1), np.int64)) for k in LONG_ARRAYS)
+        sc = np.zeros(7, np.int64)
+        _ck(lib().ig_placement_support(self._h, C.c_int32(window), C.c_int32(min_hosts), *[_p(out[k]) for k in INT_ARRAYS + LONG_ARRAYS], _p(sc)))
+        for k in INT_ARRAYS + LONG_ARRAYS:
+            out[k] = out[k][:self.N]
+        out.update((k, int(v)) for k, v in zip(SCALARS, sc))
+        return out
+
+    def debug_placement_support_form(self, form="default"):
+        """the scan of the placement support: ``"thread"`` (a thread per row, the yardstick), ``"wave"`` (a wave per row) or
+        ``"default"`` (the form the library ships: by the row's length)"""
+        _ck(lib().ig_debug_placement_support_form(self._h, C.c_int32(PLACEMENT_SUPPORT_FORMS.index(form))))
+
+    def debug_placement_support_forms(self):
+        """the last placement support call's work lists, as ``debug_assembly_contacts_forms``"""
+        o = np.zeros(8, np.int64)
+        _ck(lib().ig_debug_placement_support_forms(self._h, _p(o)))
+        return dict(short=(int(o[0]), int(o[1])), lds=(int(o[2]), int(o[3])), long=(int(o[4]), int(o[5])), runs=int(o[6]), longest=int(o[7]))
+
+    def debug_placement_support_time(self, window, min_hosts=None, n=1):
+        """the call n times with hipEvents around each pass -> (ms [n, 10]: ``PLACEMENT_SUPPORT_PASSES``, checksum of the arrays of
+        the last call)"""
+        ms = np.zeros((int(n), len(PLACEMENT_SUPPORT_PASSES)), np.float32)
+        ck = C.c_int64()
+        _ck(lib().ig_debug_placement_support_time(self._h, C.c_int32(int(window)), C.c_int32(int(window) if min_hosts is None else int(min_hosts)), C.c_int32(int(n)),
+                                                  _p(ms), C.byref(ck)))
         return ms, int(ck.value)
 
     # ---- bookkeeping

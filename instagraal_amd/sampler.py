@@ -1034,6 +1034,41 @@ class sampler:  # noqa: N801 - the reference's class name
         res = self.join_support(window, window_kb) if result is None else result
         return js.best_joins(res, n, min_pairs)
 
+    # ------------------------------------------------------ placement support
+    def placement_support(self, window=None, window_kb=None, min_hosts=None):
+        """Where the contacts say each bin belongs (``ig_placement_support``; the rule: ``placement_support.py``): every placed bin
+        of a linear contig with the density of its contacts inside a window around where it sits (home) and around the densest
+        other site of the genome (best) and the runner-up (second), the bin itself taken out of the order.  ``window``: in
+        positions (default 64), or ``window_kb``; ``min_hosts``: the fewest positions a site's window must hold (default: the
+        window).  -> dict: the per-bin arrays of ``placement_support.ARRAYS``, the scalars of ``placement_support.SCALARS``,
+        ``home_density``, ``best_density`` (obs / (n_positions * hosts)), ``ratio`` = best / home (inf: nothing at home; nan:
+        nothing anywhere), ``second_ratio`` (the runner-up's density over the best's), the sites for people -- ``scaffold``,
+        ``best_scaffold``, ``second_scaffold`` (canonical ids: ``assembly_contacts.scaffold_names`` names them) and
+        ``best_before`` / ``best_after`` / ``second_before`` / ``second_after``, the bins in front of and behind the site (-1:
+        none) -- and ``order``.  No reference counterpart."""
+        from . import placement_support as ps
+
+        if window is not None and window_kb is not None:
+            raise ValueError("placement_support: window or window_kb, not both")
+        if window_kb is not None:
+            window = ps.window_from_kb(window_kb, self.mean_kb())
+        w = ps.check_window(ps.DEFAULT_WINDOW if window is None else window)
+        res = self.ctx.placement_support(w, ps.check_min_hosts(min_hosts, w))
+        order = self.ctx.contact_map_order().astype(np.int64)
+        parent = self.np_sub_frags_2_frags["x"].astype(np.int64)
+        res["order"] = order
+        res.update(ps.densities(res))
+        res.update(ps.sites_for_people(res, order, parent, self.gpu_vect_frags.copy_from_gpu().id_c))
+        return res
+
+    def misplaced_bins(self, n=20, min_ratio=1.0, result=None, window=None, window_kb=None, min_hosts=None):
+        """The ``n`` bins of ``placement_support()`` whose contacts are denser somewhere else than at home by more than
+        ``min_ratio``, best first (``placement_support.misplaced_bins``: inf first, ties by bin id)."""
+        from . import placement_support as ps
+
+        res = self.placement_support(window, window_kb, min_hosts) if result is None else result
+        return ps.misplaced_bins(res, n, min_ratio)
+
     # ----------------------------------------------------------- expected map
     def expected_map(self, max_side=2048):
         """What the model in use (``param_simu``) predicts for the pixels of ``contact_map(max_side)`` (``ig_expected_map``; the

@@ -194,7 +194,7 @@ class instagraal_class:
         self.collect_id_fA_sampled.append(id_frag)
 
     def full_em(self, n_cycles, n_neighbours, bomb, id_start_sample_param, save_matrix=False, save_law=False, save_junctions=False,
-                save_contacts=False, save_joins=False, save_residuals=False):  # IG:196-291
+                save_contacts=False, save_joins=False, save_residuals=False, save_placements=False):  # IG:196-291
         sampler = self.simulation.sampler
         if bomb:
             sampler.bomb_the_genome()
@@ -252,6 +252,10 @@ class instagraal_class:
             from . import join_support as jsup
 
             jsup.write_joins(self._out("joins.txt"), sampler.join_support())
+        if save_placements:  # (once, behind the last cycle, where joins.txt is written: the bins the contacts would rather see elsewhere)
+            from . import placement_support as psup
+
+            psup.write_placements(self._out("placements.txt"), sampler.placement_support())
         self.save_behaviour_to_txt()
 
     def save_behaviour_to_txt(self):  # IG:293-330
@@ -267,7 +271,7 @@ class instagraal_class:
 
 def run_instagraal(hic_folder, reference_fa, output_folder=None, level=4, cycles=100, coverage_std=1, neighborhood=5, device=0,
                    circular=False, bomb=False, pyramid_only=False, save_pickle=False, save_matrix=False, simple=False, save_law=False,
-                   save_junctions=False, save_contacts=False, save_joins=False, save_residuals=False):
+                   save_junctions=False, save_contacts=False, save_joins=False, save_residuals=False, save_placements=False):
     """IG:502-581 (defaults of cli/main.py: level 4, 100 cycles, 5 neighbours, 1 std).  The three trailing switches of the
     reference's signature (IG:512-514) are accepted: ``save_pickle`` dumps the run object to ``graal.pkl`` as the reference
     tries to (IG:589-594: a warning when it cannot be pickled -- device handles here, h5py handles there); ``save_matrix``
@@ -287,7 +291,10 @@ def run_instagraal(hic_folder, reference_fa, output_folder=None, level=4, cycles
     the model's expectation and their ratio (``sampler.join_support``); ``save_residuals`` (an addition too) writes after
     every cycle ``residuals_cycle_<j>.png``, log2(observed / expected) of that genome's contact map against what the model in use
     predicts for every pixel, and ``residuals_cycle_<j>.txt``, the 20 pixels off the diagonal with the largest excess
-    (``sampler.residual_map``, ``sampler.strongest_residuals``)."""
+    (``sampler.residual_map``, ``sampler.strongest_residuals``); ``save_placements`` (an addition too) writes
+    ``placements.txt`` once, behind the last cycle: one line per bin whose contacts are denser around another site of the genome than
+    around where it sits, inside a window of 64 sub-fragments, with that site, the two densities and their ratio
+    (``sampler.placement_support``)."""
     import warnings
 
     if simple and not pyramid_only:
@@ -307,7 +314,7 @@ def run_instagraal(hic_folder, reference_fa, output_folder=None, level=4, cycles
                       "after the sampler copied the fragment arrays)")
         p2.simulation.level.S_o_A_frags["circ"] += 1
     p2.full_em(n_cycles=cycles, n_neighbours=neighborhood, bomb=bomb, id_start_sample_param=4, save_matrix=save_matrix, save_law=save_law,
-               save_junctions=save_junctions, save_contacts=save_contacts, save_joins=save_joins, save_residuals=save_residuals)
+               save_junctions=save_junctions, save_contacts=save_contacts, save_joins=save_joins, save_residuals=save_residuals, save_placements=save_placements)
     if save_pickle:  # IG:589-594
         import pickle
 

@@ -1,0 +1,395 @@
+// AddressSanitizer / UBSan / LeakSanitizer harness for the HOST logic of the placement support (csrc/ig_host_place.inc) with the records
+// it shares with the join support (join_enqueue_records in csrc/ig_host_join.inc) and the sort and reduction it shares with the contacts
+// in genome coordinates (csrc/ig_host_lift.inc): a stand-alone program on the fake HIP runtime (fake_hip_runtime.cpp: device memory is
+// the heap, so every copy, fill and model write is checked against the real allocation sizes).  The models below script what steers the
+// host -- the number of contigs, the entries per row, the work lists of the three sort forms, the heads, the sum of the counts -- with
+// protocol-conforming values; the sums mean nothing here, memory safety, the sizes of the buffers against the work lists, that nothing
+// outlives a call and every error path are the subject.  Built and run by tests/test_placement_support_sanitize.py.
+#include <algorithm>
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <vector>
+
+#define ig_fail_msg harness_copy_of_ig_fail_msg /* ig_common.cuh defines it (for ig_draw.cpp): the library object has the real one */
+#include "../../instagraal_amd/csrc/ig_common.cuh"
+#undef ig_fail_msg
+#include "fake_hip_runtime.h"
+
+#define CHECK(x)                                                                                                           \
+    do {                                                                                                                   \
+        if (!(x)) {                                                                                                        \
+            std::fprintf(stderr, "%s:%d: CHECK failed: %s   [last error: %s]\n", __FILE__, __LINE__, #x, ig_last_error()); \
+            return 1;                                                                                                      \
+        }                                                                                                                  \
+    } while (0)
+
+typedef unsigned long long u64;
+// mirrors of the device structs (ig_kernels_lift.cuh, ig_kernels_join.cuh: device code, not included here)
+struct Item {
+    long long off;
+    int len, pad;
+};
+struct Long {
+    long long off, scratch, len;
+};
+struct End {
+    int start, n;
+    float l_kb;
+    int pad;
+};
+enum { NS_COUNTED = 3, NS_ENTRIES = 4, NI = 11, NL = 6 };
+
+static int g_per_contig = 3;      // positions per modelled contig
+static long long g_entries = 0;   // (contact, row) entries the emit model makes
+static u64 g_counted = 1000;      // what the count pass reports as the sum of the counted contacts' counts
+static bool g_no_heads = false;   // the reduction finds no head: a device error the host must catch
+static bool g_many_heads = false; // more contigs than positions: inconsistent tables
+static long g_scans = 0;          // launches of the scan's model
+
+static size_t g_free_bytes = (size_t)1 << 34; // what the device reports free
+// the fake runtime has no hipMemGetInfo (the library refers to it weakly): this program brings its own, so the check runs here
+extern "C" hipError_t hipMemGetInfo(size_t* free_bytes, size_t* total_bytes)
+{
+    *free_bytes = g_free_bytes;
+    *total_bytes = (size_t)1 << 34;
+    return hipSuccess;
+}
+
+static u64 row_of_entry(long long e, int U) { return (u64)((e * 2654435761ll) % (long long)std::max(U - 2, 1)); }
+
+static void model_heads(void** a, dim3, dim3)
+{
+    const int T = *(int*)a[1];
+    u64* head = *(u64**)a[2];
+    for (int r = 0; r < T; r++) head[r] = g_many_heads ? 2 : r % g_per_contig == 0;
+}
+static void model_scan_apply(void** a, dim3 grid, dim3)
+{
+    const u64* in = *(const u64**)a[0];
+    u64* out = *(u64**)a[1];
+    const long long stride = *(long long*)a[2];
+    const int n = *(int*)a[3];
+    for (unsigned y = 0; y < grid.y; y++) {
+        u64 run = 0;
+        for (int i = 0; i < n; i++) out[y * stride + i] = run += in[y * stride + i];
+    }
+}
+static void model_ends(void** a, dim3, dim3)
+{
+    const int T = *(int*)a[2], K = *(int*)a[3];
+    End* ends = *(End**)a[9];
+    for (int k = 0; k < K; k++) ends[k] = End{k * g_per_contig, std::min(g_per_contig, T - k * g_per_contig), 1.0f, 0};
+}
+static void model_records(void** a, dim3, dim3)
+{
+    const int M = *(int*)a[1];
+    int4* rec = *(int4**)a[6];
+    for (int s = 0; s < M; s++) rec[s] = make_int4(0, 0, s / g_per_contig, s);
+}
+static void model_bins(void** a, dim3, dim3)
+{
+    const int N = *(int*)a[2], M = *(int*)a[3];
+    const int4* rec = *(const int4**)a[4];
+    int4* bins = *(int4**)a[6];
+    for (int f = 0; f < N; f++) bins[f] = make_int4(rec[std::min(2 * f, M - 1)].w, 2, 0, 0);
+}
+static void model_count(void** a, dim3, dim3)
+{
+    const int N = *(int*)a[5];
+    u64 *counter = *(u64**)a[6], *sc = *(u64**)a[9];
+    for (long long e = 0; e < g_entries; e++) counter[row_of_entry(e, N)]++;
+    sc[NS_ENTRIES] += (u64)g_entries;
+    sc[NS_COUNTED] += g_counted;
+}
+static void model_scatter(void** a, dim3, dim3)
+{
+    const int N = *(int*)a[5];
+    u64 *cursor = *(u64**)a[6], *ent = *(u64**)a[7];
+    const u64 n_ent = *(u64*)a[8];
+    for (long long e = 0; e < g_entries; e++) {
+        const u64 row = row_of_entry(e, N), slot = cursor[row]++;
+        if (slot < n_ent) ent[slot] = ((u64)(e % 5) << 32) | 1ull;
+    }
+}
+template <bool FILL>
+static void model_classify(void** a, dim3, dim3)
+{
+    const u64* rowstart = *(const u64**)a[0];
+    const int U = *(int*)a[1], short_max = *(int*)a[2], lds_max = *(int*)a[3];
+    u64 *cls = *(u64**)a[4], *cur = *(u64**)a[5];
+    int* short_rows = *(int**)a[6];
+    Item *lds_items = *(Item**)a[7], *run_items = *(Item**)a[8];
+    Long* long_rows = *(Long**)a[9];
+    for (int r = 0; r < U; r++) {
+        const u64 b = rowstart[r], len = rowstart[r + 1] - b;
+        if (len < 2) continue;
+        if (len <= (u64)short_max) {
+            if (!FILL) cls[0]++, cls[1] += len;
+            else short_rows[cur[0]++] = r;
+        } else if (len <= (u64)lds_max) {
+            if (!FILL) cls[2]++, cls[3] += len;
+            else lds_items[cur[1]++] = Item{(long long)b, (int)len, 0};
+        } else {
+            const u64 run = (u64)lds_max, n_runs = run > 1 ? (len + run - 1) / run : 0;
+            if (!FILL) {
+                cls[4]++, cls[5] += len, cls[6] += n_runs;
+                cls[7] = std::max(cls[7], len);
+            } else {
+                long_rows[cur[2]++] = Long{(long long)b, (long long)cur[3], (long long)len};
+                cur[3] += len;
+                for (u64 q = 0; q < n_runs; q++) run_items[cur[4]++] = Item{(long long)(b + q * run), (int)std::min(run, len - q * run), 0};
+            }
+        }
+    }
+}
+static void model_sort_items(void** a, dim3 grid, dim3) // k_lift_sort_lds: touches every entry of every listed stretch
+{
+    const Item* items = *(const Item**)a[0];
+    u64* ent = *(u64**)a[1];
+    for (unsigned i = 0; i < grid.x; i++) std::sort(ent + items[i].off, ent + items[i].off + items[i].len);
+}
+static void model_sort_wave(void** a, dim3, dim3)
+{
+    const int* rows = *(const int**)a[0];
+    const int n_rows = *(int*)a[1];
+    const u64* rowstart = *(const u64**)a[2];
+    u64* ent = *(u64**)a[3];
+    for (int i = 0; i < n_rows; i++) std::sort(ent + rowstart[rows[i]], ent + rowstart[rows[i] + 1]);
+}
+static void model_merge(void** a, dim3 grid, dim3) // k_lift_merge: reads and writes every entry of every long row on both sides
+{
+    const Long* rows = *(const Long**)a[0];
+    u64 *ent = *(u64**)a[1], *scratch = *(u64**)a[2];
+    const int to_scratch = *(int*)a[4];
+    for (unsigned i = 0; i < grid.x; i++)
+        for (long long e = 0; e < rows[i].len; e++)
+            (to_scratch ? scratch[rows[i].scratch + e] : ent[rows[i].off + e]) = to_scratch ? ent[rows[i].off + e] : scratch[rows[i].scratch + e];
+}
+static void model_head_totals(void** a, dim3 grid, dim3)
+{
+    const long long n = *(long long*)a[2];
+    u64 *totals = *(u64**)a[3], *n_heads = *(u64**)a[4];
+    if (g_no_heads) return;
+    for (unsigned b = 0; b < grid.x; b++) totals[b] = (u64)std::min<long long>(2048, n - 2048ll * b); // every entry is a head
+    *n_heads += (u64)n;
+}
+static void model_reduce(void** a, dim3, dim3)
+{
+    const u64* ent = *(const u64**)a[0];
+    const long long n = *(long long*)a[2];
+    const u64* rowstart = *(const u64**)a[4];
+    const int U = *(int*)a[5];
+    const u64 n_out = *(u64*)a[6];
+    int* out_col = *(int**)a[7];
+    u64 *out_cnt = *(u64**)a[8], *row_heads = *(u64**)a[9];
+    int row = 0;
+    for (long long e = 0; e < n && (u64)e < n_out; e++) {
+        while (row + 1 < U && rowstart[row + 1] <= (u64)e) row++;
+        out_col[e] = (int)(ent[e] >> 32);
+        out_cnt[e] += ent[e] & 0xffffffffull;
+        row_heads[row]++;
+    }
+}
+// k_place_scan: reads the records of every bin, the rows, every summed entry and every prefix sum (one more than the entries), the
+// tables by position; writes every word of the output arrays
+static void model_scan(void** a, dim3, dim3)
+{
+    const int4* bins = *(const int4**)a[0];
+    const int N = *(int*)a[1];
+    const u64* rowptr = *(const u64**)a[2];
+    const int* col = *(const int**)a[3];
+    const u64* pre = *(const u64**)a[4];
+    const long long n_ent = *(long long*)a[5];
+    const int2* meta = *(const int2**)a[6];
+    const u64* incl = *(const u64**)a[7];
+    const int T = *(int*)a[8];
+    int* out_i = *(int**)a[13];
+    long long* out_l = *(long long**)a[14];
+    u64 sum = 0;
+    for (int f = 0; f < N; f++) {
+        sum += (u64)bins[f].x;
+        for (u64 e = rowptr[f]; e < rowptr[f + 1] && e < (u64)n_ent; e++) sum += (u64)col[e] + pre[e + 1] - pre[e];
+    }
+    sum += pre[n_ent] + rowptr[N];
+    for (int r = 0; r < T; r++) sum += (u64)meta[r].y + incl[r];
+    for (int k = 0; k < NI; k++)
+        for (int f = 0; f < N; f++) out_i[(size_t)k * N + f] = k == 0 ? 0 : (int)(sum & 1) + k;
+    for (int k = 0; k < NL; k++)
+        for (int f = 0; f < N; f++) out_l[(size_t)k * N + f] = 100 + k;
+    g_scans++;
+}
+
+struct Out {
+    std::vector<int32_t> vi;
+    std::vector<int64_t> vl;
+    int64_t sc[7];
+    int N;
+    explicit Out(int n) : vi((size_t)NI * n, -7), vl((size_t)NL * n, -7), N(n)
+    {
+        for (int k = 0; k < 7; k++) sc[k] = -7;
+    }
+    int32_t* i(int k) { return vi.data() + (size_t)k * N; }
+    int64_t* l(int k) { return vl.data() + (size_t)k * N; }
+    bool untouched() const
+    {
+        return std::all_of(vi.begin(), vi.end(), [](int32_t v) { return v == -7; }) && std::all_of(vl.begin(), vl.end(), [](int64_t v) { return v == -7; }) && sc[0] == -7;
+    }
+};
+
+static int call(ig_ctx* c, int window, int min_hosts, Out& o, int32_t* first = nullptr, bool null_first = false)
+{
+    (void)first;
+    return ig_placement_support(c, window, min_hosts, null_first ? nullptr : o.i(0), o.i(1), o.i(2), o.i(3), o.i(4), o.i(5), o.i(6), o.i(7), o.i(8), o.i(9), o.i(10), o.l(0),
+                                o.l(1), o.l(2), o.l(3), o.l(4), o.l(5), o.sc);
+}
+
+static int call_and_read(ig_ctx* c, int window, int min_hosts, int N, long long want_entries)
+{
+    Out o(N);
+    const long before = fake_hip::allocations();
+    (void)before;
+    CHECK(call(c, window, min_hosts, o) == 0);
+    CHECK(o.sc[NS_ENTRIES] == want_entries && o.sc[6] == N && o.sc[5] >= 0);
+    for (int f = 0; f < N; f++) CHECK(o.i(0)[f] == 0 && o.l(5)[f] == 105 && o.i(10)[f] >= 10);
+    int64_t forms[8];
+    CHECK(ig_debug_placement_support_forms(c, forms) == 0 && forms[1] + forms[3] + forms[5] <= want_entries);
+    CHECK(want_entries < 40 || forms[0] + forms[2] + forms[4] > 0); // (the lists of the call just made, read behind its buffers' release)
+    return 0;
+}
+
+int main()
+{
+    fake_hip::set_model("k_join_heads", model_heads);
+    fake_hip::set_model("k_junc_scan_apply", model_scan_apply);
+    fake_hip::set_model("k_join_ends", model_ends);
+    fake_hip::set_model("k_join_records", model_records);
+    fake_hip::set_model("k_place_bins", model_bins);
+    fake_hip::set_model("k_place_emitILb0E", model_count);
+    fake_hip::set_model("k_place_emitILb1E", model_scatter);
+    fake_hip::set_model("k_lift_classifyILb0E", model_classify<false>);
+    fake_hip::set_model("k_lift_classifyILb1E", model_classify<true>);
+    fake_hip::set_model("k_lift_sort_lds", model_sort_items);
+    fake_hip::set_model("k_lift_sort_wave", model_sort_wave);
+    fake_hip::set_model("k_lift_merge", model_merge);
+    fake_hip::set_model("k_lift_head_totals", model_head_totals);
+    fake_hip::set_model("k_lift_reduce", model_reduce);
+    fake_hip::set_model("k_place_scan", model_scan);
+
+    // a genome of 40 bins of two sub-fragments each in one contig per bin, a few contacts
+    const int N = 40, M = 80;
+    std::vector<float> sub((size_t)M * 4);
+    std::vector<int32_t> soa((size_t)17 * N, 0), row, col, cnt;
+    for (int f = 0; f < N; f++) {
+        const int v[17] = {0, 0, f, 0, 2000, 2, 0, f, -1, -1, 1, 2, 2000, 1, 0, 1, f};
+        for (int k = 0; k < 17; k++) soa[(size_t)k * N + f] = v[k];
+        for (int w = 0; w < 2; w++) {
+            float* s = &sub[(size_t)4 * (2 * f + w)];
+            s[0] = (float)f, s[1] = 0.5f + (float)w, s[2] = 1.5f - (float)w, s[3] = (float)w;
+        }
+    }
+    for (int a = 0; a < M; a++)
+        for (int b = a + 1; b < M; b += 7) row.push_back(a), col.push_back(b), cnt.push_back(1 + (a + b) % 5);
+    const int64_t Z = (int64_t)row.size();
+
+    ig_ctx* c = nullptr;
+    CHECK(ig_create(0, &c) == 0 && c);
+    {
+        Out o(N);
+        CHECK(call(c, 64, 64, o) != 0 && std::strstr(ig_last_error(), "contacts") && o.untouched()); // nothing uploaded yet
+        CHECK(ig_upload_subfrag_table(c, sub.data(), M) == 0);
+        CHECK(ig_upload_contacts(c, row.data(), col.data(), cnt.data(), Z, M, 0, 1) == 0);
+        CHECK(call(c, 64, 64, o) != 0 && std::strstr(ig_last_error(), "state") && o.untouched());
+        CHECK(ig_upload_state(c, soa.data(), N) == 0);
+        for (int bad : {0, 1025, -3}) CHECK(call(c, bad, 1, o) != 0 && std::strstr(ig_last_error(), "window") && o.untouched());
+        for (int bad : {0, 129, -1}) CHECK(call(c, 64, bad, o) != 0 && std::strstr(ig_last_error(), "min_hosts") && o.untouched());
+        CHECK(call(c, 1024, 2049, o) != 0 && call(c, 1, 3, o) != 0 && o.untouched());
+        CHECK(call(c, 64, 64, o, nullptr, true) != 0 && std::strstr(ig_last_error(), "NULL") && o.untouched());
+        CHECK(ig_debug_placement_support_form(c, 3) != 0 && ig_debug_placement_support_form(c, -1) != 0);
+        CHECK(ig_set_shard(c, 1, 2) == 0); // a sharded handle: refused before anything is allocated
+        const long before = fake_hip::allocations();
+        CHECK(call(c, 64, 64, o) != 0 && std::strstr(ig_last_error(), "all contacts on one handle") && fake_hip::allocations() == before && o.untouched());
+        CHECK(ig_set_shard(c, 0, 1) == 0);
+    }
+
+    // shapes of the entries: none; a few (rows of the short form); many (lds and long rows under lowered limits); every form of the scan
+    for (int per : {3, 1, 80}) { // 27, 80 contigs -- and one
+        g_per_contig = per;
+        for (long long entries : {0ll, 50ll, (long long)(2 * Z)}) { // (the host refuses more than two entries per contact)
+            g_entries = entries;
+            for (int limits = 0; limits < 3; limits++) {
+                CHECK(ig_debug_assembly_contacts_limits(c, limits == 0 ? 0 : limits == 1 ? 2 : 1, limits == 0 ? 0 : limits == 1 ? 4 : 1) == 0);
+                for (int form = 0; form < 3; form++) {
+                    CHECK(ig_debug_placement_support_form(c, form) == 0);
+                    const long scans = g_scans;
+                    if (call_and_read(c, 64, 1 + form, N, g_entries)) return 1;
+                    CHECK(g_scans - scans == (form == 0 ? 2 : 1)); // the default launches both forms, each leaving the other's rows alone
+                }
+            }
+        }
+    }
+    CHECK(ig_debug_assembly_contacts_limits(c, 0, 0) == 0 && ig_debug_placement_support_form(c, 0) == 0);
+    g_per_contig = 3;
+    Out o(N);
+    // the plausibility checks, before anything is sized by what the device reported
+    g_entries = 2 * Z + 2; // more entries than two per contact
+    CHECK(call(c, 64, 64, o) != 0 && std::strstr(ig_last_error(), "device error") && o.untouched());
+    g_entries = 51; // an odd number of entries
+    CHECK(call(c, 64, 64, o) != 0 && std::strstr(ig_last_error(), "device error") && o.untouched());
+    g_entries = 300;
+    g_many_heads = true; // more contigs than positions
+    CHECK(call(c, 64, 64, o) != 0 && std::strstr(ig_last_error(), "inconsistent tables") && o.untouched());
+    g_many_heads = false;
+    g_no_heads = true; // no head among the entries: caught too
+    CHECK(call(c, 64, 64, o) != 0 && std::strstr(ig_last_error(), "distinct") && o.untouched());
+    g_no_heads = false;
+    g_free_bytes = 4096; // the entries do not fit what is free: refused with the bytes named, before anything is allocated by their number
+    {
+        const long before = fake_hip::allocations();
+        CHECK(call(c, 64, 64, o) != 0 && std::strstr(ig_last_error(), "bytes of device memory") && o.untouched());
+        CHECK(fake_hip::allocations() - before < 16); // (the records and the counters only)
+    }
+    g_free_bytes = (size_t)1 << 34;
+    // the overflow guard: 2 w sum(counts) >= 2^62
+    g_counted = 1ull << 51;
+    CHECK(call(c, 1024, 1024, o) != 0 && std::strstr(ig_last_error(), "counts too large for this window") && o.untouched());
+    g_counted = (1ull << 51) - 1000; // (the other classes are 0 here: just below)
+    if (call_and_read(c, 1024, 1024, N, 300)) return 1;
+    g_counted = 1ull << 60;
+    CHECK(call(c, 2, 1, o) != 0 && std::strstr(ig_last_error(), "counts too large for this window"));
+    if (call_and_read(c, 1, 1, N, 300)) return 1;
+    g_counted = 1ull << 62;
+    CHECK(call(c, 1, 1, o) != 0 && std::strstr(ig_last_error(), "counts too large for this window") && o.untouched());
+    g_counted = 1000;
+    // every allocation of a call fails once: an error, nothing written, nothing leaked, and the next call works
+    int failed = 0;
+    for (int n = 0; n < 64; n++) {
+        Out q(N);
+        fake_hip::fail_allocation_in(n);
+        const int rc = call(c, 64, 64, q);
+        fake_hip::fail_allocation_in(-1);
+        if (rc) {
+            CHECK(q.untouched());
+            failed++;
+        }
+        if (call_and_read(c, 64, 64, N, 300)) return 1;
+    }
+    CHECK(failed >= 20);
+    // the time entry point; the join support and the lift through the functions they share with this feature
+    std::vector<float> ms(2 * 10);
+    int64_t ck = 0;
+    CHECK(ig_debug_placement_support_time(c, 64, 64, 2, ms.data(), &ck) == 0 && ig_debug_placement_support_time(c, 64, 64, 0, ms.data(), &ck) != 0);
+    CHECK(ig_debug_placement_support_time(c, 64, 129, 1, ms.data(), &ck) != 0);
+    int64_t nu, ne, sc8[8];
+    CHECK(ig_assembly_contacts_build(c, 1, &nu, &ne, sc8) == 0 || std::strlen(ig_last_error()) > 0);
+    CHECK(ig_join_support_build(c, 64, 0, &nu, &ne, sc8) == 0 || std::strlen(ig_last_error()) > 0);
+    if (call_and_read(c, 64, 64, N, 300)) return 1;
+    // ig_destroy behind a failed call
+    fake_hip::fail_allocation_in(9);
+    CHECK(call(c, 64, 64, o) != 0);
+    fake_hip::fail_allocation_in(-1);
+    ig_destroy(c);
+    std::printf("place harness ok (%ld launches, %ld allocations)\n", fake_hip::launches(), fake_hip::allocations());
+    return 0;
+}
