@@ -1,7 +1,7 @@
 """The contacts in the coordinates of the current genome: every Hi-C contact re-indexed from sub-fragment ids to the scaffolded
 assembly, sorted, at full resolution -- the data behind the contact map, the distance law and the junction profile, in the form
 ``cooler load -f coo bins.bed pixels.tsv`` takes.  This module is the single definition of the rule (pure numpy, no GPU); the device
-passes (``ig_assembly_contacts_build``, csrc/ig_kernels_lift.cuh) reproduce its arrays byte for byte.
+passes (``ig_assembly_contacts_build``, csrc/ig_kernels_lift.cuh, csrc/ig_kernels_rows.cuh) reproduce its arrays byte for byte.
 
 The rule.  The POSITIONS are the contact map's: the sub-fragments of the placed contigs (contigs in ascending canonical id, a
 contig placed only if every one of its bins is active, ``full_order_high`` inside it), 0 .. T - 1; ``position[s]`` is the place of

@@ -329,26 +329,30 @@ struct ChainTest {     /* k_chain_hist_eval -> the decide wave, per set: the his
     double z;
 };
 
-/* the contact map of the current genome (ig_kernels_map.cuh): buffers kept from call to call */
-struct MapBuf {
-    int* base = nullptr;  /* [N] first position of the bin's contig in the order, -1: the contig is not placed */
-    int* pix = nullptr;   /* [M] pixel of every sub-fragment, -1: left out */
-    int* order = nullptr; /* [M] order[r] = sub-fragment at position r */
+/* the genome view (ig_host_genome.inc, ig_kernels_genome.cuh): the tables every report on the current genome starts from, made by
+ * genome_view for the state of the moment, kept from call to call and sized for (N, M); freed by free_genome_buffers */
+struct GenomeBuf {
+    int* base = nullptr;   /* [N] first position of the bin's contig in the order, -1: the contig is not placed */
+    int* pix = nullptr;    /* [M] pixel of every sub-fragment, -1: left out */
+    int* order = nullptr;  /* [M] order[r] = sub-fragment at position r */
     int* err = nullptr;
+    int4* rec = nullptr;   /* [M] (dist, s_tot, contig, position or -1) per sub-fragment */
+    float* ds = nullptr;   /* [M] dist by position of the genome order */
+    int2* meta = nullptr;  /* [M] (first position of the contig, its sub-fragments; negated: a ring) by position */
+    int N = 0, M = 0;
+};
+
+/* the contact map of the current genome (ig_kernels_map.cuh): the image, kept from call to call */
+struct MapBuf {
     unsigned long long* image = nullptr; /* [image_cap] */
     size_t image_cap = 0;
-    int N = 0, M = 0;
 };
 
 /* the distance law of the current genome (ig_kernels_law.cuh): buffers kept from call to call */
 struct LawBuf {
-    int4* rec = nullptr;   /* [M] (dist, s_tot, contig, position or -1) per sub-fragment */
-    float* ds = nullptr;   /* [M] dist by position of the genome order */
-    int2* meta = nullptr;  /* [M] (first position of the contig, its sub-fragments; negated: a ring) by position */
-    float* edges = nullptr;
+    float* edges = nullptr;            /* LAW_MAX_EDGES */
     unsigned long long* out = nullptr; /* LAW_OUT_WORDS (ig_host_law.inc) */
-    int* flag = nullptr;   /* the pairs pass saw dist decrease inside a contig */
-    int M = 0;
+    int* flag = nullptr;               /* the pairs pass saw dist decrease inside a contig */
 };
 
 /* the junction support profile of the current genome (ig_kernels_junc.cuh): buffers kept from call to call */
@@ -361,7 +365,7 @@ struct JuncBuf {
 };
 
 /* the lists and the scratch of one sort of the rows and one reduction of their equal columns (lift_sort_rows, lift_reduce_rows in
- * ig_host_lift.inc), freed behind the build (lift_work_free): the contacts in genome coordinates and the join support have one each */
+ * ig_host_rows.inc), freed behind the build with the rest of a RowBuf's temporaries */
 struct LiftWork {
     int* short_rows = nullptr;
     struct LiftItem *lds_items = nullptr, *run_items = nullptr;
@@ -371,25 +375,37 @@ struct LiftWork {
     unsigned long long* rtot = nullptr;    /* the reduction: heads per chunk of entries */
 };
 
-/* the contacts in the coordinates of the current genome (ig_kernels_lift.cuh): work buffers kept from call to call, the lists of a
- * build (freed behind it), and the built result: a snapshot that stays on the device until it is released */
+/* the row builder (rows_build in ig_host_rows.inc, ig_kernels_rows.cuh): what one counting sort of a feature's entries into U rows,
+ * the sort of the rows and the reduction of their equal columns need, and the rows they leave.  Every feature that builds rows has
+ * one; which of rows_free_temp (the result stays) and rows_free (nothing stays) it calls, and when, is the feature's lifetime rule */
+struct RowBuf {
+    /* kept until rows_free: grow-only (rows_reserve), cap rows */
+    unsigned long long* count = nullptr;  /* [cap + 2] entries per row; behind the reduction: heads per row */
+    unsigned long long* cursor = nullptr; /* [cap + 2] the scatter's cursors */
+    unsigned long long* tot = nullptr;    /* the scans' chunk totals over cap + 2 words */
+    unsigned long long* sc = nullptr;     /* ROWS_SC_WORDS: k_lift_classify's sizes and cursors, the heads of the reduction */
+    long long cap = -1;
+    /* one build's temporaries (rows_free_temp) */
+    unsigned long long* rowstart = nullptr; /* [U + 1] first entry of every row behind the scatter */
+    LiftWork work;
+    /* the result */
+    unsigned long long* rowptr = nullptr;  /* [U + 1] */
+    unsigned long long* ent = nullptr;     /* not reduced: [n_out] column << 32 | count, sorted.  Reduced: a temporary -- rows_free_temp
+                                            * frees it where out_col is set, which is how it tells the two apart */
+    int* out_col = nullptr;                /* reduced: [n_out] */
+    unsigned long long* out_cnt = nullptr; /* reduced: [n_out] */
+};
+
+/* the contacts in the coordinates of the current genome (ig_kernels_lift.cuh): work buffers kept from call to call, and the built
+ * result (rows.rowptr and rows.ent or rows.out_col, rows.out_cnt): a snapshot that stays on the device until it is released */
 struct LiftBuf {
     int* key = nullptr;                  /* [M] unit of every sub-fragment, -1: not placed */
     unsigned long long* head = nullptr;  /* [M + 1] level 1: 1 where the parent bin changes along the order */
     unsigned long long* incl = nullptr;  /* [M + 1] ... and their running sum */
-    unsigned long long* count = nullptr; /* [M + 1] kept contacts per row; level 1, later: heads per row */
-    unsigned long long* cursor = nullptr; /* [M + 1] the scatter's cursors */
-    unsigned long long* tot = nullptr;   /* the scans' chunk totals over M + 2 words */
-    unsigned long long* sc = nullptr;    /* LIFT_SC_WORDS (ig_host_lift.inc) */
+    unsigned long long* htot = nullptr;  /* that scan's chunk totals */
+    unsigned long long* sc = nullptr;    /* LIFT_NS scalars of the passes over the contacts */
     int M = 0;
-    /* one build's */
-    unsigned long long* rowstart = nullptr; /* [U + 1] first entry of every row behind the scatter */
-    LiftWork work;
-    /* the snapshot */
-    unsigned long long* rowptr = nullptr; /* [n_units + 1] */
-    unsigned long long* ent = nullptr;    /* level 0: [n_entries] column << 32 | count */
-    int* out_col = nullptr;               /* level 1: [n_entries] */
-    unsigned long long* out_cnt = nullptr;
+    RowBuf rows;                         /* reserved for M rows with the buffers above */
     bool valid = false;
     int level = 0;
     long long n_placed = 0, n_units = 0, n_entries = 0;
@@ -404,19 +420,12 @@ struct JoinBuf {
     /* one build's */
     unsigned long long* head = nullptr;   /* [T + 1] 1 at the first position of a linear placed contig */
     unsigned long long* incl = nullptr;   /* [T + 1] ... and their running sum */
+    unsigned long long* htot = nullptr;   /* that scan's chunk totals */
     int4* rec = nullptr;                  /* [M] (depth from the head, depth from the tail, run index, 0) per sub-fragment */
-    unsigned long long* count = nullptr;  /* [2 K + 2] emissions per row; later: links per row */
-    unsigned long long* cursor = nullptr; /* [2 K + 2] the scatter's cursors */
-    unsigned long long* tot = nullptr;    /* the scans' chunk totals */
     unsigned long long* sc = nullptr;     /* JOIN_SC_WORDS (ig_host_join.inc) */
-    unsigned long long* rowstart = nullptr; /* [2 K + 1] first entry of every row behind the scatter */
-    unsigned long long* ent = nullptr;    /* [entries] upper end << 32 | count */
-    LiftWork work;
-    /* the snapshot */
+    /* the snapshot: rows.rowptr [2 K + 1], rows.out_col and rows.out_cnt (observed) [n_links], and */
+    RowBuf rows;
     struct JoinEnd* ends = nullptr;       /* [K] first position, positions, length in kb per contig */
-    unsigned long long* rowptr = nullptr; /* [2 K + 1] */
-    int* out_col = nullptr;               /* [n_links] */
-    unsigned long long* out_cnt = nullptr; /* [n_links] observed */
     unsigned long long* pairs = nullptr;  /* [n_links] (a build with the model) */
     unsigned long long* expq = nullptr;   /* [n_links] */
     bool valid = false, model = false;
@@ -431,20 +440,13 @@ struct JoinBuf {
 struct PlaceBuf {
     unsigned long long* head = nullptr;   /* [T + 1] the join support's heads ... */
     unsigned long long* incl = nullptr;   /* [T + 1] ... their running sum */
+    unsigned long long* htot = nullptr;   /* that scan's chunk totals */
     int4* rec = nullptr;                  /* [M] ... and records: (depth, depth, run index, position) per sub-fragment */
     struct JoinEnd* ends = nullptr;       /* [K] */
-    unsigned long long* tot = nullptr;    /* the scans' chunk totals */
     int4* bins = nullptr;                 /* [N] (first position, positions, run index, 0) per bin */
-    unsigned long long* count = nullptr;  /* [N + 2] emissions per row; later: summed entries per row */
-    unsigned long long* cursor = nullptr; /* [N + 2] the scatter's cursors */
-    unsigned long long* sc = nullptr;     /* PLACE_SC_WORDS (ig_host_place.inc) */
-    unsigned long long* rowstart = nullptr; /* [N + 1] first entry of every row behind the scatter */
-    unsigned long long* ent = nullptr;    /* [entries] position << 32 | count */
-    LiftWork work;
-    unsigned long long* rowptr = nullptr; /* [N + 1] the rows of the summed entries */
-    int* out_col = nullptr;               /* [n_summed] positions */
-    unsigned long long* out_cnt = nullptr; /* [n_summed] counts */
-    unsigned long long* pre = nullptr;    /* [n_summed + 1] their exclusive prefix sums */
+    unsigned long long* sc = nullptr;     /* PLACE_NS scalars of the passes over the contacts */
+    RowBuf rows;                          /* N rows of summed entries: rowptr, out_col (positions), out_cnt (counts) */
+    unsigned long long* pre = nullptr;    /* [n_summed + 1] the exclusive prefix sums of the counts */
     unsigned long long* ptot = nullptr;   /* that scan's chunk totals */
     int* out_i = nullptr;                 /* [PLACE_NI][N] */
     long long* out_l = nullptr;           /* [PLACE_NL][N] */
@@ -567,6 +569,7 @@ struct ig_ctx {
     Glob* glob;
     long long* scratch8; /* 8 x int64 reduction scratch of the from-scratch passes */
     MoveBuf mb;
+    GenomeBuf genome;
     MapBuf map;
     LawBuf law;
     JuncBuf junc;

@@ -4,8 +4,9 @@
  *   /root/reference/src/instagraal/kernels/kernel_sparse_adapt.cu  ("KA", 38 CUDA kernels)
  *   /root/reference/src/instagraal/cuda_lib_gl_single.py           ("CL", pycuda host code)
  *
- * One translation unit; the device code lives in the parts included below, this file is the host side
- * (handles, uploads, the launch sequences, the extern "C" entry points).
+ * One translation unit; the device code lives in the ig_kernels_*.cuh parts included below, the host side (handles, uploads, the
+ * launch sequences, the extern "C" entry points) in the ig_host_*.inc parts: core, upload; genome and rows, the layers the reports
+ * on the current genome share; map, law, junc, lift, join, emap, place, one per report; batch, nuis, debug.
  *
  * A batch of W moves (CL:1401-1465 each) is one launch sequence on one stream, no host round trip inside:
  *   k_gather        O(N)            local fragment lists of the touched contigs, uniq-mutation lists, flags
@@ -24,14 +25,14 @@
  * plus the one-move kernels k_scores / k_delta / k_apply / k_post / k_commit (single moves, windowed winners), and the
  * from-scratch pass over all contacts: k_pack_tab_sig / k_nuis_prepare, k_tile_trans, k_full_nz_tiled; the
  * nuisance step's screened pass: k_hist_build / k_hist_walk / k_hist_eval (tier 0), k_full_diff_tiled (tier 1);
- * the contact map of the current genome: k_map_pixels, k_contact_map, k_map_mirror; its distance law:
- * k_law_records, k_law_sorted, k_law_observed, k_law_pairs; its junction support profile: k_junc_observed,
- * k_junc_count, k_junc_model, k_junc_scan_totals / _tops / _apply; the contacts in its coordinates: k_lift_heads,
- * k_lift_keys, k_lift_pass, k_lift_classify, k_lift_sort_wave / _lds, k_lift_merge, k_lift_row_bits, k_lift_head_totals, k_lift_reduce
- * (DESIGN.md 4.13); the join support of its scaffold ends: k_join_heads, k_join_ends, k_join_records, k_join_emit, k_join_model, with
- * the sorts and the reduction of 4.13; its expected contact map: k_emap_count, k_emap_rows, k_emap_list,
- * k_emap_tiles, with the scan of 4.12 and the mirror of 4.10; the placement support of its bins: k_place_bins,
- * k_place_emit, k_place_scan, with the records of 4.14, the sorts and the reduction of 4.13 and the scan of 4.12.
+ * the reports on the current genome and the two layers they share -- the genome view: k_map_pixels, k_law_records,
+ * k_law_sorted; the row builder: k_scan64_totals / _tops / _apply, k_lift_classify, k_lift_sort_wave / _lds, k_lift_merge,
+ * k_lift_row_bits, k_lift_head_totals, k_lift_reduce --; the contact map: k_contact_map, k_map_mirror; the distance
+ * law: k_law_observed, k_law_pairs (4.11); the junction support profile: k_junc_observed, k_junc_count, k_junc_model (4.12); the
+ * contacts in genome coordinates: k_lift_heads, k_lift_keys, k_lift_pass (4.13); the join support of the scaffold ends: k_join_heads,
+ * k_join_ends, k_join_records, k_join_emit, k_join_model (4.14); the expected contact map: k_emap_count, k_emap_rows, k_emap_list,
+ * k_emap_tiles, with the mirror of 4.10 (4.15); the placement support of the bins: k_place_bins, k_place_emit, k_place_scan, with the
+ * records of 4.14 (4.16).
  *
  * Environment knobs (tests, fault injection and tuning only; the table in INTEGRATION.md section 4 is the reference): IG_BATCH_W, IG_WINDOW
  * (widths), IG_POOL_ENTRIES, IG_WIDE_LISTS, IG_NO_HOST_FLAG, IG_POISON_ALLOC / IG_POISON_ONLY (force the rare paths), IG_SCREEN,
@@ -51,6 +52,8 @@
 #include "ig_kernels_screen.cuh"
 #include "ig_kernels_commit.cuh"
 #include "ig_kernels_nuis.cuh"
+#include "ig_kernels_genome.cuh"
+#include "ig_kernels_rows.cuh"
 #include "ig_kernels_map.cuh"
 #include "ig_kernels_law.cuh"
 #include "ig_kernels_junc.cuh"
@@ -59,9 +62,11 @@
 #include "ig_kernels_emap.cuh"
 #include "ig_kernels_place.cuh"
 
-/* ================================================================== host side (one translation unit, twelve parts) */
+/* ================================================================== host side (one translation unit, fourteen parts) */
 #include "ig_host_core.inc"
 #include "ig_host_upload.inc"
+#include "ig_host_genome.inc"
+#include "ig_host_rows.inc"
 #include "ig_host_map.inc"
 #include "ig_host_law.inc"
 #include "ig_host_junc.inc"

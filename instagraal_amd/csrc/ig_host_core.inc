@@ -1,6 +1,7 @@
 /* ig_host_core.inc -- part of ig_hip.hip (one translation unit; included there in order): the handle: the helper thread of the nuisance runs, allocation and timers, ig_create / ig_destroy, the from-scratch pass's launches, window buffers, slice pool and batch buffers. */
 
 /* ================================================================== host side */
+static void free_genome_buffers(ig_ctx* c); /* ig_host_genome.inc */
 static void free_map_buffers(ig_ctx* c);   /* ig_host_map.inc */
 static void free_law_buffers(ig_ctx* c);   /* ig_host_law.inc */
 static void free_junc_buffers(ig_ctx* c);  /* ig_host_junc.inc */
@@ -454,6 +455,7 @@ extern "C" void ig_destroy(ig_ctx* c)
     if (c->host_step) hipHostFree(c->host_step);
     drain_timers(c);
     free_move_buffers(c);
+    free_genome_buffers(c);
     free_map_buffers(c);
     free_law_buffers(c);
     free_junc_buffers(c);

@@ -26,14 +26,17 @@ static void free_emap_buffers(ig_ctx* c)
     e.form = form; /* (the setting of ig_debug_expected_map_form belongs to the handle and stays) */
 }
 
-/* the guards of the map under this entry point's name, the positions under max_side, ds and meta by position (the law's) */
-static int emap_prepare(ig_ctx* c, const char* who, int max_side, int* T, int* bin, int* side)
+/* the genome view under this entry point's name: the pixels under max_side, ds and meta by position (no contact is read, so no
+ * record is asked for) */
+static int emap_view(ig_ctx* c, const char* who, int max_side, int* T, int* bin, int* side)
 {
     if (max_side < 1) return fail("%s: max_side must be >= 1 (got %d)", who, max_side);
-    if (map_prepare(c, who, max_side, true, T, bin, side)) return -1;
+    GenomeDims d;
+    if (genome_view(c, who, max_side, GENOME_SORTED, &d)) return -1;
     if (!c->have_params) return fail("%s: set parameters first", who);
-    if (law_ensure_buffers(c)) return -1;
-    law_enqueue_sorted(c, *T);
+    *T = d.T;
+    *bin = d.bin;
+    *side = d.side;
     return 0;
 }
 
@@ -54,7 +57,7 @@ static int emap_alloc(ig_ctx* c, int side, bool tiles)
     if (tiles) {
         DALLOC(e.cnt, (size_t)side);
         DALLOC(e.off, (size_t)side + 1);
-        DALLOC(e.tot, (size_t)junc_chunks(side));
+        DALLOC(e.tot, (size_t)scan_chunks(side));
     }
     return 0;
 }
@@ -70,9 +73,9 @@ static int emap_enqueue(ig_ctx* c, const char* who, int T, int bin, int side, in
     HIPCK(hipMemsetAsync(e.img, 0, 3 * px * sizeof(unsigned long long), c->stream));
     HIPCK(hipMemsetAsync(e.sc, 0, EMAP_NS * sizeof(unsigned long long), c->stream));
     const int blocks = (T + EMAP_THREADS - 1) / EMAP_THREADS;
-    hipLaunchKernelGGL(k_emap_count, dim3(blocks), dim3(EMAP_THREADS), 0, c->stream, c->law.ds, c->law.meta, T, bin, tiles ? e.cnt : nullptr, e.sc);
+    hipLaunchKernelGGL(k_emap_count, dim3(blocks), dim3(EMAP_THREADS), 0, c->stream, c->genome.ds, c->genome.meta, T, bin, tiles ? e.cnt : nullptr, e.sc);
     if (!tiles) {
-        hipLaunchKernelGGL(k_emap_rows, dim3(blocks), dim3(EMAP_THREADS), 0, c->stream, c->law.ds, c->law.meta, T, bin, side, c->glob, cis_q, cis_pairs, ring_pairs, e.sc);
+        hipLaunchKernelGGL(k_emap_rows, dim3(blocks), dim3(EMAP_THREADS), 0, c->stream, c->genome.ds, c->genome.meta, T, bin, side, c->glob, cis_q, cis_pairs, ring_pairs, e.sc);
     } else {
         HIPCK(hipMemsetAsync(e.off, 0, sizeof(unsigned long long), c->stream));
         scan64_enqueue(c, e.cnt, e.off + 1, 0, side, 1, e.tot);
@@ -94,13 +97,13 @@ static int emap_enqueue(ig_ctx* c, const char* who, int T, int bin, int side, in
         hipLaunchKernelGGL(k_emap_list, dim3((unsigned)((n_tiles + EMAP_THREADS - 1) / EMAP_THREADS)), dim3(EMAP_THREADS), 0, c->stream, e.off, side, (long long)n_tiles, e.list);
         /* the shortcut leans on ds not decreasing inside a contig: where k_emap_count saw it decrease every tile is walked */
         if (form != EMAP_FORM_TILES_PLAIN && !nonmono)
-            hipLaunchKernelGGL((k_emap_tiles<true>), dim3((unsigned)n_tiles), dim3(EMAP_THREADS), 0, c->stream, e.list, c->law.ds, c->law.meta, T, bin, side, c->glob, cis_q, cis_pairs,
+            hipLaunchKernelGGL((k_emap_tiles<true>), dim3((unsigned)n_tiles), dim3(EMAP_THREADS), 0, c->stream, e.list, c->genome.ds, c->genome.meta, T, bin, side, c->glob, cis_q, cis_pairs,
                                ring_pairs, e.sc);
         else
-            hipLaunchKernelGGL((k_emap_tiles<false>), dim3((unsigned)n_tiles), dim3(EMAP_THREADS), 0, c->stream, e.list, c->law.ds, c->law.meta, T, bin, side, c->glob, cis_q, cis_pairs,
+            hipLaunchKernelGGL((k_emap_tiles<false>), dim3((unsigned)n_tiles), dim3(EMAP_THREADS), 0, c->stream, e.list, c->genome.ds, c->genome.meta, T, bin, side, c->glob, cis_q, cis_pairs,
                                ring_pairs, e.sc);
     }
-    const int nt = (side + MAP_TILE - 1) / MAP_TILE;
+    const int nt = (side + MAP_TILE - 1) / MAP_TILE; /* (the contact map's mirror, ig_kernels_map.cuh) */
     for (int k = 0; k < 3; k++) hipLaunchKernelGGL(k_map_mirror, dim3(nt, nt), dim3(MAP_TILE, 8), 0, c->stream, e.img + (size_t)k * px, side);
     return 0;
 }
@@ -132,7 +135,7 @@ static int emap_run(ig_ctx* c, int32_t max_side, int64_t* cis_q, int64_t* cis_pa
 {
     const char* who = "ig_expected_map";
     int T = 0, bin = 1, side = 0;
-    if (emap_prepare(c, who, max_side, &T, &bin, &side)) return -1;
+    if (emap_view(c, who, max_side, &T, &bin, &side)) return -1;
     *side_out = side;
     *bin_out = bin;
     const long long px = (long long)side * (long long)side;
@@ -176,24 +179,10 @@ static int emap_time(ig_ctx* c, int32_t max_side, int32_t form, int32_t n, float
 {
     const char* who = "ig_debug_expected_map_time";
     int T = 0, bin = 1, side = 0;
-    if (emap_prepare(c, who, max_side, &T, &bin, &side)) return -1;
+    if (emap_view(c, who, max_side, &T, &bin, &side)) return -1;
     if (side == 0) return fail("%s: no sub-fragment is placed", who);
     if (emap_alloc(c, side, emap_tiles(form, bin))) return -1;
-    hipEvent_t a, b;
-    HIPCK(hipEventCreate(&a));
-    HIPCK(hipEventCreate(&b));
-    int rc = 0;
-    for (int r = 0; r < n && !rc; r++) {
-        hipError_t e = hipEventRecord(a, c->stream);
-        rc = emap_enqueue(c, who, T, bin, side, form);
-        if (e == hipSuccess) e = hipEventRecord(b, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        if (e == hipSuccess) e = hipEventElapsedTime(&ms_n[r], a, b);
-        if (e != hipSuccess && !rc) rc = fail("%s: %s", who, hipGetErrorString(e));
-    }
-    hipEventDestroy(a);
-    hipEventDestroy(b);
-    if (rc) return rc;
+    if (time_repeats(c, who, n, ms_n, [&] { return emap_enqueue(c, who, T, bin, side, form); })) return -1;
     long long sc[8];
     if (emap_finish(c, who, T, bin, sc)) return -1;
     if (checksum) { /* of the last build: the three images word by word, then the pair counts and the largest value: every form must agree on it */

@@ -1,12 +1,8 @@
 /* ig_host_join.inc -- part of ig_hip.hip (one translation unit; included there in order): join support, which scaffold ends the
  * contacts of the current genome would link (ig_kernels_join.cuh; the rule: instagraal_amd/join_support.py). */
 
-/* JoinBuf.sc, in 64-bit words: the scalars of the passes over the contacts, k_lift_classify's sizes and cursors, the heads of the
- * reduction, the largest |quantised model value| */
-#define JOIN_SC_CLS JOIN_NS
-#define JOIN_SC_CUR (JOIN_SC_CLS + LIFT_C_WORDS)
-#define JOIN_SC_HEADS (JOIN_SC_CUR + 5)
-#define JOIN_SC_MAXQ (JOIN_SC_HEADS + 1)
+/* JoinBuf.sc, in 64-bit words: the scalars of the passes over the contacts, the largest |quantised model value| */
+#define JOIN_SC_MAXQ JOIN_NS
 #define JOIN_SC_WORDS (JOIN_SC_MAXQ + 1)
 /* the passes ig_debug_join_support_time reports, in this order */
 #define JOIN_P_ENDS 0
@@ -26,11 +22,6 @@
  * measured yet */
 #define JOIN_SHIP_COMBINE 0
 
-/* The free device memory is asked for through a WEAK reference: a HIP runtime without hipMemGetInfo (the fake one of the host-only
- * sanitizer harness, tests/sanitize/fake_hip_runtime.cpp) still links, and the check is skipped there.  Against libamdhip64 the
- * symbol is always bound. */
-extern "C" hipError_t hipMemGetInfo(size_t* free_bytes, size_t* total_bytes) __attribute__((weak));
-
 /* the one free function of the feature: what a build needed, and (keep_snapshot = false) the built result.  The setting of
  * ig_debug_join_support_combine belongs to the handle and stays. */
 static void free_join_buffers(ig_ctx* c, bool keep_snapshot)
@@ -38,21 +29,16 @@ static void free_join_buffers(ig_ctx* c, bool keep_snapshot)
     JoinBuf& j = c->join;
     hipFree(j.head);
     hipFree(j.incl);
+    hipFree(j.htot);
     hipFree(j.rec);
-    hipFree(j.count);
-    hipFree(j.cursor);
-    hipFree(j.tot);
     hipFree(j.sc);
-    hipFree(j.rowstart);
-    hipFree(j.ent);
-    j.head = j.incl = j.count = j.cursor = j.tot = j.sc = j.rowstart = j.ent = nullptr;
+    j.head = j.incl = j.htot = j.sc = nullptr;
     j.rec = nullptr;
-    lift_work_free(j.work);
+    rows_free_temp(j.rows);
+    rows_free_reserve(j.rows);
     if (keep_snapshot) return;
+    rows_free_result(j.rows);
     hipFree(j.ends);
-    hipFree(j.rowptr);
-    hipFree(j.out_col);
-    hipFree(j.out_cnt);
     hipFree(j.pairs);
     hipFree(j.expq);
     const int combine = j.combine;
@@ -60,22 +46,23 @@ static void free_join_buffers(ig_ctx* c, bool keep_snapshot)
     j.combine = combine;
 }
 
-/* The ends and the records (pass 1), shared with the placement support (ig_host_place.inc): the heads of the linear placed contigs,
- * their 64-bit scan, the table per contig and one record per sub-fragment, on the library's stream behind law_records (c->law.meta,
- * c->map.pix, c->map.order of T placed positions).  Allocates head, incl: [T + 1]; tot: the scans' chunk totals over 2 M + 3 words;
- * ends: [K]; rec: [M] -- the caller's buffers, freed by the caller whatever happens.  Waits once, for K. */
-static int join_enqueue_records(ig_ctx* c, const char* who, int T, unsigned long long*& head, unsigned long long*& incl, unsigned long long*& tot, int4*& rec,
+/* The ends and the records, shared with the placement support (ig_host_place.inc): the heads of the linear placed contigs, their
+ * 64-bit scan, the table per contig and one record per sub-fragment, on the library's stream behind the genome view (genome.meta,
+ * genome.pix, genome.order of T placed positions: genome_positions with GENOME_SORTED).  Allocates head, incl: [T + 1]; htot: that
+ * scan's chunk totals; ends: [K]; rec: [M] -- the caller's buffers, freed by the caller whatever happens.  Waits once, for K. */
+static int join_enqueue_records(ig_ctx* c, const char* who, int T, unsigned long long*& head, unsigned long long*& incl, unsigned long long*& htot, int4*& rec,
                                 JoinEnd*& ends, long long* K_out)
 {
+    const GenomeBuf& g = c->genome;
     const int M = c->M;
     long long K = 0;
     DALLOC(rec, (size_t)M);
     DALLOC(head, (size_t)T + 1);
     DALLOC(incl, (size_t)T + 1);
-    DALLOC(tot, (size_t)junc_chunks(2 * M + 3));
+    DALLOC(htot, (size_t)scan_chunks(T + 1));
     if (T > 0) {
-        hipLaunchKernelGGL(k_join_heads, dim3((T + JOIN_THREADS - 1) / JOIN_THREADS), dim3(JOIN_THREADS), 0, c->stream, c->law.meta, T, head);
-        scan64_enqueue(c, head, incl, 0, T, 1, tot);
+        hipLaunchKernelGGL(k_join_heads, dim3((T + JOIN_THREADS - 1) / JOIN_THREADS), dim3(JOIN_THREADS), 0, c->stream, g.meta, T, head);
+        scan64_enqueue(c, head, incl, 0, T, 1, htot);
         unsigned long long n_heads = 0;
         HIPCK(hipMemcpyAsync(&n_heads, incl + (T - 1), sizeof(n_heads), hipMemcpyDeviceToHost, c->stream));
         HIPCK(hipStreamSynchronize(c->stream));
@@ -85,20 +72,21 @@ static int join_enqueue_records(ig_ctx* c, const char* who, int T, unsigned long
     const int Ki = (int)K; /* K <= T <= M */
     DALLOC(ends, (size_t)K);
     if (K > 0)
-        hipLaunchKernelGGL(k_join_ends, dim3((T + JOIN_THREADS - 1) / JOIN_THREADS), dim3(JOIN_THREADS), 0, c->stream, c->law.meta, incl, T, Ki, c->map.order, M, c->sub_tab,
-                           c->st.LB, c->N, ends);
-    hipLaunchKernelGGL(k_join_records, dim3((M + JOIN_THREADS - 1) / JOIN_THREADS), dim3(JOIN_THREADS), 0, c->stream, c->map.pix, M, T, c->law.meta, incl, Ki, rec);
+        hipLaunchKernelGGL(k_join_ends, dim3((T + JOIN_THREADS - 1) / JOIN_THREADS), dim3(JOIN_THREADS), 0, c->stream, g.meta, incl, T, Ki, g.order, M, c->sub_tab, c->st.LB, c->N,
+                           ends);
+    hipLaunchKernelGGL(k_join_records, dim3((M + JOIN_THREADS - 1) / JOIN_THREADS), dim3(JOIN_THREADS), 0, c->stream, g.pix, M, T, g.meta, incl, Ki, rec);
     *K_out = K;
     return 0;
 }
 
-/* The build, up to the snapshot's fields.  The caller frees what it leaves behind and, on an error, the half-built snapshot. */
+/* The build, up to the snapshot's fields: the ends and the records, the rows of the links (rows_build) from k_join_emit, the model
+ * over the links found.  The caller frees what it leaves behind and, on an error, the half-built snapshot. */
 static int join_build_impl(ig_ctx* c, const char* who, int window, bool model, float* ms)
 {
     JoinBuf& j = c->join;
-    if (window < 1 || window > JUNC_MAX_WINDOW) return fail("%s: 1 <= window <= %d positions (got %d)", who, JUNC_MAX_WINDOW, window);
+    if (check_window(who, window)) return -1;
     int T = 0;
-    if (law_records(c, who, true, &T)) return -1; /* (the guards of the map under this entry point's name; max_side = M: pix is the position) */
+    if (genome_positions(c, who, GENOME_SORTED, &T)) return -1;
     if (model && !c->have_params) return fail("%s: set parameters first", who);
     LiftTimer timer(c, ms, JOIN_PASSES);
     DALLOC(j.sc, (size_t)JOIN_SC_WORDS);
@@ -106,94 +94,47 @@ static int join_build_impl(ig_ctx* c, const char* who, int window, bool model, f
     /* the ends */
     long long K = 0;
     timer.begin();
-    if (join_enqueue_records(c, who, T, j.head, j.incl, j.tot, j.rec, j.ends, &K)) return -1;
+    if (join_enqueue_records(c, who, T, j.head, j.incl, j.htot, j.rec, j.ends, &K)) return -1;
     const int Ki = (int)K, Ui = 2 * Ki; /* K <= T <= M: the ends fit an int */
     timer.end(JOIN_P_ENDS);
     j.n_placed = T;
     j.n_contigs = K;
-    /* count */
+    /* the links */
     const bool combine = j.combine < 0 ? JOIN_SHIP_COMBINE != 0 : j.combine != 0;
-    DALLOC(j.count, (size_t)Ui + 2);
-    DALLOC(j.cursor, (size_t)Ui + 2);
-    DALLOC(j.rowstart, (size_t)Ui + 1);
-    timer.begin();
-    HIPCK(hipMemsetAsync(j.count, 0, ((size_t)Ui + 2) * sizeof(unsigned long long), c->stream));
-    if (c->Z > 0) {
-        if (combine)
-            hipLaunchKernelGGL((k_join_emit<false, true>), dim3(lift_blocks(c->Z)), dim3(JOIN_THREADS), 0, c->stream, c->crow, c->cc, c->Z, j.rec, window, Ui, j.count, nullptr,
-                               0ull, j.sc, c->rank, c->world);
+    auto emit = [&](bool scatter, unsigned long long* slots, unsigned long long* ent, unsigned long long n_ent) {
+        const dim3 grid(lift_blocks(c->Z)), block(JOIN_THREADS);
+        if (!scatter && combine)
+            hipLaunchKernelGGL((k_join_emit<false, true>), grid, block, 0, c->stream, c->crow, c->cc, c->Z, j.rec, window, Ui, slots, ent, n_ent, j.sc, c->rank, c->world);
+        else if (!scatter)
+            hipLaunchKernelGGL((k_join_emit<false, false>), grid, block, 0, c->stream, c->crow, c->cc, c->Z, j.rec, window, Ui, slots, ent, n_ent, j.sc, c->rank, c->world);
+        else if (combine)
+            hipLaunchKernelGGL((k_join_emit<true, true>), grid, block, 0, c->stream, c->crow, c->cc, c->Z, j.rec, window, Ui, slots, ent, n_ent, j.sc, c->rank, c->world);
         else
-            hipLaunchKernelGGL((k_join_emit<false, false>), dim3(lift_blocks(c->Z)), dim3(JOIN_THREADS), 0, c->stream, c->crow, c->cc, c->Z, j.rec, window, Ui, j.count,
-                               nullptr, 0ull, j.sc, c->rank, c->world);
-    }
-    timer.end(JOIN_P_COUNT);
-    /* the rows' starts */
-    timer.begin();
-    HIPCK(hipMemsetAsync(j.rowstart, 0, sizeof(unsigned long long), c->stream));
-    if (Ui > 0) scan64_enqueue(c, j.count, j.rowstart + 1, 0, Ui, 1, j.tot);
-    timer.end(JOIN_P_SCAN);
+            hipLaunchKernelGGL((k_join_emit<true, false>), grid, block, 0, c->stream, c->crow, c->cc, c->Z, j.rec, window, Ui, slots, ent, n_ent, j.sc, c->rank, c->world);
+    };
+    auto check = [&](long long E) {
+        return E < 0 || E > 4 * (long long)c->Z || (E > 0 && K < 2) ? fail("%s: %lld entries of %lld contacts (device error)", who, E, (long long)c->Z) : 0;
+    };
+    /* per entry: the word itself, the long rows' scratch and their runs' items (8 bytes each), a bit, and a link of its own (column,
+     * observed, pairs, expected_q: 28 bytes) */
+    const RowsSpec spec = {j.sc, JOIN_NS, JOIN_ENTRIES, 53, " (a smaller window has fewer entries)", true,
+                           {JOIN_P_COUNT, JOIN_P_SCAN, JOIN_P_SCATTER, JOIN_P_SORT_SHORT, JOIN_P_REDUCE}};
     unsigned long long sc[JOIN_NS];
-    HIPCK(hipMemcpyAsync(sc, j.sc, sizeof(sc), hipMemcpyDeviceToHost, c->stream));
-    HIPCK(hipStreamSynchronize(c->stream));
-    const long long E = (long long)sc[JOIN_ENTRIES];
-    if (E < 0 || E > 4 * (long long)c->Z || (E > 0 && K < 2)) return fail("%s: %lld entries of %lld contacts (device error)", who, E, (long long)c->Z);
-    for (int k = 0; k < 8; k++) j.forms[k] = 0;
-    j.n_entries = E;
-    if (E == 0) { /* no link: the rows' starts, all zero, are the result's rows */
-        j.rowptr = j.rowstart;
-        j.rowstart = nullptr;
-        j.n_links = 0;
-        return 0;
-    }
-    /* what the entries need at the most, before anything is allocated by their number: per entry the word itself, the long rows'
-     * scratch and their runs' items (8 bytes each), a bit, and a link of its own (column, observed, pairs, expected_q: 28 bytes);
-     * per row the lists of the three forms */
-    {
-        const unsigned long long need = (unsigned long long)E * 53 + (unsigned long long)(Ui + 1) * (8 + sizeof(LiftItem) + sizeof(LiftLong)) + (1ull << 20);
-        size_t free_b = ~(size_t)0, total_b = 0;
-        if (&hipMemGetInfo != nullptr) HIPCK(hipMemGetInfo(&free_b, &total_b));
-        if (need > (unsigned long long)free_b)
-            return fail("%s: %lld entries need %llu bytes of device memory, %zu are free (a smaller window has fewer entries)", who, E, need, free_b);
-    }
-    DALLOC(j.ent, (size_t)E);
-    /* scatter */
-    timer.begin();
-    HIPCK(hipMemcpyAsync(j.cursor, j.rowstart, (size_t)Ui * sizeof(unsigned long long), hipMemcpyDeviceToDevice, c->stream));
-    if (combine)
-        hipLaunchKernelGGL((k_join_emit<true, true>), dim3(lift_blocks(c->Z)), dim3(JOIN_THREADS), 0, c->stream, c->crow, c->cc, c->Z, j.rec, window, Ui, j.cursor, j.ent,
-                           (unsigned long long)E, j.sc, c->rank, c->world);
-    else
-        hipLaunchKernelGGL((k_join_emit<true, false>), dim3(lift_blocks(c->Z)), dim3(JOIN_THREADS), 0, c->stream, c->crow, c->cc, c->Z, j.rec, window, Ui, j.cursor, j.ent,
-                           (unsigned long long)E, j.sc, c->rank, c->world);
-    timer.end(JOIN_P_SCATTER);
-    /* sort and reduce: the lift's, under the limits of ig_debug_assembly_contacts_limits */
-    if (lift_sort_rows(c, who, timer, JOIN_P_SORT_SHORT, j.rowstart, Ui, j.ent, E, c->lift.short_max, c->lift.lds_max, j.sc + JOIN_SC_CLS, j.sc + JOIN_SC_CUR, j.forms,
-                       j.work))
-        return -1;
-    long long n_links = 0;
-    if (lift_reduce_rows(c, who, timer, JOIN_P_REDUCE, j.rowstart, Ui, j.ent, E, j.sc + JOIN_SC_HEADS, j.count, j.tot, j.work, &j.out_col, &j.out_cnt, &j.rowptr, &n_links))
-        return -1;
-    j.n_links = n_links;
+    if (rows_build(c, who, j.rows, Ui, spec, sc, check, emit, timer, j.forms, &j.n_entries, &j.n_links)) return -1;
+    const long long n_links = j.n_links;
     /* the model over the links found */
-    if (model) {
+    if (model && n_links > 0) {
         DALLOC(j.pairs, (size_t)n_links);
         DALLOC(j.expq, (size_t)n_links);
         timer.begin();
         HIPCK(hipMemsetAsync(j.pairs, 0, (size_t)n_links * sizeof(unsigned long long), c->stream));
         HIPCK(hipMemsetAsync(j.expq, 0, (size_t)n_links * sizeof(unsigned long long), c->stream));
-        hipLaunchKernelGGL((k_join_model<1>), dim3((unsigned)((n_links + JOIN_THREADS - 1) / JOIN_THREADS)), dim3(JOIN_THREADS), 0, c->stream, j.rowptr, Ui, j.out_col, n_links,
-                           j.ends, Ki, c->law.ds, T, window, c->glob, j.pairs, j.expq, j.sc + JOIN_SC_MAXQ);
-        hipLaunchKernelGGL((k_join_model<64>), dim3((unsigned)((n_links * 64 + JOIN_THREADS - 1) / JOIN_THREADS)), dim3(JOIN_THREADS), 0, c->stream, j.rowptr, Ui, j.out_col,
-                           n_links, j.ends, Ki, c->law.ds, T, window, c->glob, j.pairs, j.expq, j.sc + JOIN_SC_MAXQ);
+        hipLaunchKernelGGL((k_join_model<1>), dim3((unsigned)((n_links + JOIN_THREADS - 1) / JOIN_THREADS)), dim3(JOIN_THREADS), 0, c->stream, j.rows.rowptr, Ui, j.rows.out_col,
+                           n_links, j.ends, Ki, c->genome.ds, T, window, c->glob, j.pairs, j.expq, j.sc + JOIN_SC_MAXQ);
+        hipLaunchKernelGGL((k_join_model<64>), dim3((unsigned)((n_links * 64 + JOIN_THREADS - 1) / JOIN_THREADS)), dim3(JOIN_THREADS), 0, c->stream, j.rows.rowptr, Ui,
+                           j.rows.out_col, n_links, j.ends, Ki, c->genome.ds, T, window, c->glob, j.pairs, j.expq, j.sc + JOIN_SC_MAXQ);
         timer.end(JOIN_P_MODEL);
-        /* the overflow guard: a link adds at most w (w + 1) / 2 values of at most max_q */
-        unsigned long long max_q = 0;
-        HIPCK(hipMemcpyAsync(&max_q, j.sc + JOIN_SC_MAXQ, sizeof(max_q), hipMemcpyDeviceToHost, c->stream));
-        HIPCK(hipStreamSynchronize(c->stream));
-        const unsigned long long n = (unsigned long long)window * (unsigned long long)(window + 1) / 2; /* < 2^20 */
-        if (max_q > ((1ull << 62) - 1) / n) /* max_q * n >= 2^62 */
-            return fail("%s: model value too large for this window (the largest value, %.6g, times %llu pairs does not fit the 64-bit sum)", who,
-                        (double)max_q / IG_QSCALE, n);
+        if (check_model_sum(c, who, j.sc + JOIN_SC_MAXQ, window)) return -1;
     }
     HIPCK(hipStreamSynchronize(c->stream));
     return 0;
@@ -262,7 +203,7 @@ extern "C" int ig_join_support_rows(ig_ctx* c, int64_t* rowptr, int64_t capacity
     if (!rowptr) return fail("ig_join_support_rows: NULL output");
     const long long words = 2 * j.n_contigs + 1;
     if (capacity < words) return fail("ig_join_support_rows: the rows need %lld words, the caller's capacity is %lld", words, (long long)capacity);
-    HIPCK(hipMemcpy(rowptr, j.rowptr, (size_t)words * sizeof(int64_t), hipMemcpyDeviceToHost));
+    HIPCK(hipMemcpy(rowptr, j.rows.rowptr, (size_t)words * sizeof(int64_t), hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -277,8 +218,8 @@ extern "C" int ig_join_support_fetch(ig_ctx* c, int64_t first, int64_t n, int32_
     if ((pairs || expected_q) && !j.model) return fail("ig_join_support_fetch: the result was built with model = 0: it has no pairs and no expected_q");
     if (n == 0) return 0;
     if (!col || !observed) return fail("ig_join_support_fetch: NULL output");
-    HIPCK(hipMemcpy(col, j.out_col + first, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
-    HIPCK(hipMemcpy(observed, j.out_cnt + first, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost));
+    HIPCK(hipMemcpy(col, j.rows.out_col + first, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    HIPCK(hipMemcpy(observed, j.rows.out_cnt + first, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost));
     if (pairs) HIPCK(hipMemcpy(pairs, j.pairs + first, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost));
     if (expected_q) HIPCK(hipMemcpy(expected_q, j.expq + first, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost));
     return 0;
@@ -320,7 +261,7 @@ extern "C" int ig_debug_join_support_time(ig_ctx* c, int32_t window, int32_t n, 
         JoinBuf& j = c->join;
         unsigned long long s = 0, place = 1;
         std::vector<long long> rows((size_t)(2 * j.n_contigs + 1));
-        HIPCK(hipMemcpy(rows.data(), j.rowptr, rows.size() * sizeof(long long), hipMemcpyDeviceToHost));
+        HIPCK(hipMemcpy(rows.data(), j.rows.rowptr, rows.size() * sizeof(long long), hipMemcpyDeviceToHost));
         for (long long v : rows) s += (unsigned long long)v * place++;
         std::vector<int32_t> col((size_t)j.n_links);
         std::vector<int64_t> obs((size_t)j.n_links);

@@ -20,14 +20,12 @@ static void free_junc_buffers(ig_ctx* c)
     c->junc = JuncBuf{};
 }
 
-static inline int junc_chunks(int n_words) { return (n_words + JUNC_CHUNK - 1) / JUNC_CHUNK; }
-
-/* Argument checks, the guards of the map and the law's records (law_records), the buffers, the number of internal junctions.
- * T: placed sub-fragments. */
+/* Argument checks, the genome view (its guards, the records by position, ds and meta), the buffers, the number of internal
+ * junctions.  T: placed sub-fragments. */
 static int junc_prepare(ig_ctx* c, const char* who, int window, bool want_model, int* T_out)
 {
-    if (window < 1 || window > JUNC_MAX_WINDOW) return fail("%s: 1 <= window <= %d positions (got %d)", who, JUNC_MAX_WINDOW, window);
-    if (law_records(c, who, true, T_out)) return -1;
+    if (check_window(who, window)) return -1;
+    if (genome_positions(c, who, GENOME_RECORDS | GENOME_SORTED, T_out)) return -1;
     if (want_model && !c->have_params) return fail("%s: set parameters first", who);
     JuncBuf& j = c->junc;
     const int M = c->M;
@@ -35,13 +33,13 @@ static int junc_prepare(ig_ctx* c, const char* who, int window, bool want_model,
         free_junc_buffers(c);
         DALLOC(j.diff, 3 * ((size_t)M + 1));
         DALLOC(j.prof, 3 * ((size_t)M + 1));
-        DALLOC(j.tot, 3 * (size_t)junc_chunks(M + 1));
+        DALLOC(j.tot, 3 * (size_t)scan_chunks(M + 1));
         DALLOC(j.sc, (size_t)JUNC_NS);
         j.M = M;
     }
     const int T = *T_out;
     HIPCK(hipMemsetAsync(j.sc, 0, JUNC_NS * sizeof(unsigned long long), c->stream));
-    if (T > 0) hipLaunchKernelGGL(k_junc_count, dim3((T + JUNC_THREADS - 1) / JUNC_THREADS), dim3(JUNC_THREADS), 0, c->stream, c->law.meta, T, j.sc + JUNC_INTERNAL);
+    if (T > 0) hipLaunchKernelGGL(k_junc_count, dim3((T + JUNC_THREADS - 1) / JUNC_THREADS), dim3(JUNC_THREADS), 0, c->stream, c->genome.meta, T, j.sc + JUNC_INTERNAL);
     return 0;
 }
 
@@ -56,11 +54,11 @@ static int junc_enqueue_observed(ig_ctx* c, int T, int window, bool combine)
     const int blocks = (int)std::min<long long>((c->Z + JUNC_THREADS - 1) / JUNC_THREADS, 4096);
     const bool narrow = c->max_count < (1 << 25); /* 64 counts fit an int */
     if (combine && narrow)
-        hipLaunchKernelGGL((k_junc_observed<true, int>), dim3(blocks), dim3(JUNC_THREADS), 0, c->stream, c->crow, c->cc, c->Z, c->law.rec, window, diff, j.sc, c->rank, c->world);
+        hipLaunchKernelGGL((k_junc_observed<true, int>), dim3(blocks), dim3(JUNC_THREADS), 0, c->stream, c->crow, c->cc, c->Z, c->genome.rec, window, diff, j.sc, c->rank, c->world);
     else if (combine)
-        hipLaunchKernelGGL((k_junc_observed<true, long long>), dim3(blocks), dim3(JUNC_THREADS), 0, c->stream, c->crow, c->cc, c->Z, c->law.rec, window, diff, j.sc, c->rank, c->world);
+        hipLaunchKernelGGL((k_junc_observed<true, long long>), dim3(blocks), dim3(JUNC_THREADS), 0, c->stream, c->crow, c->cc, c->Z, c->genome.rec, window, diff, j.sc, c->rank, c->world);
     else
-        hipLaunchKernelGGL((k_junc_observed<false, int>), dim3(blocks), dim3(JUNC_THREADS), 0, c->stream, c->crow, c->cc, c->Z, c->law.rec, window, diff, j.sc, c->rank, c->world);
+        hipLaunchKernelGGL((k_junc_observed<false, int>), dim3(blocks), dim3(JUNC_THREADS), 0, c->stream, c->crow, c->cc, c->Z, c->genome.rec, window, diff, j.sc, c->rank, c->world);
     return 0;
 }
 
@@ -72,24 +70,12 @@ static int junc_enqueue_model(ig_ctx* c, int T, int window)
     HIPCK(hipMemsetAsync(j.sc + JUNC_DEV_MAXQ, 0, sizeof(unsigned long long), c->stream));
     if (T == 0) return 0;
     if (window > JUNC_WAVE_WINDOW)
-        hipLaunchKernelGGL((k_junc_model<64>), dim3((unsigned)(((long long)T * 64 + JUNC_THREADS - 1) / JUNC_THREADS)), dim3(JUNC_THREADS), 0, c->stream, c->law.ds, c->law.meta, T,
+        hipLaunchKernelGGL((k_junc_model<64>), dim3((unsigned)(((long long)T * 64 + JUNC_THREADS - 1) / JUNC_THREADS)), dim3(JUNC_THREADS), 0, c->stream, c->genome.ds, c->genome.meta, T,
                            window, c->glob, j.diff + JUNC_ARR_PAIRS * stride, j.diff + JUNC_ARR_EXP * stride, j.sc + JUNC_DEV_MAXQ);
     else
-        hipLaunchKernelGGL((k_junc_model<1>), dim3((T + JUNC_THREADS - 1) / JUNC_THREADS), dim3(JUNC_THREADS), 0, c->stream, c->law.ds, c->law.meta, T, window, c->glob,
+        hipLaunchKernelGGL((k_junc_model<1>), dim3((T + JUNC_THREADS - 1) / JUNC_THREADS), dim3(JUNC_THREADS), 0, c->stream, c->genome.ds, c->genome.meta, T, window, c->glob,
                            j.diff + JUNC_ARR_PAIRS * stride, j.diff + JUNC_ARR_EXP * stride, j.sc + JUNC_DEV_MAXQ);
     return 0;
-}
-
-/* The 64-bit inclusive prefix sums of n_arrays arrays of n words each, `stride` words apart: in -> out (in stays as it is), in three
- * steps on the library's stream; tot: n_arrays * junc_chunks(n) words of scratch.  Shared with the contacts in genome coordinates
- * (ig_host_lift.inc). */
-static void scan64_enqueue(ig_ctx* c, const unsigned long long* in, unsigned long long* out, long long stride, int n, int n_arrays,
-                           unsigned long long* tot)
-{
-    const int chunks = junc_chunks(n);
-    hipLaunchKernelGGL(k_junc_scan_totals, dim3(chunks, n_arrays), dim3(JUNC_THREADS), 0, c->stream, in, stride, n, tot);
-    hipLaunchKernelGGL(k_junc_scan_tops, dim3(n_arrays), dim3(JUNC_THREADS), 0, c->stream, tot, chunks);
-    hipLaunchKernelGGL(k_junc_scan_apply, dim3(chunks, n_arrays), dim3(JUNC_THREADS), 0, c->stream, in, out, stride, n, tot);
 }
 
 /* the prefix sums of the first n_arrays difference arrays: diff -> prof (diff stays as it is: the scan can be repeated) */
@@ -97,19 +83,6 @@ static int junc_enqueue_scan(ig_ctx* c, int T, int n_arrays)
 {
     JuncBuf& j = c->junc;
     scan64_enqueue(c, j.diff, j.prof, (long long)j.M + 1, T + 1, n_arrays, j.tot);
-    return 0;
-}
-
-/* the overflow guard of the model pass: a junction adds at most w (w + 1) / 2 values of at most max_q */
-static int junc_check_model(ig_ctx* c, const char* who, int window)
-{
-    unsigned long long max_q = 0;
-    HIPCK(hipMemcpyAsync(&max_q, c->junc.sc + JUNC_DEV_MAXQ, sizeof(max_q), hipMemcpyDeviceToHost, c->stream));
-    HIPCK(hipStreamSynchronize(c->stream));
-    const unsigned long long n = (unsigned long long)window * (unsigned long long)(window + 1) / 2; /* < 2^20 */
-    if (max_q > ((1ull << 62) - 1) / n) /* max_q * n >= 2^62 */
-        return fail("%s: model value too large for this window (the largest value, %.6g, times %llu pairs does not fit the 64-bit sum)", who,
-                    (double)max_q / IG_QSCALE, n);
     return 0;
 }
 
@@ -128,7 +101,7 @@ extern "C" int ig_junction_profile(ig_ctx* c, int32_t window, int64_t* observed,
     if (junc_enqueue_observed(c, T, window, JUNC_SHIP_COMBINE != 0)) return -1;
     if (model) {
         if (junc_enqueue_model(c, T, window)) return -1;
-        if (junc_check_model(c, "ig_junction_profile", window)) return -1;
+        if (check_model_sum(c, "ig_junction_profile", c->junc.sc + JUNC_DEV_MAXQ, window)) return -1;
     }
     if (junc_enqueue_scan(c, T, model ? 3 : 1)) return -1;
     JuncBuf& j = c->junc;
@@ -158,28 +131,11 @@ extern "C" int ig_debug_junction_profile_time(ig_ctx* c, int32_t window, int32_t
     if (n < 1 || !ms_observed_n) return fail("ig_debug_junction_profile_time: bad arguments");
     int T = 0;
     if (junc_prepare(c, "ig_debug_junction_profile_time", window, ms_model_n != nullptr, &T)) return -1;
-    hipEvent_t a, b;
-    HIPCK(hipEventCreate(&a));
-    HIPCK(hipEventCreate(&b));
-    int rc = 0;
-    const int n_arrays = ms_model_n ? 3 : 1;
-    for (int pass = 0; pass < 3 && !rc; pass++) {
-        float* ms = pass == 0 ? ms_observed_n : pass == 1 ? ms_model_n : ms_scan_n;
-        if (!ms && pass == 1) continue;
-        for (int r = 0; r < (ms ? n : 1) && !rc; r++) { /* (the scan runs once where nobody asked for its time: the checksum needs it) */
-            hipError_t e = hipEventRecord(a, c->stream);
-            rc = pass == 0 ? junc_enqueue_observed(c, T, window, combine != 0) : pass == 1 ? junc_enqueue_model(c, T, window) : junc_enqueue_scan(c, T, n_arrays);
-            if (e == hipSuccess) e = hipEventRecord(b, c->stream);
-            if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-            float t = 0.0f;
-            if (e == hipSuccess) e = hipEventElapsedTime(&t, a, b);
-            if (ms) ms[r] = t;
-            if (e != hipSuccess && !rc) rc = fail("ig_debug_junction_profile_time: %s", hipGetErrorString(e));
-        }
-    }
-    hipEventDestroy(a);
-    hipEventDestroy(b);
-    if (rc) return rc;
+    const char* who = "ig_debug_junction_profile_time";
+    if (time_repeats(c, who, n, ms_observed_n, [&] { return junc_enqueue_observed(c, T, window, combine != 0); })) return -1;
+    if (ms_model_n && time_repeats(c, who, n, ms_model_n, [&] { return junc_enqueue_model(c, T, window); })) return -1;
+    /* (the scan runs once where nobody asked for its time: the checksum needs it) */
+    if (time_repeats(c, who, ms_scan_n ? n : 1, ms_scan_n, [&] { return junc_enqueue_scan(c, T, ms_model_n ? 3 : 1); })) return -1;
     if (checksum) { /* of the last observed pass behind the scan, every word weighted by its place: both forms of the kernel must agree on it */
         std::vector<long long> h((size_t)T + JUNC_N_OBS, 0);
         if (T > 0) HIPCK(hipMemcpy(h.data(), c->junc.prof, (size_t)T * sizeof(long long), hipMemcpyDeviceToHost));

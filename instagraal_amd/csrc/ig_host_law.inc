@@ -11,59 +11,13 @@
 
 static void free_law_buffers(ig_ctx* c)
 {
-    hipFree(c->law.rec);
-    hipFree(c->law.ds);
-    hipFree(c->law.meta);
     hipFree(c->law.edges);
     hipFree(c->law.out);
     hipFree(c->law.flag);
     c->law = LawBuf{};
 }
 
-/* the law's buffers, kept from call to call */
-static int law_ensure_buffers(ig_ctx* c)
-{
-    LawBuf& l = c->law;
-    const int M = c->M;
-    if (l.M != M) {
-        free_law_buffers(c);
-        DALLOC(l.rec, (size_t)M);
-        DALLOC(l.ds, (size_t)M);
-        DALLOC(l.meta, (size_t)M);
-        DALLOC(l.edges, (size_t)LAW_MAX_EDGES);
-        DALLOC(l.out, (size_t)LAW_OUT_WORDS);
-        DALLOC(l.flag, 1);
-        l.M = M;
-    }
-    return 0;
-}
-
-/* ds and meta by position of the genome order (map_prepare with want_order has run), on the library's stream; the expected map
- * (ig_host_emap.inc), which reads no contact and so needs no record, takes these alone */
-static void law_enqueue_sorted(ig_ctx* c, int T)
-{
-    if (T > 0) hipLaunchKernelGGL(k_law_sorted, dim3((T + 255) / 256), dim3(256), 0, c->stream, c->tab, c->map.order, c->M, T, c->law.ds, c->law.meta);
-}
-
-/* The records both passes read, without the edges (the junction profile shares them, ig_host_junc.inc): the guards of the map
- * (map_prepare), the genome order, then on the library's stream k_law_records and, want_sorted, k_law_sorted.  Not waited for.
- * T: placed sub-fragments. */
-static int law_records(ig_ctx* c, const char* who, bool want_sorted, int* T_out)
-{
-    if (!c->have_contacts) return fail("%s: upload the contacts first", who);
-    int T = 0, bin = 1, side = 0;
-    /* max_side = M >= T: one position per pixel, so rec.w is the position itself (the law reads its sign only, the junction
-     * profile the position) */
-    if (map_prepare(c, who, std::max(c->M, 1), true, &T, &bin, &side)) return -1;
-    if (law_ensure_buffers(c)) return -1;
-    const int M = c->M;
-    hipLaunchKernelGGL(k_law_records, dim3((M + 255) / 256), dim3(256), 0, c->stream, c->tab, c->map.pix, M, c->law.rec);
-    if (want_sorted) law_enqueue_sorted(c, T);
-    *T_out = T;
-    return 0;
-}
-
-/* Argument checks, then the records of both passes and the edges on the device. */
+/* Argument checks, then the records of both passes (the genome view's) and the edges on the device. */
 static int law_prepare(ig_ctx* c, const char* who, const float* edges, int n_edges, bool want_pairs, int* T_out)
 {
     if (!edges) return fail("%s: edges is NULL", who);
@@ -72,7 +26,15 @@ static int law_prepare(ig_ctx* c, const char* who, const float* edges, int n_edg
         if (!(edges[i] - edges[i] == 0.0f)) return fail("%s: edge %d is not finite", who, i);
         if (i && edges[i] < edges[i - 1]) return fail("%s: the edges are not sorted (edge %d < edge %d)", who, i, i - 1);
     }
-    if (law_records(c, who, want_pairs, T_out)) return -1;
+    /* (the records' position is read for its sign only) */
+    if (genome_positions(c, who, GENOME_RECORDS | (want_pairs ? GENOME_SORTED : 0u), T_out)) return -1;
+    LawBuf& l = c->law;
+    if (!l.flag) { /* (the last of the three: a build-up that failed half way starts again) */
+        free_law_buffers(c);
+        DALLOC(l.edges, (size_t)LAW_MAX_EDGES);
+        DALLOC(l.out, (size_t)LAW_OUT_WORDS);
+        DALLOC(l.flag, 1);
+    }
     HIPCK(hipMemcpyAsync(c->law.edges, edges, (size_t)n_edges * sizeof(float), hipMemcpyHostToDevice, c->stream));
     HIPCK(hipStreamSynchronize(c->stream)); /* (`edges` is the caller's pageable memory) */
     return 0;
@@ -88,10 +50,10 @@ static int law_enqueue_observed(ig_ctx* c, int n_edges, bool privatised)
     const int blocks = (int)std::min<long long>((c->Z + LAW_THREADS - 1) / LAW_THREADS, 2048);
     const size_t lds = law_lds_bytes(n_edges);
     if (privatised)
-        hipLaunchKernelGGL((k_law_observed<true>), dim3(blocks), dim3(LAW_THREADS), lds, c->stream, c->crow, c->cc, c->Z, l.rec, l.edges, n_edges,
+        hipLaunchKernelGGL((k_law_observed<true>), dim3(blocks), dim3(LAW_THREADS), lds, c->stream, c->crow, c->cc, c->Z, c->genome.rec, l.edges, n_edges,
                            l.out + LAW_OUT_OBS, l.out + LAW_OUT_OSC, c->rank, c->world);
     else
-        hipLaunchKernelGGL((k_law_observed<false>), dim3(blocks), dim3(LAW_THREADS), lds, c->stream, c->crow, c->cc, c->Z, l.rec, l.edges, n_edges,
+        hipLaunchKernelGGL((k_law_observed<false>), dim3(blocks), dim3(LAW_THREADS), lds, c->stream, c->crow, c->cc, c->Z, c->genome.rec, l.edges, n_edges,
                            l.out + LAW_OUT_OBS, l.out + LAW_OUT_OSC, c->rank, c->world);
     return 0;
 }
@@ -106,10 +68,10 @@ static int law_enqueue_pairs(ig_ctx* c, int T, int n_edges, bool brute)
     const int blocks = (T + LAW_THREADS - 1) / LAW_THREADS;
     const size_t lds = law_lds_bytes(n_edges);
     if (brute)
-        hipLaunchKernelGGL((k_law_pairs<true>), dim3(blocks), dim3(LAW_THREADS), lds, c->stream, l.ds, l.meta, T, l.edges, n_edges, l.out + LAW_OUT_PAIRS,
+        hipLaunchKernelGGL((k_law_pairs<true>), dim3(blocks), dim3(LAW_THREADS), lds, c->stream, c->genome.ds, c->genome.meta, T, l.edges, n_edges, l.out + LAW_OUT_PAIRS,
                            l.out + LAW_OUT_PSC, l.flag);
     else
-        hipLaunchKernelGGL((k_law_pairs<false>), dim3(blocks), dim3(LAW_THREADS), lds, c->stream, l.ds, l.meta, T, l.edges, n_edges, l.out + LAW_OUT_PAIRS,
+        hipLaunchKernelGGL((k_law_pairs<false>), dim3(blocks), dim3(LAW_THREADS), lds, c->stream, c->genome.ds, c->genome.meta, T, l.edges, n_edges, l.out + LAW_OUT_PAIRS,
                            l.out + LAW_OUT_PSC, l.flag);
     return 0;
 }
@@ -158,25 +120,9 @@ extern "C" int ig_debug_distance_law_time(ig_ctx* c, const float* edges, int32_t
     if (n < 1 || !ms_observed_n) return fail("ig_debug_distance_law_time: bad arguments");
     int T = 0;
     if (law_prepare(c, "ig_debug_distance_law_time", edges, n_edges, ms_pairs_n != nullptr, &T)) return -1;
-    hipEvent_t a, b;
-    HIPCK(hipEventCreate(&a));
-    HIPCK(hipEventCreate(&b));
-    int rc = 0;
-    for (int pass = 0; pass < 2 && !rc; pass++) {
-        float* ms = pass ? ms_pairs_n : ms_observed_n;
-        if (!ms) continue;
-        for (int r = 0; r < n && !rc; r++) {
-            hipError_t e = hipEventRecord(a, c->stream);
-            rc = pass ? law_enqueue_pairs(c, T, n_edges, false) : law_enqueue_observed(c, n_edges, privatised != 0);
-            if (e == hipSuccess) e = hipEventRecord(b, c->stream);
-            if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-            if (e == hipSuccess) e = hipEventElapsedTime(&ms[r], a, b);
-            if (e != hipSuccess && !rc) rc = fail("ig_debug_distance_law_time: %s", hipGetErrorString(e));
-        }
-    }
-    hipEventDestroy(a);
-    hipEventDestroy(b);
-    if (rc) return rc;
+    const char* who = "ig_debug_distance_law_time";
+    if (time_repeats(c, who, n, ms_observed_n, [&] { return law_enqueue_observed(c, n_edges, privatised != 0); })) return -1;
+    if (ms_pairs_n && time_repeats(c, who, n, ms_pairs_n, [&] { return law_enqueue_pairs(c, T, n_edges, false); })) return -1;
     if (checksum) { /* of the last observed pass, every word weighted by its place: both forms of the kernel must agree on it */
         std::vector<long long> h(LAW_MAX_BINS + LAW_NS);
         HIPCK(hipMemcpy(h.data(), c->law.out, h.size() * sizeof(long long), hipMemcpyDeviceToHost));

@@ -1,12 +1,6 @@
 /* ig_host_place.inc -- part of ig_hip.hip (one translation unit; included there in order): placement support, where the contacts say
  * each bin belongs (ig_kernels_place.cuh; the rule: instagraal_amd/placement_support.py). */
 
-/* PlaceBuf.sc, in 64-bit words: the scalars of the passes over the contacts, k_lift_classify's sizes and cursors, the heads of the
- * reduction */
-#define PLACE_SC_CLS PLACE_NS
-#define PLACE_SC_CUR (PLACE_SC_CLS + LIFT_C_WORDS)
-#define PLACE_SC_HEADS (PLACE_SC_CUR + 5)
-#define PLACE_SC_WORDS (PLACE_SC_HEADS + 1)
 /* the passes ig_debug_placement_support_time reports, in this order */
 #define PLACE_P_RECORDS 0
 #define PLACE_P_COUNT 1
@@ -28,19 +22,12 @@ static void free_place_buffers(ig_ctx* c)
     PlaceBuf& p = c->place;
     hipFree(p.head);
     hipFree(p.incl);
+    hipFree(p.htot);
     hipFree(p.rec);
     hipFree(p.ends);
-    hipFree(p.tot);
     hipFree(p.bins);
-    hipFree(p.count);
-    hipFree(p.cursor);
     hipFree(p.sc);
-    hipFree(p.rowstart);
-    hipFree(p.ent);
-    lift_work_free(p.work);
-    hipFree(p.rowptr);
-    hipFree(p.out_col);
-    hipFree(p.out_cnt);
+    rows_free(p.rows);
     hipFree(p.pre);
     hipFree(p.ptot);
     hipFree(p.out_i);
@@ -53,99 +40,71 @@ static void free_place_buffers(ig_ctx* c)
     for (int k = 0; k < 8; k++) p.forms[k] = forms[k];
 }
 
-/* One call up to the device's arrays (p.out_i, p.out_l) and the scalars.  The caller frees everything. */
+/* One call up to the device's arrays (p.out_i, p.out_l) and the scalars: the records and the bins, the rows of the profile
+ * (rows_build) from k_place_emit, their prefix sums, the scan over the sites.  The caller frees everything. */
 static int place_impl(ig_ctx* c, const char* who, int window, int min_hosts, float* ms, long long scalars[7])
 {
     PlaceBuf& p = c->place;
     for (int k = 0; k < 8; k++) p.forms[k] = 0; /* (a call that fails reports no lists of an earlier one) */
-    if (window < 1 || window > JUNC_MAX_WINDOW) return fail("%s: 1 <= window <= %d positions (got %d)", who, JUNC_MAX_WINDOW, window);
+    if (check_window(who, window)) return -1;
     if (min_hosts < 1 || min_hosts > 2 * window) return fail("%s: 1 <= min_hosts <= 2 * window = %d (got %d)", who, 2 * window, min_hosts);
     if (c->world != 1) return fail("%s: placement support needs all contacts on one handle (this one holds shard %d of %d)", who, c->rank, c->world);
     int T = 0;
-    if (law_records(c, who, true, &T)) return -1; /* (the guards of the map under this entry point's name; max_side = M: pix is the position) */
+    if (genome_positions(c, who, GENOME_SORTED, &T)) return -1;
     const int M = c->M, N = c->N;
     if (N < 1 || N > 2 * M + 3) return fail("%s: %d bins over %d sub-fragments (inconsistent tables)", who, N, M);
     LiftTimer timer(c, ms, PLACE_PASSES);
-    DALLOC(p.sc, (size_t)PLACE_SC_WORDS);
-    HIPCK(hipMemsetAsync(p.sc, 0, PLACE_SC_WORDS * sizeof(unsigned long long), c->stream));
+    DALLOC(p.sc, (size_t)PLACE_NS);
+    HIPCK(hipMemsetAsync(p.sc, 0, PLACE_NS * sizeof(unsigned long long), c->stream));
     /* the records: per sub-fragment (the join support's), per bin */
     long long K = 0;
     timer.begin();
-    if (join_enqueue_records(c, who, T, p.head, p.incl, p.tot, p.rec, p.ends, &K)) return -1;
+    if (join_enqueue_records(c, who, T, p.head, p.incl, p.htot, p.rec, p.ends, &K)) return -1;
     const int Ki = (int)K;
     DALLOC(p.bins, (size_t)N);
     hipLaunchKernelGGL(k_place_bins, dim3((N + PLACE_THREADS - 1) / PLACE_THREADS), dim3(PLACE_THREADS), 0, c->stream, c->st.sub_first, c->st.sl, N, M, p.rec, T, p.bins);
     timer.end(PLACE_P_RECORDS);
-    /* count */
-    DALLOC(p.count, (size_t)N + 2);
-    DALLOC(p.cursor, (size_t)N + 2);
-    DALLOC(p.rowstart, (size_t)N + 1);
-    timer.begin();
-    HIPCK(hipMemsetAsync(p.count, 0, ((size_t)N + 2) * sizeof(unsigned long long), c->stream));
-    if (c->Z > 0)
-        hipLaunchKernelGGL((k_place_emit<false>), dim3(lift_blocks(c->Z)), dim3(PLACE_THREADS), 0, c->stream, c->crow, c->cc, c->Z, p.rec, c->sub_tab, N, p.count, nullptr, 0ull,
-                           p.sc);
-    timer.end(PLACE_P_COUNT);
-    /* the rows' starts */
-    timer.begin();
-    HIPCK(hipMemsetAsync(p.rowstart, 0, sizeof(unsigned long long), c->stream));
-    scan64_enqueue(c, p.count, p.rowstart + 1, 0, N, 1, p.tot);
-    timer.end(PLACE_P_ROWS);
+    /* the profile */
+    auto emit = [&](bool scatter, unsigned long long* slots, unsigned long long* ent, unsigned long long n_ent) {
+        const dim3 grid(lift_blocks(c->Z)), block(PLACE_THREADS);
+        if (!scatter) hipLaunchKernelGGL((k_place_emit<false>), grid, block, 0, c->stream, c->crow, c->cc, c->Z, p.rec, c->sub_tab, N, slots, ent, n_ent, p.sc);
+        else hipLaunchKernelGGL((k_place_emit<true>), grid, block, 0, c->stream, c->crow, c->cc, c->Z, p.rec, c->sub_tab, N, slots, ent, n_ent, p.sc);
+    };
     unsigned long long sc[PLACE_NS];
-    HIPCK(hipMemcpyAsync(sc, p.sc, sizeof(sc), hipMemcpyDeviceToHost, c->stream));
-    HIPCK(hipStreamSynchronize(c->stream));
-    for (int k = 0; k < PLACE_NS; k++) scalars[k] = (long long)sc[k];
-    scalars[5] = K;
-    scalars[6] = 0;
-    /* the overflow guard: obs * hosts <= sum(counts) * 2 w must stay below 2^62 */
-    unsigned long long total = 0;
-    for (int k = 0; k < 4; k++) {
-        if (sc[k] >= 1ull << 62) return fail("%s: counts too large for this window", who);
-        total += sc[k];
-    }
-    if (total > ((1ull << 62) - 1) / (2ull * (unsigned long long)window)) /* 2 w total >= 2^62 */
-        return fail("%s: counts too large for this window (the contacts sum to %llu; times %d hosts that does not fit the 64-bit comparison)", who, total,
-                    2 * window);
-    const long long E = (long long)sc[PLACE_ENTRIES];
-    if (E < 0 || E > 2 * (long long)c->Z || (E & 1) || (E > 0 && (K < 1 || N < 2)))
-        return fail("%s: %lld entries of %lld contacts over %lld contigs (device error)", who, E, (long long)c->Z, K);
-    if (E > 0x7fffffffll) return fail("%s: %lld entries are more than one call can sort (2^31 - 1)", who, E);
-    long long n_sum = 0;
-    if (E > 0) {
-        /* what the entries need at the most, before anything is allocated by their number: per entry the word itself, the long rows'
-         * scratch and their runs' items (8 bytes each), a bit, and a summed entry of its own (position, count, prefix sum: 20 bytes);
-         * per row the lists of the three forms */
-        {
-            const unsigned long long need = (unsigned long long)E * 45 + (unsigned long long)(N + 1) * (8 + sizeof(LiftItem) + sizeof(LiftLong)) + (1ull << 20);
-            size_t free_b = ~(size_t)0, total_b = 0;
-            if (&hipMemGetInfo != nullptr) HIPCK(hipMemGetInfo(&free_b, &total_b));
-            if (need > (unsigned long long)free_b) return fail("%s: %lld entries need %llu bytes of device memory, %zu are free", who, E, need, free_b);
+    auto check = [&](long long E) {
+        for (int k = 0; k < PLACE_NS; k++) scalars[k] = (long long)sc[k];
+        scalars[5] = K;
+        scalars[6] = 0;
+        /* the overflow guard: obs * hosts <= sum(counts) * 2 w must stay below 2^62 */
+        unsigned long long total = 0;
+        for (int k = 0; k < 4; k++) {
+            if (sc[k] >= 1ull << 62) return fail("%s: counts too large for this window", who);
+            total += sc[k];
         }
-        DALLOC(p.ent, (size_t)E);
-        /* scatter */
-        timer.begin();
-        HIPCK(hipMemcpyAsync(p.cursor, p.rowstart, (size_t)N * sizeof(unsigned long long), hipMemcpyDeviceToDevice, c->stream));
-        hipLaunchKernelGGL((k_place_emit<true>), dim3(lift_blocks(c->Z)), dim3(PLACE_THREADS), 0, c->stream, c->crow, c->cc, c->Z, p.rec, c->sub_tab, N, p.cursor, p.ent,
-                           (unsigned long long)E, p.sc);
-        timer.end(PLACE_P_SCATTER);
-        /* sort and reduce: the lift's, under the limits of ig_debug_assembly_contacts_limits */
-        if (lift_sort_rows(c, who, timer, PLACE_P_SORT_SHORT, p.rowstart, N, p.ent, E, c->lift.short_max, c->lift.lds_max, p.sc + PLACE_SC_CLS, p.sc + PLACE_SC_CUR, p.forms,
-                           p.work))
-            return -1;
-        if (lift_reduce_rows(c, who, timer, PLACE_P_REDUCE, p.rowstart, N, p.ent, E, p.sc + PLACE_SC_HEADS, p.count, p.tot, p.work, &p.out_col, &p.out_cnt, &p.rowptr, &n_sum))
-            return -1;
-    } else { /* an empty profile: every row is empty */
-        DALLOC(p.rowptr, (size_t)N + 1);
-        DALLOC(p.out_col, (size_t)0);
-        DALLOC(p.out_cnt, (size_t)0);
-        HIPCK(hipMemsetAsync(p.rowptr, 0, ((size_t)N + 1) * sizeof(unsigned long long), c->stream));
+        if (total > ((1ull << 62) - 1) / (2ull * (unsigned long long)window)) /* 2 w total >= 2^62 */
+            return fail("%s: counts too large for this window (the contacts sum to %llu; times %d hosts that does not fit the 64-bit comparison)", who, total,
+                        2 * window);
+        if (E < 0 || E > 2 * (long long)c->Z || (E & 1) || (E > 0 && (K < 1 || N < 2)))
+            return fail("%s: %lld entries of %lld contacts over %lld contigs (device error)", who, E, (long long)c->Z, K);
+        if (E > 0x7fffffffll) return fail("%s: %lld entries are more than one call can sort (2^31 - 1)", who, E);
+        return 0;
+    };
+    /* per entry: the word itself, the long rows' scratch and their runs' items (8 bytes each), a bit, and a summed entry of its own
+     * (position, count, prefix sum: 20 bytes) */
+    const RowsSpec spec = {p.sc, PLACE_NS, PLACE_ENTRIES, 45, "", true, {PLACE_P_COUNT, PLACE_P_ROWS, PLACE_P_SCATTER, PLACE_P_SORT_SHORT, PLACE_P_REDUCE}};
+    long long E = 0, n_sum = 0;
+    if (rows_build(c, who, p.rows, N, spec, sc, check, emit, timer, p.forms, &E, &n_sum)) return -1;
+    if (E == 0) { /* an empty profile: every row is empty */
+        DALLOC(p.rows.out_col, (size_t)0);
+        DALLOC(p.rows.out_cnt, (size_t)0);
     }
+    const RowBuf& r = p.rows;
     /* the exclusive prefix sums of the summed counts */
     DALLOC(p.pre, (size_t)n_sum + 1);
-    DALLOC(p.ptot, (size_t)junc_chunks((int)std::max<long long>(n_sum, 1)));
+    DALLOC(p.ptot, (size_t)scan_chunks(std::max<long long>(n_sum, 1)));
     timer.begin();
     HIPCK(hipMemsetAsync(p.pre, 0, sizeof(unsigned long long), c->stream));
-    if (n_sum > 0) scan64_enqueue(c, p.out_cnt, p.pre + 1, 0, (int)n_sum, 1, p.ptot);
+    if (n_sum > 0) scan64_enqueue(c, r.out_cnt, p.pre + 1, 0, (int)n_sum, 1, p.ptot);
     timer.end(PLACE_P_PREFIX);
     /* the scan */
     DALLOC(p.out_i, (size_t)PLACE_NI * (size_t)N);
@@ -153,11 +112,11 @@ static int place_impl(ig_ctx* c, const char* who, int window, int min_hosts, flo
     const long long wave_entries = p.form == 1 ? (long long)0x7fffffffffffffffll : p.form == 2 ? -1ll : (long long)PLACE_WAVE_ENTRIES;
     timer.begin();
     if (p.form != 2)
-        hipLaunchKernelGGL((k_place_scan<1>), dim3((N + PLACE_THREADS - 1) / PLACE_THREADS), dim3(PLACE_THREADS), 0, c->stream, p.bins, N, p.rowptr, p.out_col, p.pre, n_sum,
-                           c->law.meta, p.incl, T, Ki, window, min_hosts, wave_entries, p.out_i, p.out_l);
+        hipLaunchKernelGGL((k_place_scan<1>), dim3((N + PLACE_THREADS - 1) / PLACE_THREADS), dim3(PLACE_THREADS), 0, c->stream, p.bins, N, r.rowptr, r.out_col, p.pre, n_sum,
+                           c->genome.meta, p.incl, T, Ki, window, min_hosts, wave_entries, p.out_i, p.out_l);
     if (p.form != 1)
-        hipLaunchKernelGGL((k_place_scan<64>), dim3((unsigned)(((long long)N * 64 + PLACE_THREADS - 1) / PLACE_THREADS)), dim3(PLACE_THREADS), 0, c->stream, p.bins, N, p.rowptr,
-                           p.out_col, p.pre, n_sum, c->law.meta, p.incl, T, Ki, window, min_hosts, wave_entries, p.out_i, p.out_l);
+        hipLaunchKernelGGL((k_place_scan<64>), dim3((unsigned)(((long long)N * 64 + PLACE_THREADS - 1) / PLACE_THREADS)), dim3(PLACE_THREADS), 0, c->stream, p.bins, N, r.rowptr,
+                           r.out_col, p.pre, n_sum, c->genome.meta, p.incl, T, Ki, window, min_hosts, wave_entries, p.out_i, p.out_l);
     timer.end(PLACE_P_SCAN);
     HIPCK(hipStreamSynchronize(c->stream));
     return 0;

@@ -4,13 +4,13 @@
  * two ends were adjacent.  The rule is stated once, in instagraal_amd/join_support.py; the passes here reproduce its arrays byte
  * for byte.
  *
- * The ends: k_join_heads flags the first position of every linear placed contig, the 64-bit scan of the junction profile numbers
+ * The ends: k_join_heads flags the first position of every linear placed contig, the 64-bit scan (ig_kernels_rows.cuh) numbers
  * them, k_join_ends writes the table per contig (first position, positions, length in kb) and k_join_records one 16-byte record
  * per sub-fragment: (depth from the head, depth from the tail, run index or JOIN_UNPLACED / JOIN_RING, the position or 0: the
  * placement support, ig_kernels_place.cuh, reads the last).
  * The links: k_join_emit is the counting sort of the contacts in genome coordinates (k_lift_pass) with up to four emissions per
  * contact, entry = (row: the lower end, word: the upper end << 32 | count); the rows are sorted and the equal columns summed by
- * the kernels of ig_kernels_lift.cuh on this feature's own buffers.  Integer sums: the result does not depend on the launch
+ * the kernels of ig_kernels_rows.cuh on this feature's own buffers.  Integer sums: the result does not depend on the launch
  * shapes or on the order in which the atomics land.
  * The model: k_join_model<G> over the links found, G lanes per link.
  *
@@ -90,7 +90,7 @@ __global__ void __launch_bounds__(JOIN_THREADS) k_join_records(const int* __rest
  * SCATTER = true: the counters have become cursors; every emission takes the next slot of its row and writes (hi, count) there.
  * n_ent: the entries the first pass counted -- nothing is written beyond them.
  * COMBINE = false, the yardstick: one atomic per emission.  COMBINE = true: for each of the four emissions in turn a run of a
- * wave's lanes with an equal lo issues ONE atomic, by its head and for the run's length (the run-head ballot of k_lift_pass): late
+ * wave's lanes with an equal lo issues ONE atomic, by its head and for the run's length (rows_slot, ig_kernels_rows.cuh): late
  * in an assembly there are few ends, and every lane of a wave hits the same counter.
  * A sharded handle takes the rows i % world == rank. */
 template <bool SCATTER, bool COMBINE>
@@ -146,20 +146,8 @@ __global__ void __launch_bounds__(JOIN_THREADS) k_join_emit(const int* __restric
             unsigned long long slot = 0;
             if (!COMBINE) {
                 if (lo >= 0) slot = atomicAdd(&counter[lo], 1ull);
-            } else {
-                const int left = __shfl_up(lo, 1, 64);
-                const bool head = lane == 0 || left != lo;
-                const unsigned long long heads = __ballot(head);
-                const unsigned long long above = lane == 63 ? 0ull : heads >> (lane + 1);
-                const int run_end = above ? lane + __ffsll((long long)above) : 64; /* first lane behind this lane's run */
-                unsigned long long base = 0;
-                if (head && lo >= 0) base = atomicAdd(&counter[lo], (unsigned long long)(run_end - lane));
-                if (SCATTER) {
-                    const unsigned long long upto = lane == 63 ? heads : heads & ((2ull << lane) - 1ull); /* (lane 0 is a head) */
-                    const int start = 63 - __clzll((long long)upto); /* the head of this lane's run */
-                    slot = __shfl(base, start, 64) + (unsigned long long)(lane - start);
-                }
-            }
+            } else
+                slot = rows_slot<SCATTER>(counter, lo, lane);
             if (SCATTER && lo >= 0 && slot < n_ent) ent[slot] = lift_pack(hi, cnt);
         }
     }
@@ -171,11 +159,7 @@ __global__ void __launch_bounds__(JOIN_THREADS) k_join_emit(const int* __restric
     if (r_unpl) atomicAdd(&sc[JOIN_UNPLACED_OBS], r_unpl);
     if (r_contrib) atomicAdd(&sc[JOIN_CONTRIBUTIONS], r_contrib);
     if (r_ent) atomicAdd(&sc[JOIN_ENTRIES], r_ent);
-    __syncthreads();
-    if (threadIdx.x < JOIN_NS) {
-        const unsigned long long v = sc[threadIdx.x];
-        if (v) atomicAdd(&out_sc[threadIdx.x], v);
-    }
+    rows_flush<JOIN_NS>(sc, out_sc);
 }
 
 /* pairs of a link between ends of contigs of na and nb positions: depth u = 0 .. ua - 1, ua = min(w, na), pairs with

@@ -7,7 +7,7 @@
  * placed contig that is not a ring adds its value at word pa + 1 and takes it away at word pb + 1, so the junctions pa < j <= pb
  * see it.  Unsigned wrap-around adds: the sums return to 0 behind every contig, so whatever wraps on the way unwraps again, and
  * integer addition makes the result independent of threads, waves, workgroups and the order of the atomics.  The records are
- * the distance law's (k_law_records, k_law_sorted).
+ * the genome view's (ig_kernels_genome.cuh), the prefix sum is the 64-bit scan of ig_kernels_rows.cuh.
  *
  * Nothing here writes anything a move reads. */
 #pragma once
@@ -24,8 +24,6 @@
 #define JUNC_INTERNAL 5
 #define JUNC_SPANNED 6  /* (summed on the host from the profile) */
 #define JUNC_DEV_MAXQ 6 /* on the device that word holds the largest |quantised model value| the model pass saw */
-#define JUNC_ITEMS 8    /* words per thread of the scan */
-#define JUNC_CHUNK (JUNC_THREADS * JUNC_ITEMS)
 #define JUNC_WAVE_WINDOW 64 /* windows beyond this: one wave per position in the model pass, else one thread */
 
 /* The observed part: one pass over the contacts (row of contact k: crow[k]; column and count: cc[k]; row-major sorted), one
@@ -178,84 +176,4 @@ __global__ void __launch_bounds__(JUNC_THREADS) k_junc_model(const float* __rest
     }
     /* (the maximum only grows: a wave that cannot raise what is there already leaves the word alone) */
     if ((threadIdx.x & 63) == 0 && mx > *(volatile unsigned long long*)maxq) atomicMax(maxq, mx);
-}
-
-/* ---- the prefix sums of the difference arrays (blockIdx.y: the array), in three steps: the totals of chunks of JUNC_CHUNK words,
- * an exclusive scan of the totals by one workgroup, every chunk scanned again from its total.  No workgroup waits for another. */
-
-/* exclusive prefix of v over the workgroup's threads, and the total; wsum: JUNC_THREADS / 64 words of LDS */
-__device__ __forceinline__ unsigned long long junc_block_scan(unsigned long long v, unsigned long long* wsum, unsigned long long* total)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    unsigned long long inc = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const unsigned long long o = __shfl_up(inc, d, 64);
-        if (lane >= d) inc += o;
-    }
-    __syncthreads(); /* (whoever called before has read wsum) */
-    if (lane == 63) wsum[wave] = inc;
-    __syncthreads();
-    unsigned long long before = 0, all = 0;
-#pragma unroll
-    for (int k = 0; k < JUNC_THREADS / 64; k++) {
-        const unsigned long long s = wsum[k];
-        if (k < wave) before += s;
-        all += s;
-    }
-    *total = all;
-    return before + inc - v;
-}
-
-__global__ void __launch_bounds__(JUNC_THREADS) k_junc_scan_totals(const unsigned long long* __restrict__ in, long long stride, int n,
-                                                                   unsigned long long* __restrict__ totals)
-{
-    __shared__ unsigned long long wsum[JUNC_THREADS / 64];
-    const unsigned long long* a = in + (long long)blockIdx.y * stride;
-    const int base = blockIdx.x * JUNC_CHUNK;
-    unsigned long long v = 0;
-#pragma unroll
-    for (int i = 0; i < JUNC_ITEMS; i++) {
-        const int idx = base + i * JUNC_THREADS + threadIdx.x;
-        if (idx < n) v += a[idx];
-    }
-    unsigned long long total;
-    junc_block_scan(v, wsum, &total);
-    if (threadIdx.x == 0) totals[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = total;
-}
-
-__global__ void __launch_bounds__(JUNC_THREADS) k_junc_scan_tops(unsigned long long* __restrict__ totals, int n_chunks)
-{
-    __shared__ unsigned long long wsum[JUNC_THREADS / 64];
-    unsigned long long* t = totals + (size_t)blockIdx.x * n_chunks;
-    unsigned long long carry = 0;
-    for (int base = 0; base < n_chunks; base += JUNC_THREADS) {
-        const int i = base + threadIdx.x;
-        unsigned long long total;
-        const unsigned long long ex = junc_block_scan(i < n_chunks ? t[i] : 0ull, wsum, &total);
-        if (i < n_chunks) t[i] = carry + ex;
-        carry += total;
-    }
-}
-
-__global__ void __launch_bounds__(JUNC_THREADS) k_junc_scan_apply(const unsigned long long* __restrict__ in, unsigned long long* __restrict__ out,
-                                                                  long long stride, int n, const unsigned long long* __restrict__ totals)
-{
-    __shared__ unsigned long long wsum[JUNC_THREADS / 64];
-    const unsigned long long* a = in + (long long)blockIdx.y * stride;
-    unsigned long long* o = out + (long long)blockIdx.y * stride;
-    const int first = blockIdx.x * JUNC_CHUNK + threadIdx.x * JUNC_ITEMS; /* JUNC_ITEMS words in a row per thread */
-    unsigned long long w[JUNC_ITEMS], v = 0;
-#pragma unroll
-    for (int i = 0; i < JUNC_ITEMS; i++) {
-        w[i] = first + i < n ? a[first + i] : 0ull;
-        v += w[i];
-    }
-    unsigned long long total;
-    unsigned long long run = totals[(size_t)blockIdx.y * gridDim.x + blockIdx.x] + junc_block_scan(v, wsum, &total);
-#pragma unroll
-    for (int i = 0; i < JUNC_ITEMS; i++) {
-        run += w[i];
-        if (first + i < n) o[first + i] = run;
-    }
 }

@@ -26,32 +26,6 @@
 /* LDS of both passes (dynamic: a law of 100 bins leaves the occupancy alone): the workgroup's histogram, its scalars, the edges */
 __host__ __device__ inline size_t law_lds_bytes(int n_edges) { return (size_t)(n_edges - 1 + LAW_NS) * 8 + (size_t)n_edges * 4; }
 
-/* one 16-byte record per sub-fragment, one gather per contact endpoint: (dist, s_tot, contig, position in the genome order or -1:
- * the contig is not placed -- the map's position table with one position per pixel) */
-__global__ void k_law_records(Tables t, const int* __restrict__ pix, int M, int4* __restrict__ rec)
-{
-    const int s = blockIdx.x * blockDim.x + threadIdx.x;
-    if (s >= M) return;
-    rec[s] = make_int4(__float_as_int(t.dist[s]), __float_as_int(t.stot[s]), t.cp[s].x, pix[s]);
-}
-
-/* the same by POSITION r of the genome order (order[r] = sub-fragment): ds[r] = its dist, meta[r] = (first position of its contig,
- * sub-fragments of its contig; negated: a ring) */
-__global__ void k_law_sorted(Tables t, const int* __restrict__ order, int M, int T, float* __restrict__ ds, int2* __restrict__ meta)
-{
-    const int r = blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= T) return;
-    const int s = order[r];
-    if ((unsigned)s >= (unsigned)M) { /* (a position nobody wrote: an inconsistent state -- a contig of one, nothing read out of bounds) */
-        ds[r] = 0.0f;
-        meta[r] = make_int2(r, 1);
-        return;
-    }
-    const int len = t.len[s];
-    ds[r] = t.dist[s];
-    meta[r] = make_int2(r - t.cp[s].y, t.stot[s] != 0.0f ? -len : len);
-}
-
 /* edges[b] <= s < edges[b + 1]  <=>  b = (number of edges <= s) - 1: comparisons only */
 __device__ __forceinline__ int law_upper_bound(const float* e, int n_edges, float s)
 {

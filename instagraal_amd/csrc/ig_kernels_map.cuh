@@ -13,26 +13,6 @@
 #define MAP_THREADS 256
 #define MAP_TILE 32
 
-/* position r of sub-fragment s = first position of its contig (map_base of its bin, -1: the contig is not placed) + its rank inside
- * the contig, which is Tables.cp[s].y (k_fill_tables folds the orientation in); pixel = r / bin.  order (may be null): order[r] = s. */
-__global__ void k_map_pixels(const SubTab* __restrict__ sub, Tables t, const int* __restrict__ map_base, int M, int T, int bin,
-                             int* __restrict__ pix, int* __restrict__ order, int* __restrict__ err)
-{
-    const int s = blockIdx.x * blockDim.x + threadIdx.x;
-    if (s >= M) return;
-    const int base = map_base[sub[s].parent];
-    int p = -1;
-    if (base >= 0) {
-        const int r = base + t.cp[s].y;
-        if ((unsigned)r < (unsigned)T) {
-            if (order) order[r] = s;
-            p = r / bin;
-        } else
-            atomicOr(err, 1); /* the tables and the state disagree: reported by the host, nothing is written out of bounds */
-    }
-    pix[s] = p;
-}
-
 /* One pass over the contacts (row of contact k: crow[k]; column and count: cc[k]; row-major sorted).
  *
  * COMBINE = false, the yardstick: one atomic per contact END -- image[pi][pj] and image[pj][pi] (pi == pj: twice into that pixel).

@@ -8,7 +8,7 @@
  * JOIN_RING, 0).
  * The profile: k_place_emit is the counting sort of k_join_emit with two emissions per counted contact, entry = (row: the bin of
  * one end, word: the ORIGINAL position of the other end << 32 | count); the rows are sorted and the equal columns summed by the
- * kernels of ig_kernels_lift.cuh on this feature's own buffers, and the 64-bit scan of the junction profile turns the summed counts
+ * kernels of ig_kernels_rows.cuh on this feature's own buffers, and the 64-bit scan there turns the summed counts
  * into exclusive prefix sums: a window sum is two binary searches and one subtraction.
  * The scan: k_place_scan<G>, the segmented sliding-window pass over the sorted sparse rows.  The shift from the original positions
  * to the guest's reduced order is monotone and is applied here (place_bound).  Not every site is visited: only the ends of the
@@ -104,11 +104,7 @@ __global__ void __launch_bounds__(PLACE_THREADS) k_place_emit(const int* __restr
     if (r_within) atomicAdd(&sc[PLACE_WITHIN_OBS], r_within);
     if (r_counted) atomicAdd(&sc[PLACE_COUNTED_OBS], r_counted);
     if (r_ent) atomicAdd(&sc[PLACE_ENTRIES], r_ent);
-    __syncthreads();
-    if (threadIdx.x < PLACE_NS) {
-        const unsigned long long v = sc[threadIdx.x];
-        if (v) atomicAdd(&out_sc[threadIdx.x], v);
-    }
+    rows_flush<PLACE_NS>(sc, out_sc);
 }
 
 /* a guest's row and what the rule needs of the guest */

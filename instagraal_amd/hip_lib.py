@@ -18,7 +18,7 @@ SRC = os.path.join(HERE, "csrc", "ig_hip.hip")
 SRC_HOST = os.path.join(HERE, "csrc", "ig_draw.cpp")  # host-only part: the candidate draw
 DEPS = [SRC, SRC_HOST] + [os.path.join(HERE, "csrc", f) for f in ("ig_ops.cuh", "ig_common.cuh", "ig_model.cuh", "ig_kernels_setup.cuh",
                                                           "ig_kernels_score.cuh", "ig_kernels_screen.cuh", "ig_kernels_commit.cuh",
-                                                          "ig_kernels_nuis.cuh", "ig_kernels_map.cuh", "ig_kernels_law.cuh", "ig_kernels_junc.cuh", "ig_kernels_lift.cuh", "ig_kernels_join.cuh", "ig_kernels_emap.cuh", "ig_kernels_place.cuh", "ig_host_core.inc", "ig_host_upload.inc",
+                                                          "ig_kernels_nuis.cuh", "ig_kernels_genome.cuh", "ig_kernels_rows.cuh", "ig_kernels_map.cuh", "ig_kernels_law.cuh", "ig_kernels_junc.cuh", "ig_kernels_lift.cuh", "ig_kernels_join.cuh", "ig_kernels_emap.cuh", "ig_kernels_place.cuh", "ig_host_core.inc", "ig_host_upload.inc", "ig_host_genome.inc", "ig_host_rows.inc",
                                                           "ig_host_map.inc", "ig_host_law.inc", "ig_host_junc.inc", "ig_host_lift.inc", "ig_host_join.inc", "ig_host_emap.inc", "ig_host_place.inc",
                                                           "ig_host_batch.inc", "ig_host_nuis.inc", "ig_host_debug.inc")] + \
        [os.path.join(ROOT, "include", f) for f in ("ig_detmath.h", "ig_detmath_tables.h", "instagraal_hip.h")]

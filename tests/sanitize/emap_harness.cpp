@@ -118,7 +118,7 @@ static int run(ig_ctx* c, int max_side, int64_t cap, Out& o)
 int main()
 {
     fake_hip::set_model("k_emap_count", model_count);
-    fake_hip::set_model("k_junc_scan_apply", model_scan_apply);
+    fake_hip::set_model("k_scan64_apply", model_scan_apply);
     fake_hip::set_model("k_emap_rows", model_rows);
     fake_hip::set_model("k_emap_list", model_list);
     fake_hip::set_model("k_emap_tilesILb1E", model_tiles<true>);

@@ -1,6 +1,6 @@
 // AddressSanitizer / UBSan / LeakSanitizer harness for the HOST logic of the placement support (csrc/ig_host_place.inc) with the records
 // it shares with the join support (join_enqueue_records in csrc/ig_host_join.inc) and the sort and reduction it shares with the contacts
-// in genome coordinates (csrc/ig_host_lift.inc): a stand-alone program on the fake HIP runtime (fake_hip_runtime.cpp: device memory is
+// in genome coordinates (csrc/ig_host_rows.inc): a stand-alone program on the fake HIP runtime (fake_hip_runtime.cpp: device memory is
 // the heap, so every copy, fill and model write is checked against the real allocation sizes).  The models below script what steers the
 // host -- the number of contigs, the entries per row, the work lists of the three sort forms, the heads, the sum of the counts -- with
 // protocol-conforming values; the sums mean nothing here, memory safety, the sizes of the buffers against the work lists, that nothing
@@ -26,7 +26,7 @@
     } while (0)
 
 typedef unsigned long long u64;
-// mirrors of the device structs (ig_kernels_lift.cuh, ig_kernels_join.cuh: device code, not included here)
+// mirrors of the device structs (ig_kernels_rows.cuh, ig_kernels_join.cuh: device code, not included here)
 struct Item {
     long long off;
     int len, pad;
@@ -262,7 +262,7 @@ static int call_and_read(ig_ctx* c, int window, int min_hosts, int N, long long 
 int main()
 {
     fake_hip::set_model("k_join_heads", model_heads);
-    fake_hip::set_model("k_junc_scan_apply", model_scan_apply);
+    fake_hip::set_model("k_scan64_apply", model_scan_apply);
     fake_hip::set_model("k_join_ends", model_ends);
     fake_hip::set_model("k_join_records", model_records);
     fake_hip::set_model("k_place_bins", model_bins);
