@@ -389,6 +389,36 @@ int ig_placement_support(ig_ctx* ctx, int32_t window, int32_t min_hosts, int32_t
                          int32_t* second_offset, int32_t* second_hosts, int64_t* home_left, int64_t* home_right, int64_t* best_left,
                          int64_t* best_right, int64_t* second_left, int64_t* second_right, int64_t scalars[7]);
 
+/* ---- orientation support: which segments the contacts would reverse (no reference counterpart; the rule:
+ * instagraal_amd/orientation_support.py) ------------------------------------------------------------------------------------------
+ * Positions: the contact map's, 0 .. T - 1 (ig_contact_map_order).  The caller gives n_seg SEGMENTS [seg_first[k], seg_last[k]] of
+ * positions, ascending, disjoint, each inside one placed contig; they need not cover the order.  With n = last - first + 1 a
+ * segment's ARM is m = min(n / 2, window) -- the left arm [first, first + m - 1], the right arm [last - m + 1, last] -- and its
+ * FLANKS are the up to `window` (1 .. 1024) positions of its contig on either side.
+ * geometry[k] = {status, arm, left_flank, right_flank}; status, the first that fits: 1 fewer than two positions, 2 on a ring, 3 both
+ * flanks empty, 0 judged.  arm and flanks are 0 on a ring.  The rows of observed and expected_q of a segment that is not judged are 0.
+ * observed[k] = {LL, LR, RL, RR} (arm, flank): a contact with both ends placed in one linear contig at positions pa < pb, in the
+ * segments sa and sb (-1: none), sa != sb or both -1, counts its lower end for sa if sa is judged and pb - last[sa] <= window -- to LR
+ * if pa is in the left arm, to RR if in the right arm -- and its upper end for sb if sb is judged and first[sb] - pa <= window -- to LL
+ * if pb is in the left arm, to RL if in the right arm.  keep = LL + RR, flip = LR + RL; reversing the segment swaps LL with RL and LR
+ * with RR exactly.
+ * expected_q[k] = {keep, flip} (model != 0; NULL allowed iff model == 0): the sum over the m * (left_flank + right_flank) pairs (arm
+ * position, flank position) of each class of the model's value at s = fabsf(dist_i - dist_k) under parameter set 0, quantised, in
+ * units of 2^-32 (the junction profile's q).
+ * scalars: every contact in the first class it fits {0 unplaced, 1 trans, 2 ring, 3 within_segment (sa == sb >= 0), 4 counted (a
+ * quadrant took it), 5 uncounted}, then {6 entries_observed = the sum of all quadrants, 7 n_judged}.  [0] + .. + [5] = the sum of all
+ * counts; [4] <= [6] <= 2 [4].  64-bit integer sums: exact, the same from run to run, whatever the launch shapes.
+ * Fails, with nothing written and the handle usable: a NULL output, a window out of range, a malformed list ("segment list ..."),
+ * and a parameter set under which the largest quantised model value times 2 window^2 reaches 2^62 ("model value too large for this
+ * window").  n_seg == 0 is no error: every linear cis contact is uncounted.
+ * Guards and effects as ig_contact_map: reads the CURRENT coordinates, changes nothing a move reads, synchronous, an error while a
+ * nuisance step or a chain is in flight.  A sharded handle (ig_set_shard) adds its shard's rows to observed and the class scalars
+ * -- the ranks' results sum to the whole -- and computes geometry and expected_q whole.  Device memory: 4 bytes per sub-fragment and
+ * 100 bytes per segment, kept from call to call. */
+int ig_orientation_support(ig_ctx* ctx, int32_t window, int32_t model, int32_t n_seg, const int32_t* seg_first, const int32_t* seg_last,
+                           int32_t* geometry /*[n_seg][4]: status, arm, left_flank, right_flank*/, int64_t* observed /*[n_seg][4]*/,
+                           int64_t* expected_q /*[n_seg][2], NULL allowed iff model==0*/, int64_t* scalars /*[8]*/, int32_t* n_placed);
+
 /* ---- multi-GPU (contact shards) -------------------------- */
 /* Two-phase move: partial sums over this handle's contact shard are left in a device buffer of
  * ig_partials_count() int64 values; the caller all-reduces (SUM) it across ranks, then finishes. */
@@ -512,6 +542,13 @@ int ig_debug_placement_support_forms(ig_ctx* ctx, int64_t out8[8]);
 /* the call n times, hipEvents around each pass: ms_n[n][10] = {records, count, rows, scatter, sort short, sort lds, sort long, reduce,
  * prefix, scan}; *checksum (may be NULL): the arrays of the last call, each word weighted by its place: every form must agree on it */
 int ig_debug_placement_support_time(ig_ctx* ctx, int32_t window, int32_t min_hosts, int32_t n, float* ms_n, int64_t* checksum);
+/* orientation support: one pass n times, hipEvents around each (zero + kernel): ms_n[n].  pass 0, the observed pass -- form 0: one
+ * atomic per counted end (the yardstick), 1: equal row ends summed inside the wave first; pass 1, the model pass -- form 0: as
+ * shipped (a wave per segment of up to ORIENT_WAVE_PAIRS terms, a workgroup beyond), 1: a wave per segment, 2: a workgroup per
+ * judged segment.  *checksum (may be NULL): the words the last pass wrote (pass 0: the quadrants and the seven scalars; pass 1:
+ * expected_q), each weighted by its place: every form of a pass must agree on it */
+int ig_debug_orientation_support_time(ig_ctx* ctx, int32_t window, int32_t n_seg, const int32_t* seg_first, const int32_t* seg_last, int32_t pass,
+                                      int32_t form, int32_t n, float* ms_n, int64_t* checksum);
 #ifdef __cplusplus
 }
 #endif

@@ -467,6 +467,21 @@ struct EmapBuf {
     int form = 0; /* ig_debug_expected_map_form: 0 the form the library ships (EMAP_TILE_MIN_BIN), 1 rows, 2 tiles, 3 tiles without the constant shortcut */
 };
 
+/* orientation support (ig_kernels_orient.cuh): buffers kept from call to call -- seg sized for M, the per-segment arrays grown to the
+ * longest list seen (cap); freed by free_orient_buffers (ig_host_orient.inc) */
+struct OrientBuf {
+    int* seg = nullptr;                  /* [M] the segment of every position, -1: none */
+    int *first = nullptr, *last = nullptr; /* [cap] the caller's list */
+    int4* geo = nullptr;                 /* [cap] (status, arm, left flank, right flank) */
+    int4* bnd = nullptr;                 /* [cap] (first, last, arm of a judged segment or 0, 0) */
+    int* large = nullptr;                /* [cap] the segments the model pass gives a workgroup */
+    unsigned long long* obs = nullptr;   /* [cap][4] LL, LR, RL, RR */
+    unsigned long long* expq = nullptr;  /* [cap][2] keep, flip */
+    unsigned long long* sc = nullptr;    /* ORIENT_NS scalars */
+    int* ctl = nullptr;                  /* 2 words: ORIENT_CTL_* */
+    int M = 0, cap = 0;
+};
+
 struct ig_ctx {
     int device;
     hipStream_t stream;
@@ -577,6 +592,7 @@ struct ig_ctx {
     JoinBuf join;
     EmapBuf emap;
     PlaceBuf place;
+    OrientBuf orient;
     int* batch_out; /* committed moves, pending slot, (unused), candidates, predicted deltas used, contigs */
     int *host_bo, *host_bo_dev; /* the same in mapped host memory (+ [7] = sequence number of the decide launch), and its device address */
     int bo_seq;

@@ -117,18 +117,23 @@ static int check_window(const char* who, int window)
     return 0;
 }
 
-/* the overflow guard of a model pass (k_junc_model, k_join_model) that left the largest |quantised value| it saw in *d_maxq: a
- * junction or a link adds at most w (w + 1) / 2 values of at most max_q.  Waits for the stream. */
-static int check_model_sum(ig_ctx* c, const char* who, const unsigned long long* d_maxq, int window)
+/* the overflow guard of a model pass that left the largest |quantised value| it saw in *d_maxq and adds at most n_values of them into
+ * one word.  Waits for the stream. */
+static int check_model_values(ig_ctx* c, const char* who, const unsigned long long* d_maxq, unsigned long long n_values)
 {
     unsigned long long max_q = 0;
     HIPCK(hipMemcpyAsync(&max_q, d_maxq, sizeof(max_q), hipMemcpyDeviceToHost, c->stream));
     HIPCK(hipStreamSynchronize(c->stream));
-    const unsigned long long n = (unsigned long long)window * (unsigned long long)(window + 1) / 2; /* < 2^20 */
-    if (max_q > ((1ull << 62) - 1) / n) /* max_q * n >= 2^62 */
+    if (max_q > ((1ull << 62) - 1) / n_values) /* max_q * n_values >= 2^62 */
         return fail("%s: model value too large for this window (the largest value, %.6g, times %llu pairs does not fit the 64-bit sum)", who,
-                    (double)max_q / IG_QSCALE, n);
+                    (double)max_q / IG_QSCALE, n_values);
     return 0;
+}
+
+/* ... of k_junc_model and k_join_model: a junction or a link adds at most w (w + 1) / 2 values (< 2^20) */
+static int check_model_sum(ig_ctx* c, const char* who, const unsigned long long* d_maxq, int window)
+{
+    return check_model_values(c, who, d_maxq, (unsigned long long)window * (unsigned long long)(window + 1) / 2);
 }
 
 /* n repetitions of enqueue() -- launches on the library's stream, non-zero: stop -- between two events, waited for each: the

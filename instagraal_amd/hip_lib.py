@@ -18,8 +18,8 @@ SRC = os.path.join(HERE, "csrc", "ig_hip.hip")
 SRC_HOST = os.path.join(HERE, "csrc", "ig_draw.cpp")  # host-only part: the candidate draw
 DEPS = [SRC, SRC_HOST] + [os.path.join(HERE, "csrc", f) for f in ("ig_ops.cuh", "ig_common.cuh", "ig_model.cuh", "ig_kernels_setup.cuh",
                                                           "ig_kernels_score.cuh", "ig_kernels_screen.cuh", "ig_kernels_commit.cuh",
-                                                          "ig_kernels_nuis.cuh", "ig_kernels_genome.cuh", "ig_kernels_rows.cuh", "ig_kernels_map.cuh", "ig_kernels_law.cuh", "ig_kernels_junc.cuh", "ig_kernels_lift.cuh", "ig_kernels_join.cuh", "ig_kernels_emap.cuh", "ig_kernels_place.cuh", "ig_host_core.inc", "ig_host_upload.inc", "ig_host_genome.inc", "ig_host_rows.inc",
-                                                          "ig_host_map.inc", "ig_host_law.inc", "ig_host_junc.inc", "ig_host_lift.inc", "ig_host_join.inc", "ig_host_emap.inc", "ig_host_place.inc",
+                                                          "ig_kernels_nuis.cuh", "ig_kernels_genome.cuh", "ig_kernels_rows.cuh", "ig_kernels_map.cuh", "ig_kernels_law.cuh", "ig_kernels_junc.cuh", "ig_kernels_lift.cuh", "ig_kernels_join.cuh", "ig_kernels_emap.cuh", "ig_kernels_place.cuh", "ig_kernels_orient.cuh", "ig_host_core.inc", "ig_host_upload.inc", "ig_host_genome.inc", "ig_host_rows.inc",
+                                                          "ig_host_map.inc", "ig_host_law.inc", "ig_host_junc.inc", "ig_host_lift.inc", "ig_host_join.inc", "ig_host_emap.inc", "ig_host_place.inc", "ig_host_orient.inc",
                                                           "ig_host_batch.inc", "ig_host_nuis.inc", "ig_host_debug.inc")] + \
        [os.path.join(ROOT, "include", f) for f in ("ig_detmath.h", "ig_detmath_tables.h", "instagraal_hip.h")]
 
@@ -28,6 +28,8 @@ ASSEMBLY_CONTACTS_PASSES = ("count", "scan", "scatter", "sort_short", "sort_lds"
 JOIN_SUPPORT_PASSES = ("ends", "count", "scan", "scatter", "sort_short", "sort_lds", "sort_long", "reduce", "model")  # ig_debug_join_support_time
 PLACEMENT_SUPPORT_PASSES = ("records", "count", "rows", "scatter", "sort_short", "sort_lds", "sort_long", "reduce", "prefix", "scan")  # ig_debug_placement_support_time
 PLACEMENT_SUPPORT_FORMS = ("default", "thread", "wave")  # ig_debug_placement_support_form
+ORIENTATION_SUPPORT_WAVE_PAIRS = 4096  # ORIENT_WAVE_PAIRS (csrc/ig_kernels_orient.cuh): 2 * pairs beyond this take a workgroup in the model pass
+ORIENTATION_SUPPORT_FORMS = {"observed": ("atomic", "combined"), "model": ("default", "wave", "workgroup")}  # ig_debug_orientation_support_time: pass -> forms
 MAX_CANDIDATES = 16
 
 FRAG_FIELDS = ("pos", "sub_pos", "id_c", "start_bp", "len_bp", "sub_len", "circ", "id", "prev", "next", "l_cont",
@@ -860,6 +862,48 @@ class Context:
         ms = np.zeros((int(n), len(JOIN_SUPPORT_PASSES)), np.float32)
         ck = C.c_int64()
         _ck(lib().ig_debug_join_support_time(self._h, C.c_int32(int(window)), C.c_int32(int(n)), _p(ms), C.byref(ck)))
+        return ms, int(ck.value)
+
+    # ---- orientation support: which segments the contacts would reverse (the rule: orientation_support.py)
+    @staticmethod
+    def _segments(first, last):
+        f, l = np.asarray(first), np.asarray(last)
+        if f.ndim != 1 or f.shape != l.shape or not (np.issubdtype(f.dtype, np.integer) and np.issubdtype(l.dtype, np.integer)):
+            raise HipError("orientation_support: segment list: first and last are integer vectors of one length")
+        if f.size and (min(f.min(), l.min()) < -2 ** 31 or max(f.max(), l.max()) >= 2 ** 31):
+            raise HipError("orientation_support: segment list out of range")
+        return np.ascontiguousarray(f, np.int32), np.ascontiguousarray(l, np.int32)
+
+    def orientation_support(self, window, first, last, model=True):
+        """the contacts between the arms and the flanks of the segments [first[k], last[k]] of positions, and what the model expects
+        of the pairs that keep and that would flip each -> dict: window, n_placed, n_seg, first, last, geometry (int32 [n_seg, 4]:
+        status, arm, left_flank, right_flank), observed (int64 [n_seg, 4]: LL, LR, RL, RR), expected_q (int64 [n_seg, 2]: keep,
+        flip; None with ``model=False``) and the int64 scalars of ``orientation_support.SCALARS``"""
+        from .orientation_support import SCALARS
+
+        f, l = self._segments(first, last)
+        n_seg = int(f.size)
+        geo = np.zeros((n_seg, 4), np.int32)
+        obs = np.zeros((n_seg, 4), np.int64)
+        exq = np.zeros((n_seg, 2), np.int64) if model else None
+        sc = np.zeros(8, np.int64)
+        n = C.c_int32()
+        _ck(lib().ig_orientation_support(self._h, C.c_int32(int(window)), C.c_int32(int(bool(model))), C.c_int32(n_seg), _p(f), _p(l), _p(geo), _p(obs), _p(exq),
+                                         _p(sc), C.byref(n)))
+        out = dict(window=int(window), n_placed=n.value, n_seg=n_seg, first=f.astype(np.int64), last=l.astype(np.int64), geometry=geo, observed=obs, expected_q=exq)
+        out.update((k, int(v)) for k, v in zip(SCALARS, sc))
+        return out
+
+    def debug_orientation_support_time(self, window, first, last, which="observed", form=None, n=1):
+        """one pass of the orientation support n times with hipEvents around each -> (ms [n], checksum of what the last pass wrote).
+        ``which``: "observed" (``form``: "atomic", the yardstick, or "combined") or "model" ("default", "wave", "workgroup")"""
+        forms = ORIENTATION_SUPPORT_FORMS[which]
+        f, l = self._segments(first, last)
+        ms = np.zeros(int(n), np.float32)
+        ck = C.c_int64()
+        _ck(lib().ig_debug_orientation_support_time(self._h, C.c_int32(int(window)), C.c_int32(int(f.size)), _p(f), _p(l),
+                                                    C.c_int32(("observed", "model").index(which)), C.c_int32(forms.index(forms[0] if form is None else form)),
+                                                    C.c_int32(int(n)), _p(ms), C.byref(ck)))
         return ms, int(ck.value)
 
     # ---- placement support: where the contacts say each bin belongs (the rule: placement_support.py)

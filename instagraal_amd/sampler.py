@@ -186,6 +186,9 @@ class sampler:  # noqa: N801 - the reference's class name
         self.np_init_orientable = np.array([np_sub_frags_id[S_o_A_frags["id_d"][i]]["w"] > 1 for i in range(N)],
                                            dtype=np.int32)
         self.np_init_ori = np.ones(N, dtype=np.int32)
+        # the initial contig and position of every bin: what orientation_support's blocks are co-linear with (orientation_support.py)
+        self.np_init_id_c = np.copy(S_o_A_frags["id_c"])
+        self.np_init_pos = np.copy(S_o_A_frags["pos"])
         self.ctx.set_initial_genome(self.np_init_prev, self.np_init_next, self.np_init_orientable, self.id_frags_blacklisted)
         self.gpu_vect_frags = DeviceFrags(self.ctx)
         self.setup_distri_frags()
@@ -1068,6 +1071,56 @@ class sampler:  # noqa: N801 - the reference's class name
 
         res = self.placement_support(window, window_kb, min_hosts) if result is None else result
         return ps.misplaced_bins(res, n, min_ratio)
+
+    # ---------------------------------------------------- orientation support
+    def orientation_support(self, level="bin", segments=None, window=None, window_kb=None, model=True):
+        """Which segments of the current genome the contacts would reverse (``ig_orientation_support``; the rule:
+        ``orientation_support.py``): per segment the contacts between its two arms and the flanks on either side, in four quadrants,
+        and what the model in use expects of the pairs that keep and that would flip it.  ``level``: "bin", one segment per placed
+        bin, or "block", the maximal co-linear runs of bins of one initial contig (``orientation_support.block_segments``);
+        ``segments=(first, last)``: the caller's own intervals of positions, which override ``level``.  ``window``: in positions
+        (default 8), or ``window_kb``.  -> the device's dict (window, n_placed, n_seg, first, last, geometry, observed, expected_q,
+        the scalars) plus ``level``, ``status``, the derived columns (``keep``, ``flip``, ``pairs``, ``ratio``, ``z`` and with the
+        model ``expected_keep``, ``expected_flip``, ``llr``), the segments for people -- ``first_bin``, ``last_bin``, the bins at
+        their ends, and ``scaffold`` (the canonical id: ``assembly_contacts.scaffold_names`` names it) -- and ``order``.  No
+        reference counterpart."""
+        from . import orientation_support as osup
+
+        if window is not None and window_kb is not None:
+            raise ValueError("orientation_support: window or window_kb, not both")
+        if window_kb is not None:
+            window = osup.window_from_kb(window_kb, self.mean_kb())
+        w = osup.check_window(osup.DEFAULT_WINDOW if window is None else window)
+        order = self.ctx.contact_map_order().astype(np.int64)
+        parent = self.np_sub_frags_2_frags["x"].astype(np.int64)
+        g = self.gpu_vect_frags.copy_from_gpu()
+        if segments is not None:
+            first, last = (np.asarray(a) for a in segments)
+            level = "custom"
+        elif level == "bin":
+            seg = osup.bin_segments(order, parent)
+            first, last = seg["first"], seg["last"]
+        elif level == "block":
+            seg = osup.block_segments(order, parent, g.id_c, g.ori, g.id_d, self.np_init_id_c, self.np_init_pos)
+            first, last = seg["first"], seg["last"]
+        else:
+            raise ValueError("orientation_support: level is 'bin' or 'block' (got %r)" % (level,))
+        res = self.ctx.orientation_support(w, first, last, model=model)
+        res["level"], res["order"] = level, order
+        res["status"] = res["geometry"][:, 0].copy()
+        res.update(osup.derived(res))
+        at = parent[order]
+        res["first_bin"], res["last_bin"] = at[res["first"]], at[res["last"]]
+        res["scaffold"] = g.id_c.astype(np.int64)[res["first_bin"]]
+        return res
+
+    def inverted_segments(self, n=20, min_observed=0, result=None, level="bin", segments=None, window=None, window_kb=None, model=True):
+        """The ``n`` judged segments of ``orientation_support()`` with flip > keep, the most strongly reversed first
+        (``orientation_support.inverted_segments``: by llr, by z without the model; ties by segment index)."""
+        from . import orientation_support as osup
+
+        res = self.orientation_support(level, segments, window, window_kb, model) if result is None else result
+        return osup.inverted_segments(res, n, min_observed)
 
     # ----------------------------------------------------------- expected map
     def expected_map(self, max_side=2048):
