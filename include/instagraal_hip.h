@@ -515,6 +515,25 @@ int ig_debug_set_bin_active(ig_ctx* ctx, int32_t bin, int32_t active);
 /* the build n times, hipEvents around each pass: ms_n[n][7] = {count, scan, scatter, sort short, sort lds, sort long, reduce (level 1)};
  * the last result stays built; *checksum (may be NULL): its rows, columns and counts, each word weighted by its place */
 int ig_debug_assembly_contacts_time(ig_ctx* ctx, int32_t level, int32_t n, float* ms_n, int64_t* checksum);
+/* tests: the 64-bit scan of the reports (k_scan64_totals / _tops / _apply) over caller data, unchanged: the inclusive prefix sums,
+ * modulo 2^64, of the first n words of n_arrays arrays `stride` words apart (stride >= n).  in and out: n_arrays * stride words each;
+ * both go to the device, the scan runs from one buffer into the other, and BOTH come back: out with the sums (its words behind the
+ * n-th of every array as the caller left them), in as the device holds it behind the scan (unchanged, if the scan is right).  Needs
+ * a created handle, nothing uploaded. */
+int ig_debug_scan64(ig_ctx* ctx, uint64_t* in, int32_t n, int32_t n_arrays, int64_t stride, uint64_t* out);
+/* tests: the row builder of the reports (the counting sort into rows, the sort of every row in one of three forms and, reduce != 0,
+ * the sum of the runs of equal columns) over caller data, unchanged: entry k goes to row lo[k] (negative: no entry) as the word
+ * word[k] = column << 32 | count.  combine: as ig_debug_assembly_contacts_combine, of this call; the limits of
+ * ig_debug_assembly_contacts_limits hold.  *n_entries: the entries with a row; *n_out: the entries of the result (behind a reduction
+ * the distinct (row, column)); forms: as ig_debug_assembly_contacts_forms.  The result waits on the host for ig_debug_rows_fetch;
+ * nothing stays on the device.  Refused: negative n or n_rows, lo[k] >= n_rows, a column of 2^31 or more.  Needs a created handle,
+ * nothing uploaded: the sub-fragment table, the contacts and the state are not read. */
+int ig_debug_rows_build(ig_ctx* ctx, const int32_t* lo, const uint64_t* word, int64_t n, int32_t n_rows, int32_t reduce, int32_t combine,
+                        int64_t* n_entries, int64_t* n_out, int64_t forms[8]);
+/* the last ig_debug_rows_build's result: rowptr[n_rows + 1] (n_rowptr: the caller's capacity) and its n_out entries (capacity: the
+ * caller's) -- not reduced: word[n_out], sorted inside every row as unsigned 64-bit words (col and count are not written); reduced:
+ * col[n_out] and count[n_out] (word is not written) */
+int ig_debug_rows_fetch(ig_ctx* ctx, int64_t* rowptr, int64_t n_rowptr, uint64_t* word, int32_t* col, int64_t* count, int64_t capacity);
 /* join support: the form of the two passes over the contacts of THIS handle's builds: 1 a run of a wave's lanes with the same row
  * issues one atomic per emission, 0 one atomic per emission (the yardstick), negative: the form the library ships.  The result is
  * the same.  The limits of ig_debug_assembly_contacts_limits hold for this feature's sorts too. */

@@ -396,6 +396,14 @@ struct RowBuf {
     unsigned long long* out_cnt = nullptr; /* reduced: [n_out] */
 };
 
+/* the result of the last ig_debug_rows_build, on the host (ig_debug_rows_fetch): the build's own RowBuf is freed before it returns */
+struct DebugRows {
+    bool valid = false, reduced = false;
+    std::vector<long long> rowptr, count;
+    std::vector<unsigned long long> word;
+    std::vector<int> col;
+};
+
 /* the contacts in the coordinates of the current genome (ig_kernels_lift.cuh): work buffers kept from call to call, and the built
  * result (rows.rowptr and rows.ent or rows.out_col, rows.out_cnt): a snapshot that stays on the device until it is released */
 struct LiftBuf {
@@ -593,6 +601,7 @@ struct ig_ctx {
     EmapBuf emap;
     PlaceBuf place;
     OrientBuf orient;
+    DebugRows debug_rows;
     int* batch_out; /* committed moves, pending slot, (unused), candidates, predicted deltas used, contigs */
     int *host_bo, *host_bo_dev; /* the same in mapped host memory (+ [7] = sequence number of the decide launch), and its device address */
     int bo_seq;

@@ -366,3 +366,133 @@ extern "C" int ig_debug_pool_retries(ig_ctx* c, int64_t* n)
     *n = c->n_pool_retries;
     return 0;
 }
+
+/* ---- the shared layers of the reports on caller data (tests/test_hip_rows_direct.py): the 64-bit scan and the row builder, both
+ * unchanged.  Neither reads anything uploaded to the handle: a created handle is enough. */
+
+static int debug_scan64_impl(ig_ctx* c, uint64_t* in, int n, int n_arrays, long long stride, uint64_t* out, unsigned long long*& d_in,
+                             unsigned long long*& d_out, unsigned long long*& d_tot)
+{
+    const size_t words = (size_t)n_arrays * (size_t)stride;
+    DALLOC(d_in, words);
+    DALLOC(d_out, words);
+    DALLOC(d_tot, (size_t)n_arrays * scan_chunks(n));
+    HIPCK(hipMemcpyAsync(d_in, in, words * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
+    HIPCK(hipMemcpyAsync(d_out, out, words * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
+    scan64_enqueue(c, d_in, d_out, stride, n, n_arrays, d_tot);
+    HIPCK(hipMemcpyAsync(out, d_out, words * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCK(hipMemcpyAsync(in, d_in, words * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCK(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+extern "C" int ig_debug_scan64(ig_ctx* c, uint64_t* in, int32_t n, int32_t n_arrays, int64_t stride, uint64_t* out)
+{
+    IG_JOIN(c);
+    HIPCK(hipSetDevice(c->device));
+    if (!in || !out) return fail("ig_debug_scan64: NULL argument");
+    if (n < 1 || n_arrays < 1 || n_arrays > 65535 || stride < n || stride > (1ll << 31))
+        return fail("ig_debug_scan64: %d arrays of %d words, %lld apart: at least one word, at most 65535 arrays, a stride of n .. 2^31", n_arrays, n, (long long)stride);
+    if (c->nuis_in_flight || c->chain_busy) return fail("ig_debug_scan64: a nuisance step or a chain is in flight");
+    unsigned long long *d_in = nullptr, *d_out = nullptr, *d_tot = nullptr;
+    const int rc = debug_scan64_impl(c, in, n, n_arrays, stride, out, d_in, d_out, d_tot);
+    hipFree(d_in);
+    hipFree(d_out);
+    hipFree(d_tot);
+    return rc;
+}
+
+static int debug_rows_build_impl(ig_ctx* c, const char* who, RowBuf& r, const int32_t* lo, const uint64_t* word, long long n, int U, bool reduce, bool combine,
+                                 int*& d_lo, unsigned long long*& d_word, unsigned long long*& d_sc, long long forms[8], long long* n_entries, long long* n_out)
+{
+    DebugRows& d = c->debug_rows;
+    DALLOC(d_lo, (size_t)n);
+    DALLOC(d_word, (size_t)n);
+    DALLOC(d_sc, 1);
+    if (n > 0) {
+        HIPCK(hipMemcpyAsync(d_lo, lo, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+        HIPCK(hipMemcpyAsync(d_word, word, (size_t)n * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
+    }
+    HIPCK(hipMemsetAsync(d_sc, 0, sizeof(unsigned long long), c->stream));
+    auto emit = [&](bool scatter, unsigned long long* slots, unsigned long long* ent, unsigned long long n_ent) {
+        if (n == 0) return; /* no input: nothing to launch, the rows stay empty */
+        const dim3 grid(lift_blocks(n)), block(LIFT_THREADS);
+        if (!scatter && combine) hipLaunchKernelGGL((k_debug_rows_emit<false, true>), grid, block, 0, c->stream, d_lo, d_word, n, slots, ent, n_ent, d_sc);
+        else if (!scatter) hipLaunchKernelGGL((k_debug_rows_emit<false, false>), grid, block, 0, c->stream, d_lo, d_word, n, slots, ent, n_ent, d_sc);
+        else if (combine) hipLaunchKernelGGL((k_debug_rows_emit<true, true>), grid, block, 0, c->stream, d_lo, d_word, n, slots, ent, n_ent, d_sc);
+        else hipLaunchKernelGGL((k_debug_rows_emit<true, false>), grid, block, 0, c->stream, d_lo, d_word, n, slots, ent, n_ent, d_sc);
+    };
+    auto check = [&](long long E) { return E < 0 || E > n ? fail("%s: %lld entries of %lld (device error)", who, E, n) : 0; };
+    const RowsSpec spec = {d_sc, 1, 0, 0, "", reduce, {0, 0, 0, 0, 0}};
+    LiftTimer timer(c, nullptr, 0);
+    unsigned long long sc[1];
+    if (rows_build(c, who, r, U, spec, sc, check, emit, timer, forms, n_entries, n_out)) return -1;
+    HIPCK(hipStreamSynchronize(c->stream));
+    d.rowptr.assign((size_t)U + 1, 0);
+    HIPCK(hipMemcpy(d.rowptr.data(), r.rowptr, ((size_t)U + 1) * sizeof(long long), hipMemcpyDeviceToHost));
+    d.word.clear();
+    d.col.clear();
+    d.count.clear();
+    if (*n_out > 0 && reduce) {
+        d.col.resize((size_t)*n_out);
+        d.count.resize((size_t)*n_out);
+        HIPCK(hipMemcpy(d.col.data(), r.out_col, (size_t)*n_out * sizeof(int), hipMemcpyDeviceToHost));
+        HIPCK(hipMemcpy(d.count.data(), r.out_cnt, (size_t)*n_out * sizeof(long long), hipMemcpyDeviceToHost));
+    } else if (*n_out > 0) {
+        d.word.resize((size_t)*n_out);
+        HIPCK(hipMemcpy(d.word.data(), r.ent, (size_t)*n_out * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    }
+    d.reduced = reduce;
+    d.valid = true;
+    return 0;
+}
+
+extern "C" int ig_debug_rows_build(ig_ctx* c, const int32_t* lo, const uint64_t* word, int64_t n, int32_t n_rows, int32_t reduce, int32_t combine,
+                                   int64_t* n_entries, int64_t* n_out, int64_t forms[8])
+{
+    IG_JOIN(c);
+    HIPCK(hipSetDevice(c->device));
+    const char* who = "ig_debug_rows_build";
+    c->debug_rows.valid = false; /* whatever happens, the result of an earlier build is gone */
+    if (n < 0 || n_rows < 0) return fail("%s: %lld entries in %d rows: neither may be negative", who, (long long)n, n_rows);
+    if (!n_entries || !n_out || !forms || (n > 0 && (!lo || !word))) return fail("%s: NULL argument", who);
+    if (c->nuis_in_flight || c->chain_busy) return fail("%s: a nuisance step or a chain is in flight", who);
+    for (int64_t k = 0; k < n; k++) {
+        if (lo[k] >= n_rows) return fail("%s: entry %lld is of row %d, there are %d rows", who, (long long)k, lo[k], n_rows);
+        if (word[k] >> 63) return fail("%s: entry %lld has a column of 2^31 or more (word 0x%016llx)", who, (long long)k, (unsigned long long)word[k]);
+    }
+    RowBuf r;
+    int* d_lo = nullptr;
+    unsigned long long *d_word = nullptr, *d_sc = nullptr;
+    long long f[8], E = 0, K = 0;
+    const int rc = debug_rows_build_impl(c, who, r, lo, word, n, n_rows, reduce != 0, combine != 0, d_lo, d_word, d_sc, f, &E, &K);
+    hipStreamSynchronize(c->stream);
+    rows_free(r);
+    hipFree(d_lo);
+    hipFree(d_word);
+    hipFree(d_sc);
+    if (rc) return rc;
+    for (int k = 0; k < 8; k++) forms[k] = f[k];
+    *n_entries = E;
+    *n_out = K;
+    return 0;
+}
+
+extern "C" int ig_debug_rows_fetch(ig_ctx* c, int64_t* rowptr, int64_t n_rowptr, uint64_t* word, int32_t* col, int64_t* count, int64_t capacity)
+{
+    IG_JOIN(c);
+    const DebugRows& d = c->debug_rows;
+    if (!d.valid) return fail("ig_debug_rows_fetch: nothing is built (ig_debug_rows_build first)");
+    const size_t n_out = d.reduced ? d.col.size() : d.word.size();
+    if (!rowptr || n_rowptr < (int64_t)d.rowptr.size() || capacity < (int64_t)n_out)
+        return fail("ig_debug_rows_fetch: the result has %zu row words and %zu entries, the caller's capacities are %lld and %lld", d.rowptr.size(), n_out,
+                    (long long)n_rowptr, (long long)capacity);
+    if (n_out > 0 && (d.reduced ? !col || !count : !word)) return fail("ig_debug_rows_fetch: NULL output (the result is %s)", d.reduced ? "reduced" : "not reduced");
+    memcpy(rowptr, d.rowptr.data(), d.rowptr.size() * sizeof(int64_t));
+    if (d.reduced && n_out > 0) {
+        memcpy(col, d.col.data(), n_out * sizeof(int32_t));
+        memcpy(count, d.count.data(), n_out * sizeof(int64_t));
+    } else if (n_out > 0)
+        memcpy(word, d.word.data(), n_out * sizeof(uint64_t));
+    return 0;
+}

@@ -102,6 +102,7 @@ static int join_build_impl(ig_ctx* c, const char* who, int window, bool model, f
     /* the links */
     const bool combine = j.combine < 0 ? JOIN_SHIP_COMBINE != 0 : j.combine != 0;
     auto emit = [&](bool scatter, unsigned long long* slots, unsigned long long* ent, unsigned long long n_ent) {
+        if (c->Z == 0) return; /* no contacts: nothing to launch, the rows stay empty */
         const dim3 grid(lift_blocks(c->Z)), block(JOIN_THREADS);
         if (!scatter && combine)
             hipLaunchKernelGGL((k_join_emit<false, true>), grid, block, 0, c->stream, c->crow, c->cc, c->Z, j.rec, window, Ui, slots, ent, n_ent, j.sc, c->rank, c->world);

@@ -75,6 +75,7 @@ static int lift_build_impl(ig_ctx* c, const char* who, int level, float* ms)
     const int Ui = (int)U;
     HIPCK(hipMemsetAsync(l.sc, 0, LIFT_NS * sizeof(unsigned long long), c->stream));
     auto emit = [&](bool scatter, unsigned long long* slots, unsigned long long* ent, unsigned long long n_ent) {
+        if (c->Z == 0) return; /* no contacts: nothing to launch, the rows stay empty */
         const dim3 grid(lift_blocks(c->Z)), block(LIFT_THREADS);
         if (!scatter && l.no_combine)
             hipLaunchKernelGGL((k_lift_pass<false, false>), grid, block, 0, c->stream, c->crow, c->cc, c->Z, l.key, Ui, slots, ent, n_ent, l.sc, c->rank, c->world);

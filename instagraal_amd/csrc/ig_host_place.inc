@@ -66,6 +66,7 @@ static int place_impl(ig_ctx* c, const char* who, int window, int min_hosts, flo
     timer.end(PLACE_P_RECORDS);
     /* the profile */
     auto emit = [&](bool scatter, unsigned long long* slots, unsigned long long* ent, unsigned long long n_ent) {
+        if (c->Z == 0) return; /* no contacts: nothing to launch, the rows stay empty */
         const dim3 grid(lift_blocks(c->Z)), block(PLACE_THREADS);
         if (!scatter) hipLaunchKernelGGL((k_place_emit<false>), grid, block, 0, c->stream, c->crow, c->cc, c->Z, p.rec, c->sub_tab, N, slots, ent, n_ent, p.sc);
         else hipLaunchKernelGGL((k_place_emit<true>), grid, block, 0, c->stream, c->crow, c->cc, c->Z, p.rec, c->sub_tab, N, slots, ent, n_ent, p.sc);

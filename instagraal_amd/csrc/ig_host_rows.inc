@@ -236,8 +236,9 @@ struct RowsSpec {
 
 /* One build of rows into r, of a feature whose emit step is
  *   emit(bool scatter, unsigned long long* slots, unsigned long long* ent, unsigned long long n_ent)
- * which launches the feature's own kernel over the contacts: scatter = false, every entry counts for its row in slots[U + 2] (zeroed)
- * and the feature's scalars (spec.d_sc) are summed; scatter = true, slots hold the rows' cursors and every entry takes its place in
+ * which launches the feature's own kernel over its input (the contacts, for the reports; with an empty input it launches nothing:
+ * the input is the feature's, so is the gate): scatter = false, every entry counts for its row in slots[U + 2] (zeroed) and the
+ * feature's scalars (spec.d_sc) are summed; scatter = true, slots hold the rows' cursors and every entry takes its place in
  * ent[n_ent].
  * The sequence: count, the scan to the rows' starts, the feature's scalars to h_sc[spec.n_sc] and check(entries) -- the feature's
  * own refusals, non-zero: stop --, the free-memory guard, the scatter, the sort of the rows (under the limits of
@@ -258,7 +259,7 @@ static int rows_build(ig_ctx* c, const char* who, RowBuf& r, int U, const RowsSp
     /* count */
     timer.begin();
     HIPCK(hipMemsetAsync(r.count, 0, ((size_t)U + 2) * sizeof(unsigned long long), c->stream));
-    if (c->Z > 0) emit(false, r.count, nullptr, 0ull);
+    emit(false, r.count, nullptr, 0ull);
     timer.end(p.count);
     /* the rows' starts */
     timer.begin();

@@ -370,3 +370,38 @@ __global__ void __launch_bounds__(SCAN_THREADS) k_lift_reduce(const unsigned lon
         }
     }
 }
+
+/* ---- the tests' own emit kernel (ig_debug_rows_build): the row builder over caller data, shaped like k_lift_pass.  Entry k goes to
+ * row lo[k] (negative: no entry) as the word word[k]; the one scalar is the number of entries.  COMBINE = true: whole waves stay in
+ * the loop and take their slots through rows_slot; false: one atomic per entry. */
+template <bool SCATTER, bool COMBINE>
+__global__ void __launch_bounds__(LIFT_THREADS) k_debug_rows_emit(const int* __restrict__ row, const unsigned long long* __restrict__ word, long long n,
+                                                                  unsigned long long* __restrict__ counter, unsigned long long* __restrict__ ent,
+                                                                  unsigned long long n_ent, unsigned long long* __restrict__ out_sc)
+{
+    __shared__ unsigned long long sc[1];
+    if (!SCATTER) {
+        if (threadIdx.x < 1) sc[threadIdx.x] = 0ull;
+        __syncthreads();
+    }
+    const int lane = threadIdx.x & 63;
+    unsigned long long r_ent = 0;
+    const long long stride = (long long)gridDim.x * LIFT_THREADS;
+    const long long nr = COMBINE ? (n + 63) & ~63LL : n; /* whole waves stay in the loop together (the shuffles need every lane) */
+    for (long long k = (long long)blockIdx.x * LIFT_THREADS + threadIdx.x; k < nr; k += stride) {
+        int lo = -1;
+        if (k < n && row[k] >= 0) {
+            lo = row[k];
+            r_ent++;
+        }
+        unsigned long long slot = 0;
+        if (!COMBINE) {
+            if (lo >= 0) slot = atomicAdd(&counter[lo], 1ull);
+        } else
+            slot = rows_slot<SCATTER>(counter, lo, lane);
+        if (SCATTER && lo >= 0 && slot < n_ent) ent[slot] = word[k];
+    }
+    if (SCATTER) return;
+    if (r_ent) atomicAdd(&sc[0], r_ent);
+    rows_flush<1>(sc, out_sc);
+}

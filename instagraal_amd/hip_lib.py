@@ -813,6 +813,41 @@ class Context:
         _ck(lib().ig_debug_assembly_contacts_time(self._h, C.c_int32(LEVELS.index(level)), C.c_int32(int(n)), _p(ms), C.byref(ck)))
         return ms, int(ck.value)
 
+    # ---- the layers the reports share, over caller data (tests/test_hip_rows_direct.py)
+    def debug_scan64(self, words_2d, n, sentinel=0xA5A5A5A5A5A5A5A5):
+        """the reports' 64-bit scan over the first ``n`` words of every row of ``words_2d`` (uint64 [n_arrays, stride]) ->
+        (out uint64 [n_arrays, stride]: the inclusive prefix sums modulo 2^64, ``sentinel`` where nothing was written; the input as the
+        device holds it behind the scan)"""
+        words = np.ascontiguousarray(words_2d, np.uint64)
+        if words.ndim != 2:
+            raise HipError("debug_scan64: the words are an array of [n_arrays, stride]")
+        after = words.copy()
+        out = np.full(words.shape, sentinel, np.uint64)
+        _ck(lib().ig_debug_scan64(self._h, _p(after), C.c_int32(int(n)), C.c_int32(words.shape[0]), C.c_int64(words.shape[1]), _p(out)))
+        return out, after
+
+    def debug_rows_build(self, lo, word, n_rows, reduce=False, combine=True):
+        """the reports' row builder over caller data: entry k goes to row ``lo[k]`` (negative: no entry) as ``word[k]`` = column << 32 |
+        count -> dict: n_entries, n_out, forms (as ``debug_assembly_contacts_forms``), rowptr (int64 [n_rows + 1]) and ``word``
+        (uint64 [n_out], sorted inside every row) or, reduced, ``col`` (int32 [n_out]) and ``count`` (int64 [n_out])"""
+        lo = np.ascontiguousarray(lo, np.int32)
+        word = np.ascontiguousarray(word, np.uint64)
+        if lo.ndim != 1 or lo.shape != word.shape:
+            raise HipError("debug_rows_build: lo and word are vectors of one length")
+        ne, no = C.c_int64(), C.c_int64()
+        o = np.zeros(8, np.int64)
+        _ck(lib().ig_debug_rows_build(self._h, _p(lo), _p(word), C.c_int64(lo.size), C.c_int32(int(n_rows)), C.c_int32(int(bool(reduce))),
+                                      C.c_int32(int(bool(combine))), C.byref(ne), C.byref(no), _p(o)))
+        out = dict(n_entries=int(ne.value), n_out=int(no.value), rowptr=np.zeros(int(n_rows) + 1, np.int64),
+                   forms=dict(short=(int(o[0]), int(o[1])), lds=(int(o[2]), int(o[3])), long=(int(o[4]), int(o[5])), runs=int(o[6]), longest=int(o[7])))
+        if reduce:
+            out["col"], out["count"] = np.zeros(out["n_out"], np.int32), np.zeros(out["n_out"], np.int64)
+        else:
+            out["word"] = np.zeros(out["n_out"], np.uint64)
+        _ck(lib().ig_debug_rows_fetch(self._h, _p(out["rowptr"]), C.c_int64(out["rowptr"].size), _p(out.get("word")), _p(out.get("col")), _p(out.get("count")),
+                                      C.c_int64(out["n_out"])))
+        return out
+
     # ---- join support: which scaffold ends the contacts would link (the rule: join_support.py)
     def join_support(self, window, model=True):
         """builds the links between the ends of the placed linear contigs inside ``window`` positions as a snapshot on the device

@@ -244,6 +244,48 @@ def test_every_sort_form_and_every_boundary_between_them():
     s.free_gpu()
 
 
+def test_cfg2_takes_the_long_form_at_the_default_caps_and_the_scans_carry_loop():
+    """5 000 bins, 14 900 sub-fragments, 2 000 000 contacts under the limits the library ships: more than 256 chunks of entries, so the
+    reduction's scan of the heads takes its carry loop twice, and, at bin level, rows longer than the 1 024 entries of the lds form:
+    the long form with whole runs, merge widths from 1 024 up and the copy-back step.
+    Which states have such rows is the data's business, so the rule says it and the device is held to the rule: the genome order
+    puts the contigs by their canonical ids (by length), not by bin number, and under it the longest raw row at bin level measures
+    1 000 on the fresh genome and 947 after 1 000 batch moves (34 rows of up to 1 085 under the order of the bin numbers); with every
+    bin a contig of its own it measures 1 071, with 30 rows beyond 1 024.  So the genome is bombed as a third state, and there the
+    long form must have run."""
+    import test_rows_rule_host as rule
+
+    prob, s = _sampler("cfg2", seed=21)
+    long_rows_seen = {}
+    try:
+        for state in ("fresh", "after batch moves", "bombed"):
+            if state == "after batch moves":
+                s.step_sampler_batch(np.random.permutation(prob.n_frags)[:1000], 5)
+            if state == "bombed":
+                s.bomb_the_genome()
+            _, position, unit = _host_inputs(s.ctx, prob)
+            for level in LEVELS:
+                want = _rule(s.ctx, prob, level)
+                key = position if level == "sub" else np.where(position >= 0, unit[np.maximum(position, 0)], -1)
+                a, b = key[prob.coo_row], key[prob.coo_col]
+                lengths = np.bincount(np.minimum(a, b)[(a >= 0) & (b >= 0)], minlength=want["n_units"])  # the rows before the reduction
+                assert int(lengths.sum()) == want["entries_kept"] > 256 * rule.SCAN_CHUNK
+                long_rows = lengths > rule.LDS_CAP
+                long_rows_seen[state, level] = int(long_rows.sum())
+                for combine in (False, True):
+                    s.ctx.debug_assembly_contacts_combine(combine)
+                    _assert_equal(_device(s.ctx, level), want, (state, level, combine))
+                    forms = s.ctx.debug_assembly_contacts_forms()
+                    print(state, level, "combine" if combine else "one atomic per contact", "longest raw row", int(lengths.max()), forms)
+                    assert forms == rule.forms_rule(lengths, (0, 0)), (state, level, combine)
+                    assert forms["long"] == (int(long_rows.sum()), int(lengths[long_rows].sum())), (state, level, combine)
+        assert long_rows_seen["bombed", "bin"] > 0, long_rows_seen  # (the forms above equal the rule's: the long form ran there)
+    finally:
+        s.ctx.debug_assembly_contacts_combine(True)
+        s.ctx.assembly_contacts_release()
+        s.free_gpu()
+
+
 def test_two_builds_agree_fetches_in_pieces_and_the_snapshot():
     from instagraal_amd import hip_lib
 
