@@ -568,6 +568,41 @@ int ig_debug_placement_support_time(ig_ctx* ctx, int32_t window, int32_t min_hos
  * expected_q), each weighted by its place: every form of a pass must agree on it */
 int ig_debug_orientation_support_time(ig_ctx* ctx, int32_t window, int32_t n_seg, const int32_t* seg_first, const int32_t* seg_last, int32_t pass,
                                       int32_t form, int32_t n, float* ms_n, int64_t* checksum);
+
+/* ---- balancing the contact map of the current genome: one weight per unit by iterative correction (the rule:
+ * instagraal_amd/balance.py).  The device reproduces the rule's arrays byte for byte. */
+/* The rows.  level: 0 the positions of the genome order, 1 the placed bins along it, 2 the pixels of ig_contact_map under max_side
+ * (read at level 2 only).  Every contact with both ends placed in units u != v, |u - v| >= ignore_diags (>= 1), gives the entries
+ * (u, v, c) and (v, u, c); rows sorted by column, equal columns summed.  scalars[8] = {unplaced_observed, within_observed,
+ * band_observed, kept_observed, entries, n_placed, n_units, entries_out}.  Needs all contacts on this handle and no chain or
+ * nuisance step in flight; refuses a unit whose counts sum to 2^53 or more.  The rows stay on the device until ig_balance_release
+ * (or the next build). */
+int ig_balance_build(ig_ctx* ctx, int32_t level, int32_t max_side, int32_t ignore_diags, int64_t* n_units, int64_t* n_entries, int64_t scalars[8]);
+/* rowptr[n_units + 1] (capacity: its words), and per unit its entries and the sum of their counts */
+int ig_balance_rows(ig_ctx* ctx, int64_t* rowptr, int64_t* nnz, int64_t* total, int64_t capacity);
+/* entries first .. first + n - 1 of the built rows */
+int ig_balance_fetch(ig_ctx* ctx, int64_t first, int64_t n, int32_t* col, int64_t* count);
+/* The iterations of the rule over the built rows from b0[n_units] (the caller's mask: 0.0 where a unit is masked): stops after the
+ * first iteration with variance < tol (tol = 0: never) or after max_iters.  b, marg_final: [n_units] (marg_final from the final b);
+ * variance[max_iters]: one word per iteration done, zero beyond; *converged: 1 / 0.  No unit-sized array crosses to the host inside
+ * the loop.  With no entry, or b0 zero everywhere, *n_iters = 0 and nothing is launched. */
+int ig_balance_run(ig_ctx* ctx, const double* b0, double tol, int32_t max_iters, double* b, double* marg_final, double* variance, int32_t* n_iters,
+                   int32_t* converged);
+int ig_balance_release(ig_ctx* ctx);
+/* the form of k_bal_marginals of THIS handle: 0 the form the library ships, 1 a wave per row (the yardstick), 2 packed (four rows of at
+ * most 16 entries share a wave).  The bytes are the same. */
+int ig_debug_balance_form(ig_ctx* ctx, int32_t form);
+/* the iterations ig_balance_run enqueues between two looks at the device's done flag (0: the default).  The results are the same. */
+int ig_debug_balance_group(ig_ctx* ctx, int32_t group);
+/* the ordered sum (balance.lane_sum) of every row of caller data in the handle's form: values[rowptr[n_rows]], rowptr[n_rows + 1]
+ * from 0 and non-decreasing, out[n_rows].  A created handle is enough. */
+int ig_debug_lane_sums(ig_ctx* ctx, const double* values, const int64_t* rowptr, int64_t n_rows, double* out);
+/* over the built rows, from b = 1 and in the handle's form, n times with hipEvents around each: what = 0 k_bal_marginals alone, 1 one
+ * whole iteration (marginals, mean, update, variance): ms_n[n] */
+int ig_debug_balance_time(ig_ctx* ctx, int32_t what, int32_t n, float* ms_n);
+/* the build n times, hipEvents around each pass: ms_n[n][8] = {units, count, rows, scatter, sort short, sort lds, sort long, reduce};
+ * the last build's rows stay */
+int ig_debug_balance_build_time(ig_ctx* ctx, int32_t level, int32_t max_side, int32_t ignore_diags, int32_t n, float* ms_n);
 #ifdef __cplusplus
 }
 #endif

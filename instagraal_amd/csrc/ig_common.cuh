@@ -462,6 +462,31 @@ struct PlaceBuf {
     int form = 0; /* ig_debug_placement_support_form: 0 the form the library ships (PLACE_WAVE_ENTRIES), 1 a thread per row, 2 a wave per row */
 };
 
+/* balancing (ig_kernels_bal.cuh): every buffer of the feature, freed by free_bal_buffers (ig_host_bal.inc) -- what a build needs (gone
+ * behind it), the built rows: a snapshot that stays on the device until it is released, and one run's vectors (gone behind the run) */
+struct BalBuf {
+    /* one build's */
+    int* key = nullptr;                  /* [M] unit of every sub-fragment, -1: not placed */
+    unsigned long long* head = nullptr;  /* [T + 1] level 1: 1 where the parent bin changes along the order */
+    unsigned long long* incl = nullptr;  /* [T + 1] ... and their running sum */
+    unsigned long long* htot = nullptr;  /* that scan's chunk totals */
+    unsigned long long* sc = nullptr;    /* BAL_NS scalars of the passes over the contacts */
+    unsigned long long* total = nullptr; /* [U] the kept counts per unit */
+    /* the snapshot: rows.rowptr [U + 1], rows.out_col and rows.out_cnt [n_entries], and the totals on the host */
+    RowBuf rows;
+    std::vector<long long> h_total;
+    bool valid = false;
+    int level = 0;
+    long long n_placed = 0, n_units = 0, n_entries = 0;
+    long long forms[8] = {0, 0, 0, 0, 0, 0, 0, 0}; /* the last build's LIFT_C_* words */
+    /* one run's */
+    double *b = nullptr, *marg = nullptr, *dd = nullptr, *var = nullptr; /* [U], [U], [U], [max_iters] */
+    struct BalCtl* ctl = nullptr;
+    /* the handle's settings */
+    int form = 0;  /* ig_debug_balance_form: 0 the form the library ships (BAL_SHIP_FORM), 1 a wave per row, 2 packed */
+    int group = 0; /* ig_debug_balance_group: iterations enqueued between two looks at the done flag, 0: BAL_GROUP */
+};
+
 /* the expected contact map of the current genome (ig_kernels_emap.cuh): every buffer of the feature, freed by free_emap_buffers
  * (ig_host_emap.inc) at the end of every call */
 struct EmapBuf {
@@ -600,6 +625,7 @@ struct ig_ctx {
     JoinBuf join;
     EmapBuf emap;
     PlaceBuf place;
+    BalBuf bal;
     OrientBuf orient;
     DebugRows debug_rows;
     int* batch_out; /* committed moves, pending slot, (unused), candidates, predicted deltas used, contigs */

@@ -18,8 +18,8 @@ SRC = os.path.join(HERE, "csrc", "ig_hip.hip")
 SRC_HOST = os.path.join(HERE, "csrc", "ig_draw.cpp")  # host-only part: the candidate draw
 DEPS = [SRC, SRC_HOST] + [os.path.join(HERE, "csrc", f) for f in ("ig_ops.cuh", "ig_common.cuh", "ig_model.cuh", "ig_kernels_setup.cuh",
                                                           "ig_kernels_score.cuh", "ig_kernels_screen.cuh", "ig_kernels_commit.cuh",
-                                                          "ig_kernels_nuis.cuh", "ig_kernels_genome.cuh", "ig_kernels_rows.cuh", "ig_kernels_map.cuh", "ig_kernels_law.cuh", "ig_kernels_junc.cuh", "ig_kernels_lift.cuh", "ig_kernels_join.cuh", "ig_kernels_emap.cuh", "ig_kernels_place.cuh", "ig_kernels_orient.cuh", "ig_host_core.inc", "ig_host_upload.inc", "ig_host_genome.inc", "ig_host_rows.inc",
-                                                          "ig_host_map.inc", "ig_host_law.inc", "ig_host_junc.inc", "ig_host_lift.inc", "ig_host_join.inc", "ig_host_emap.inc", "ig_host_place.inc", "ig_host_orient.inc",
+                                                          "ig_kernels_nuis.cuh", "ig_kernels_genome.cuh", "ig_kernels_rows.cuh", "ig_kernels_map.cuh", "ig_kernels_law.cuh", "ig_kernels_junc.cuh", "ig_kernels_lift.cuh", "ig_kernels_join.cuh", "ig_kernels_emap.cuh", "ig_kernels_place.cuh", "ig_kernels_orient.cuh", "ig_kernels_bal.cuh", "ig_host_core.inc", "ig_host_upload.inc", "ig_host_genome.inc", "ig_host_rows.inc",
+                                                          "ig_host_map.inc", "ig_host_law.inc", "ig_host_junc.inc", "ig_host_lift.inc", "ig_host_join.inc", "ig_host_emap.inc", "ig_host_place.inc", "ig_host_orient.inc", "ig_host_bal.inc",
                                                           "ig_host_batch.inc", "ig_host_nuis.inc", "ig_host_debug.inc")] + \
        [os.path.join(ROOT, "include", f) for f in ("ig_detmath.h", "ig_detmath_tables.h", "instagraal_hip.h")]
 
@@ -30,6 +30,8 @@ PLACEMENT_SUPPORT_PASSES = ("records", "count", "rows", "scatter", "sort_short",
 PLACEMENT_SUPPORT_FORMS = ("default", "thread", "wave")  # ig_debug_placement_support_form
 ORIENTATION_SUPPORT_WAVE_PAIRS = 4096  # ORIENT_WAVE_PAIRS (csrc/ig_kernels_orient.cuh): 2 * pairs beyond this take a workgroup in the model pass
 ORIENTATION_SUPPORT_FORMS = {"observed": ("atomic", "combined"), "model": ("default", "wave", "workgroup")}  # ig_debug_orientation_support_time: pass -> forms
+BALANCE_BUILD_PASSES = ("units", "count", "rows", "scatter", "sort_short", "sort_lds", "sort_long", "reduce")  # ig_debug_balance_build_time
+BALANCE_FORMS = ("default", "wave", "packed")  # ig_debug_balance_form
 MAX_CANDIDATES = 16
 
 FRAG_FIELDS = ("pos", "sub_pos", "id_c", "start_bp", "len_bp", "sub_len", "circ", "id", "prev", "next", "l_cont",
@@ -980,6 +982,78 @@ class Context:
         _ck(lib().ig_debug_placement_support_time(self._h, C.c_int32(int(window)), C.c_int32(int(window) if min_hosts is None else int(min_hosts)), C.c_int32(int(n)),
                                                   _p(ms), C.byref(ck)))
         return ms, int(ck.value)
+
+    # ---- balancing the contact map of the current genome (the rule: balance.py)
+    def balance_build(self, level="bin", max_side=2048, ignore_diags=2):
+        """builds the rows the balancing iterates over -- both entries (u, v), (v, u) of every kept contact, sorted, equal columns
+        summed -- as a snapshot on the device -> dict: level, rowptr (int64 [n_units + 1]), nnz and total (int64 [n_units]) and the
+        int64 scalars of ``balance.SCALARS``; the entries come through ``balance_fetch``"""
+        from .balance import LEVELS, SCALARS
+
+        lv = LEVELS.index(level) if level in LEVELS else int(level)
+        nu, ne = C.c_int64(), C.c_int64()
+        sc = np.zeros(8, np.int64)
+        _ck(lib().ig_balance_build(self._h, C.c_int32(lv), C.c_int32(int(max_side)), C.c_int32(int(ignore_diags)), C.byref(nu), C.byref(ne), _p(sc)))
+        U = int(nu.value)
+        rowptr, nnz, total = np.zeros(U + 1, np.int64), np.zeros(U, np.int64), np.zeros(U, np.int64)
+        _ck(lib().ig_balance_rows(self._h, _p(rowptr), _p(nnz), _p(total), C.c_int64(rowptr.size)))
+        out = dict(level=level, rowptr=rowptr, nnz=nnz, total=total)
+        out.update((k, int(v)) for k, v in zip(SCALARS, sc))
+        return out
+
+    def balance_fetch(self, first, n):
+        """entries first .. first + n - 1 of the built rows -> (col int32 [n], count int64 [n])"""
+        n = int(n)
+        col, cnt = np.zeros(max(n, 0), np.int32), np.zeros(max(n, 0), np.int64)
+        _ck(lib().ig_balance_fetch(self._h, C.c_int64(int(first)), C.c_int64(n), _p(col), _p(cnt)))
+        return col, cnt
+
+    def balance_run(self, b0, tol=1e-5, max_iters=200):
+        """the iterations of the rule over the built rows from ``b0`` (f64 per unit, 0.0 where masked) -> dict: b, marg_final (f64
+        per unit), variance (f64 [n_iters]), n_iters, converged"""
+        b0 = np.ascontiguousarray(b0, np.float64)
+        max_iters = int(max_iters)
+        b, marg = np.zeros(b0.size, np.float64), np.zeros(b0.size, np.float64)
+        var = np.zeros(max(max_iters, 1), np.float64)
+        n, conv = C.c_int32(), C.c_int32()
+        _ck(lib().ig_balance_run(self._h, _p(b0), C.c_double(float(tol)), C.c_int32(max_iters), _p(b), _p(marg), _p(var), C.byref(n), C.byref(conv)))
+        return dict(b=b, marg_final=marg, variance=var[:n.value].copy(), n_iters=int(n.value), converged=bool(conv.value))
+
+    def balance_release(self):
+        _ck(lib().ig_balance_release(self._h))
+
+    def debug_balance_form(self, form="default"):
+        """the marginals kernel: ``"wave"`` (a wave per row, the yardstick), ``"packed"`` (four rows of at most 16 entries share a
+        wave) or ``"default"`` (the form the library ships)"""
+        _ck(lib().ig_debug_balance_form(self._h, C.c_int32(BALANCE_FORMS.index(form))))
+
+    def debug_balance_group(self, group=0):
+        """the iterations ``balance_run`` enqueues between two looks at the device's done flag (0: the default)"""
+        _ck(lib().ig_debug_balance_group(self._h, C.c_int32(int(group))))
+
+    def debug_lane_sums(self, values, rowptr):
+        """the ordered sum (``balance.lane_sum``) of every row of caller data on the device, in the handle's form -> f64 [n_rows]"""
+        values = np.ascontiguousarray(values, np.float64)
+        rowptr = np.ascontiguousarray(rowptr, np.int64)
+        if rowptr.size < 2 or rowptr[-1] != values.size:
+            raise HipError("debug_lane_sums: rowptr has n_rows + 1 >= 2 words and ends at the number of values")
+        out = np.zeros(rowptr.size - 1, np.float64)
+        _ck(lib().ig_debug_lane_sums(self._h, _p(values), _p(rowptr), C.c_int64(rowptr.size - 1), _p(out)))
+        return out
+
+    def debug_balance_time(self, what="marginals", n=1):
+        """over the built rows, from b = 1: ``"marginals"`` (the kernel alone) or ``"iteration"`` n times, event-timed -> ms [n]"""
+        ms = np.zeros(int(n), np.float32)
+        _ck(lib().ig_debug_balance_time(self._h, C.c_int32(("marginals", "iteration").index(what)), C.c_int32(int(n)), _p(ms)))
+        return ms
+
+    def debug_balance_build_time(self, level="bin", max_side=2048, ignore_diags=2, n=1):
+        """the build n times with hipEvents around each pass -> ms [n, 8]: ``BALANCE_BUILD_PASSES``; the last build's rows stay"""
+        from .balance import LEVELS
+
+        ms = np.zeros((int(n), len(BALANCE_BUILD_PASSES)), np.float32)
+        _ck(lib().ig_debug_balance_build_time(self._h, C.c_int32(LEVELS.index(level)), C.c_int32(int(max_side)), C.c_int32(int(ignore_diags)), C.c_int32(int(n)), _p(ms)))
+        return ms
 
     # ---- bookkeeping
     def renumber_contigs(self):

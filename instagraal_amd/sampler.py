@@ -960,7 +960,7 @@ class sampler:  # noqa: N801 - the reference's class name
             total = int(diag.sum())
         return res, order, table, diag, total
 
-    def assembly_contacts(self, level="sub", diagonal=True):
+    def assembly_contacts(self, level="sub", diagonal=True, balance=False):
         """The contacts in the coordinates of the current genome (``ig_assembly_contacts_build``; the rule: ``assembly_contacts.py``):
         every contact re-indexed to the units of the genome order -- ``level="sub"``: the positions of the contact map, ``"bin"``:
         the placed bins -- and sorted, as CSR arrays.  -> dict: ``rowptr`` (int64 [n_units + 1]), ``col`` (int32), ``count`` (int64),
@@ -969,6 +969,8 @@ class sampler:  # noqa: N801 - the reference's class name
         ``chrom_sizes`` ((contig ids, sizes)).  The device holds the strict upper triangle only: with ``diagonal=True`` and a
         sampler that has ``sparse_matrix`` (not one built from ``coo=``) the diagonal of the symmetrised input is merged in here as
         entries (u, u), first in their rows, as ``contact_map`` adds it to its image; their total is ``contacts_diagonal``.
+        ``balance=True`` (or a dict of ``balance()``'s parameters): the dict gains ``weight`` (f64 per unit, ``balance(level)``) and
+        ``balanced`` (count * weight[row] * weight[col] per entry; nan where a unit has no weight).
         No reference counterpart on the device (post.py lifts the raw pairs over)."""
         from . import assembly_contacts as ac
 
@@ -980,12 +982,21 @@ class sampler:  # noqa: N801 - the reference's class name
             rowptr, col, count = ac.merge_diagonal(0, rowptr, col, count, diag)
         res.pop("n_entries")
         res.update(rowptr=rowptr, col=col, count=count, order=order, bins=table, chrom_sizes=ac.chrom_sizes(table), contacts_diagonal=total)
+        if balance:
+            from . import balance as bal
+
+            res["weight"] = self.balance(level=level, **(balance if isinstance(balance, dict) else {}))["weight"]
+            res["balanced"] = bal.balanced(count, ac.rows_of(rowptr), col, res["weight"])
         return res
 
-    def write_assembly_contacts(self, folder, level="sub", diagonal=True, block_rows=None):
+    def write_assembly_contacts(self, folder, level="sub", diagonal=True, block_rows=None, balance=False):
         """Writes ``bins.bed``, ``pixels.tsv`` and ``chrom.sizes`` into ``folder``: what ``cooler load -f coo bins.bed pixels.tsv``
-        takes.  The entries are fetched from the device and written by blocks of ``block_rows`` rows.  -> the scalars (plus
-        ``contacts_diagonal`` and ``pixels_written``)."""
+        takes.  The entries are fetched from the device and written by blocks of ``block_rows`` rows.  ``balance=True`` (or a dict
+        of ``balance()``'s parameters): ``weights.tsv`` beside them -- unit, scaffold, start, end, weight per line of ``bins.bed``
+        (``balance.write_weights``); the three other files are the same bytes.  -> the scalars (plus ``contacts_diagonal`` and
+        ``pixels_written``)."""
+        import os
+
         from . import assembly_contacts as ac
 
         res, _, table, diag, total = self._assembly_contacts_frame(level, diagonal)
@@ -995,7 +1006,68 @@ class sampler:  # noqa: N801 - the reference's class name
             self.ctx.assembly_contacts_release()
         out = {k: res[k] for k in ac.SCALARS}
         out.update(level=level, contacts_diagonal=total, pixels_written=n)
+        if balance:
+            from . import balance as bal
+
+            bal.write_weights(os.path.join(folder, "weights.tsv"), table, self.balance(level=level, **(balance if isinstance(balance, dict) else {})))
         return out
+
+    # ---------------------------------------------------------------- balance
+    def balance(self, level="bin", max_side=2048, ignore_diags=2, min_nnz=10, min_count=0, mad_max=0, tol=1e-5, max_iters=200):
+        """The balancing weights of the current genome's contact map (``ig_balance_build`` / ``ig_balance_run``; the rule:
+        ``balance.py``): one weight per unit -- ``level="sub"``: the positions of the genome order, ``"bin"``: the placed bins,
+        ``"map"``: the pixels of ``contact_map(max_side)`` -- such that count * weight[u] * weight[v] has equal row sums (iterative
+        correction, cooler's update).  Contacts inside a unit and closer than ``ignore_diags`` units are left out; a unit with fewer
+        than ``min_nnz`` partners, fewer than ``min_count`` contacts or (``mad_max`` > 0) a coverage ``mad_max`` median absolute
+        deviations below the median is masked (weight nan).  -> dict: ``weight``, ``b``, ``marg_final`` (f64 per unit), ``masked``,
+        ``nnz``, ``total``, ``rowptr``, ``variance`` (f64 per iteration), ``n_iters``, ``converged``, ``scale``, the scalars of
+        ``balance.SCALARS``, the parameters, ``order`` and ``bins`` (``assembly_contacts.bins_table``; None at level "map").  The rows and
+        the iterations stay on the device; the mask is made here.  No reference counterpart."""
+        from . import assembly_contacts as ac, balance as bal
+
+        bal.check_level(level)
+        d = bal.check_ignore_diags(ignore_diags)
+        tol, max_iters = bal.check_run(tol, max_iters)
+        res = self.ctx.balance_build(level, max_side, d)
+        try:
+            masked = bal.mask_units(res["nnz"], res["total"], min_nnz, min_count, mad_max)
+            res.update(self.ctx.balance_run(np.where(masked, 0.0, 1.0), tol, max_iters))
+        finally:
+            self.ctx.balance_release()
+        res["weight"], res["scale"] = bal.finish(res["b"], res["marg_final"], masked)
+        res.update(masked=masked, level=level, max_side=int(max_side), ignore_diags=d, min_nnz=int(min_nnz), min_count=int(min_count), mad_max=mad_max, tol=tol,
+                   max_iters=max_iters)
+        order = self.ctx.contact_map_order().astype(np.int64)
+        res["order"] = order
+        res["bins"] = None
+        if level != "map":
+            g = self.gpu_vect_frags.copy_from_gpu()
+            res["bins"] = ac.bins_table(order, self.np_sub_frags_2_frags["x"].astype(np.int64), g.id_c, g.ori, self.S_o_A_sub_frags["len_bp"], level)
+        return res
+
+    def balanced_map(self, max_side=2048, **kw):
+        """``contact_map(max_side)`` balanced: the image as float64 times the outer product of the weights of its pixels
+        (``balance(level="map", max_side=max_side, **kw)``); the rows and columns of masked pixels are nan -> (image f64 [side, side],
+        bin)"""
+        image, b = self.contact_map(max_side)
+        w = self.balance(level="map", max_side=max_side, **kw)["weight"]
+        return image.astype(np.float64) * np.outer(w, w), b
+
+    def display_balanced_matrix(self, filename, max_side=2048, **kw):
+        """Writes the picture of the balanced contact map of the current genome in the form of ``display_current_matrix`` (masked
+        pixels stay blank) and returns ``(image, bin)`` of ``balanced_map``."""
+        image, b = self.balanced_map(max_side, **kw)
+        from matplotlib.backends.backend_agg import FigureCanvasAgg
+        from matplotlib.figure import Figure
+
+        fig = Figure(figsize=(14, 14))
+        FigureCanvasAgg(fig)
+        ax = fig.subplots()
+        seen = image[np.isfinite(image)]
+        ax.imshow(image, vmax=np.percentile(seen, 99) if seen.size else None, interpolation="nearest")
+        ax.axis("off")
+        fig.savefig(filename, dpi=200, bbox_inches="tight")
+        return image, b
 
     # ----------------------------------------------------------- join support
     def join_support(self, window=None, window_kb=None):

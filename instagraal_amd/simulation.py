@@ -194,7 +194,7 @@ class instagraal_class:
         self.collect_id_fA_sampled.append(id_frag)
 
     def full_em(self, n_cycles, n_neighbours, bomb, id_start_sample_param, save_matrix=False, save_law=False, save_junctions=False,
-                save_contacts=False, save_joins=False, save_residuals=False, save_placements=False, save_orientations=False):  # IG:196-291
+                save_contacts=False, save_joins=False, save_residuals=False, save_placements=False, save_orientations=False, save_weights=False):  # IG:196-291
         sampler = self.simulation.sampler
         if bomb:
             sampler.bomb_the_genome()
@@ -256,6 +256,11 @@ class instagraal_class:
             from . import placement_support as psup
 
             psup.write_placements(self._out("placements.txt"), sampler.placement_support())
+        if save_weights:  # (once, behind the last cycle, beside placements.txt: the balancing weight of every bin of the final genome)
+            from . import balance as bal
+
+            res = sampler.balance(level="bin")
+            bal.write_weights(self._out("weights.txt"), res["bins"], res)
         if save_orientations:  # (once, behind the last cycle: the blocks, then the bins, the contacts would turn round)
             from . import orientation_support as osup
 
@@ -277,7 +282,7 @@ class instagraal_class:
 def run_instagraal(hic_folder, reference_fa, output_folder=None, level=4, cycles=100, coverage_std=1, neighborhood=5, device=0,
                    circular=False, bomb=False, pyramid_only=False, save_pickle=False, save_matrix=False, simple=False, save_law=False,
                    save_junctions=False, save_contacts=False, save_joins=False, save_residuals=False, save_placements=False,
-                   save_orientations=False):
+                   save_orientations=False, save_weights=False):
     """IG:502-581 (defaults of cli/main.py: level 4, 100 cycles, 5 neighbours, 1 std).  The three trailing switches of the
     reference's signature (IG:512-514) are accepted: ``save_pickle`` dumps the run object to ``graal.pkl`` as the reference
     tries to (IG:589-594: a warning when it cannot be pickled -- device handles here, h5py handles there); ``save_matrix``
@@ -303,7 +308,9 @@ def run_instagraal(hic_folder, reference_fa, output_folder=None, level=4, cycles
     (``sampler.placement_support``); ``save_orientations`` (an addition too) writes ``orientations.txt`` once, behind the
     last cycle: one line per judged segment -- the co-linear blocks first, the bins behind them -- with the contacts between its two
     ends and the positions on either side inside a window of 8 sub-fragments, split into those that keep it as it lies and those that
-    would reverse it (``sampler.orientation_support``)."""
+    would reverse it (``sampler.orientation_support``); ``save_weights`` (an addition too) writes ``weights.txt`` once, behind
+    the last cycle: one line per bin of the final genome with its scaffold, start, end and balancing weight -- the raw count of two bins
+    times their two weights is the balanced count (``sampler.balance``)."""
     import warnings
 
     if simple and not pyramid_only:
@@ -324,7 +331,7 @@ def run_instagraal(hic_folder, reference_fa, output_folder=None, level=4, cycles
         p2.simulation.level.S_o_A_frags["circ"] += 1
     p2.full_em(n_cycles=cycles, n_neighbours=neighborhood, bomb=bomb, id_start_sample_param=4, save_matrix=save_matrix, save_law=save_law,
                save_junctions=save_junctions, save_contacts=save_contacts, save_joins=save_joins, save_residuals=save_residuals, save_placements=save_placements,
-               save_orientations=save_orientations)
+               save_orientations=save_orientations, save_weights=save_weights)
     if save_pickle:  # IG:589-594
         import pickle
 
