@@ -603,6 +603,33 @@ int ig_debug_balance_time(ig_ctx* ctx, int32_t what, int32_t n, float* ms_n);
 /* the build n times, hipEvents around each pass: ms_n[n][8] = {units, count, rows, scatter, sort short, sort lds, sort long, reduce};
  * the last build's rows stay */
 int ig_debug_balance_build_time(ig_ctx* ctx, int32_t level, int32_t max_side, int32_t ignore_diags, int32_t n, float* ms_n);
+
+/* ---- gap support: the distance the contacts put across each join of the current genome (the rule: instagraal_amd/gap_support.py;
+ * DESIGN.md 4.20).  The device reproduces the rule's arrays byte for byte. */
+/* junction[n_junc] (n_junc >= 1): positions 1 .. T - 1 of the genome order, strictly ascending, each between two positions of one
+ * placed contig; anything else is an error of the whole call.  gaps_kb[n_gaps], 2 <= n_gaps <= 64: finite, strictly ascending,
+ * gaps_kb[0] == 0.  window: 1 .. 256 positions.  Per junction: status (0 judged, 2 on a ring: its row is 0), geometry (the canonical
+ * id of the contig, left, right, 0), observed, pairs, and per junction and gap k, in units of 2^-32, log_q = the sum over the
+ * contacts that span the junction inside the window of count * ig_quantize of ig_log10 of E_k and expected_q = the sum over the pairs
+ * that could of ig_quantize of E_k, E_k = ig_rippe at separation + gaps_kb[k] under parameter set 0 (model == 0: expected_q is not
+ * computed and may be NULL).  scalars[8] = {unplaced, trans, ring, counted, uncounted, contributions, n_judged, n_placed}.  On a
+ * sharded handle observed, log_q and the first six scalars add up over the ranks; pairs and expected_q are whole on every rank.
+ * Needs the contacts, a state and parameters, no chain or nuisance step in flight.  Refuses, with nothing written to the caller's
+ * arrays and the handle usable: a malformed list or grid, "model value too large for this window" (the largest |value| times
+ * w (w + 1) / 2 reaches 2^62) and "too many contacts across one junction for this model" (the largest |log| times the largest
+ * observed reaches 2^62).  Writes nothing a move reads; its buffers are kept from call to call and freed by ig_destroy. */
+int ig_gap_support(ig_ctx* ctx, int32_t window, int32_t model, int32_t n_junc, const int32_t* junction, int32_t n_gaps, const float* gaps_kb, int32_t* status,
+                   int32_t* geometry /* [4 n_junc] */, int64_t* observed, int64_t* pairs, int64_t* log_q /* [n_junc * n_gaps] */,
+                   int64_t* expected_q /* [n_junc * n_gaps], NULL iff !model */, int64_t scalars[8]);
+/* the two model values of n separations on the CPU, from include/ig_detmath.h: e_q = ig_quantize of ig_rippe at s under params, l_q =
+ * ig_quantize of ig_log10 of that value; params: the eight floats of ig_params in its order.  No context, no GPU: HIP is not initialised. */
+int ig_model_values_host(const float params[8], const float* s, int64_t n, int64_t* e_q, int64_t* l_q);
+/* one pass of the gap support n times, hipEvents around each (zero + kernel): ms_n[n].  pass 0: the observed pass (one atomic per
+ * word); 1: the model pass as shipped (a wave per junction of up to GAP_WAVE_TERMS terms, a workgroup beyond), 2: a wave per junction,
+ * 3: a workgroup per judged junction.  *checksum (may be NULL): the words the last pass wrote (pass 0: observed, log_q and the six
+ * scalars; else expected_q), each weighted by its place: every form of the model pass must agree on it */
+int ig_debug_gap_support_time(ig_ctx* ctx, int32_t window, int32_t n_junc, const int32_t* junction, int32_t n_gaps, const float* gaps_kb, int32_t pass, int32_t n,
+                              float* ms_n, int64_t* checksum);
 #ifdef __cplusplus
 }
 #endif

@@ -339,6 +339,7 @@ struct GenomeBuf {
     int4* rec = nullptr;   /* [M] (dist, s_tot, contig, position or -1) per sub-fragment */
     float* ds = nullptr;   /* [M] dist by position of the genome order */
     int2* meta = nullptr;  /* [M] (first position of the contig, its sub-fragments; negated: a ring) by position */
+    std::vector<int> canon; /* host: [N] the canonical id of every bin's contig, of the last view (what ig_download_state numbers them) */
     int N = 0, M = 0;
 };
 
@@ -515,6 +516,25 @@ struct OrientBuf {
     int M = 0, cap = 0;
 };
 
+/* gap support (ig_kernels_gap.cuh): buffers kept from call to call -- nj sized for M, the per-junction arrays grown to the longest list
+ * seen (cap), the two [junction][gap] arrays to the most words seen (cap_words); freed by free_gap_buffers (ig_host_gap.inc) */
+struct GapBuf {
+    int* nj = nullptr;                  /* [M] the listed junctions <= every position */
+    int* junc = nullptr;                /* [cap] the caller's list */
+    int* status = nullptr;              /* [cap] 0 judged, 2 on a ring */
+    int4* geo = nullptr;                /* [cap] (the bin at position j, left, right, 0) */
+    int* large = nullptr;               /* [cap] the junctions the model pass gives a workgroup */
+    unsigned long long* pairs = nullptr; /* [cap] */
+    unsigned long long* obs = nullptr;  /* [cap] */
+    unsigned long long* logq = nullptr; /* [cap_words] [junction][gap] */
+    unsigned long long* expq = nullptr; /* [cap_words] [junction][gap] */
+    float* gaps = nullptr;              /* [GAP_MAX_GAPS] the caller's gaps */
+    unsigned long long* sc = nullptr;   /* GAP_NS scalars */
+    int* ctl = nullptr;                 /* 2 words: GAP_CTL_* */
+    int M = 0, cap = 0;
+    size_t cap_words = 0;
+};
+
 struct ig_ctx {
     int device;
     hipStream_t stream;
@@ -627,6 +647,7 @@ struct ig_ctx {
     PlaceBuf place;
     BalBuf bal;
     OrientBuf orient;
+    GapBuf gap;
     DebugRows debug_rows;
     int* batch_out; /* committed moves, pending slot, (unused), candidates, predicted deltas used, contigs */
     int *host_bo, *host_bo_dev; /* the same in mapped host memory (+ [7] = sequence number of the decide launch), and its device address */

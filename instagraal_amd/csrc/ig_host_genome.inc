@@ -84,6 +84,7 @@ static int genome_view(ig_ctx* c, const char* who, long long max_side, unsigned 
         g.N = c->N;
         g.M = M;
     }
+    g.canon = ids; /* (host: the canonical id of every bin's contig, for the reports that name contigs) */
     dims->T = (int)T;
     map_binning(T, max_side, &dims->bin, &dims->side);
     const bool order = (want & (GENOME_ORDER | GENOME_SORTED)) != 0;

@@ -18,8 +18,8 @@ SRC = os.path.join(HERE, "csrc", "ig_hip.hip")
 SRC_HOST = os.path.join(HERE, "csrc", "ig_draw.cpp")  # host-only part: the candidate draw
 DEPS = [SRC, SRC_HOST] + [os.path.join(HERE, "csrc", f) for f in ("ig_ops.cuh", "ig_common.cuh", "ig_model.cuh", "ig_kernels_setup.cuh",
                                                           "ig_kernels_score.cuh", "ig_kernels_screen.cuh", "ig_kernels_commit.cuh",
-                                                          "ig_kernels_nuis.cuh", "ig_kernels_genome.cuh", "ig_kernels_rows.cuh", "ig_kernels_map.cuh", "ig_kernels_law.cuh", "ig_kernels_junc.cuh", "ig_kernels_lift.cuh", "ig_kernels_join.cuh", "ig_kernels_emap.cuh", "ig_kernels_place.cuh", "ig_kernels_orient.cuh", "ig_kernels_bal.cuh", "ig_host_core.inc", "ig_host_upload.inc", "ig_host_genome.inc", "ig_host_rows.inc",
-                                                          "ig_host_map.inc", "ig_host_law.inc", "ig_host_junc.inc", "ig_host_lift.inc", "ig_host_join.inc", "ig_host_emap.inc", "ig_host_place.inc", "ig_host_orient.inc", "ig_host_bal.inc",
+                                                          "ig_kernels_nuis.cuh", "ig_kernels_genome.cuh", "ig_kernels_rows.cuh", "ig_kernels_map.cuh", "ig_kernels_law.cuh", "ig_kernels_junc.cuh", "ig_kernels_lift.cuh", "ig_kernels_join.cuh", "ig_kernels_emap.cuh", "ig_kernels_place.cuh", "ig_kernels_orient.cuh", "ig_kernels_bal.cuh", "ig_kernels_gap.cuh", "ig_host_core.inc", "ig_host_upload.inc", "ig_host_genome.inc", "ig_host_rows.inc",
+                                                          "ig_host_map.inc", "ig_host_law.inc", "ig_host_junc.inc", "ig_host_lift.inc", "ig_host_join.inc", "ig_host_emap.inc", "ig_host_place.inc", "ig_host_orient.inc", "ig_host_bal.inc", "ig_host_gap.inc",
                                                           "ig_host_batch.inc", "ig_host_nuis.inc", "ig_host_debug.inc")] + \
        [os.path.join(ROOT, "include", f) for f in ("ig_detmath.h", "ig_detmath_tables.h", "instagraal_hip.h")]
 
@@ -30,6 +30,8 @@ PLACEMENT_SUPPORT_PASSES = ("records", "count", "rows", "scatter", "sort_short",
 PLACEMENT_SUPPORT_FORMS = ("default", "thread", "wave")  # ig_debug_placement_support_form
 ORIENTATION_SUPPORT_WAVE_PAIRS = 4096  # ORIENT_WAVE_PAIRS (csrc/ig_kernels_orient.cuh): 2 * pairs beyond this take a workgroup in the model pass
 ORIENTATION_SUPPORT_FORMS = {"observed": ("atomic", "combined"), "model": ("default", "wave", "workgroup")}  # ig_debug_orientation_support_time: pass -> forms
+GAP_SUPPORT_WAVE_TERMS = 8192  # GAP_WAVE_TERMS (csrc/ig_kernels_gap.cuh): pairs * gaps beyond this take a workgroup in the model pass
+GAP_SUPPORT_PASSES = ("observed", "model", "model_wave", "model_workgroup")  # ig_debug_gap_support_time
 BALANCE_BUILD_PASSES = ("units", "count", "rows", "scatter", "sort_short", "sort_lds", "sort_long", "reduce")  # ig_debug_balance_build_time
 BALANCE_FORMS = ("default", "wave", "packed")  # ig_debug_balance_form
 MAX_CANDIDATES = 16
@@ -102,6 +104,19 @@ def lib():
 
 class HipError(RuntimeError):
     pass
+
+
+def model_values_host(params, s):
+    """the two quantised model values of the separations ``s`` (f32) on the CPU, from include/ig_detmath.h (``ig_model_values_host``:
+    no context, no GPU) -> (e_q, l_q), int64 arrays of the shape of ``s``: ig_quantize(ig_rippe(s, params)) and ig_quantize(ig_log10
+    of that value).  ``params``: the eight floats of ig_params in its order (``sampler.PARAM_NAMES``)"""
+    p = np.ascontiguousarray(params, np.float32).ravel()
+    if p.size != 8:
+        raise HipError("model_values_host: eight parameters in the order of ig_params (got %d)" % p.size)
+    sep = np.ascontiguousarray(s, np.float32)
+    e_q, l_q = np.zeros(sep.shape, np.int64), np.zeros(sep.shape, np.int64)
+    _ck(lib().ig_model_values_host(_p(p), _p(sep), C.c_int64(sep.size), _p(e_q), _p(l_q)))
+    return e_q, l_q
 
 
 def _ck(rc):
@@ -941,6 +956,51 @@ class Context:
         _ck(lib().ig_debug_orientation_support_time(self._h, C.c_int32(int(window)), C.c_int32(int(f.size)), _p(f), _p(l),
                                                     C.c_int32(("observed", "model").index(which)), C.c_int32(forms.index(forms[0] if form is None else form)),
                                                     C.c_int32(int(n)), _p(ms), C.byref(ck)))
+        return ms, int(ck.value)
+
+    # ---- gap support: the distance the contacts put across each join (the rule: gap_support.py)
+    @staticmethod
+    def _junctions_and_gaps(junctions, gaps_kb):
+        j, g = np.asarray(junctions), np.asarray(gaps_kb)
+        if j.ndim != 1 or not np.issubdtype(j.dtype, np.integer):
+            raise HipError("gap_support: junction list: one integer vector")
+        if j.size and (j.min() < -2 ** 31 or j.max() >= 2 ** 31):
+            raise HipError("gap_support: junction list out of range")
+        if g.ndim != 1:
+            raise HipError("gap_support: gaps: one vector")
+        return np.ascontiguousarray(j, np.int32), np.ascontiguousarray(g, np.float32)
+
+    def gap_support(self, window, junctions, gaps_kb, model=True):
+        """per listed junction the contacts that span it inside ``window`` positions and the two halves of the Poisson
+        log-likelihood under every gap of ``gaps_kb`` -> dict: window, n_junctions, junction, gaps_kb, status (int32 [n_j]), geometry
+        (int32 [n_j, 4]: contig, left, right, 0), observed, pairs (int64 [n_j]), log_q, expected_q (int64 [n_j, K]; expected_q None
+        with ``model=False``) and the int64 scalars of ``gap_support.SCALARS``"""
+        from .gap_support import SCALARS
+
+        j, g = self._junctions_and_gaps(junctions, gaps_kb)
+        n_j, K = int(j.size), int(g.size)
+        status = np.zeros(max(n_j, 1), np.int32)
+        geo = np.zeros((max(n_j, 1), 4), np.int32)
+        obs, prs = np.zeros(max(n_j, 1), np.int64), np.zeros(max(n_j, 1), np.int64)
+        lgq = np.zeros((max(n_j, 1), max(K, 1)), np.int64)
+        exq = np.zeros((max(n_j, 1), max(K, 1)), np.int64) if model else None
+        sc = np.zeros(8, np.int64)
+        _ck(lib().ig_gap_support(self._h, C.c_int32(int(window)), C.c_int32(int(bool(model))), C.c_int32(n_j), _p(j), C.c_int32(K), _p(g), _p(status), _p(geo),
+                                 _p(obs), _p(prs), _p(lgq), _p(exq), _p(sc)))
+        out = dict(window=int(window), n_junctions=n_j, junction=j.astype(np.int64), gaps_kb=g, status=status, geometry=geo, observed=obs, pairs=prs, log_q=lgq,
+                   expected_q=exq)
+        out.update((k, int(v)) for k, v in zip(SCALARS, sc))
+        return out
+
+    def debug_gap_support_time(self, window, junctions, gaps_kb, which="observed", n=1):
+        """one pass of the gap support n times with hipEvents around each -> (ms [n], checksum of what the last pass wrote).
+        ``which``: one of ``GAP_SUPPORT_PASSES`` -- "observed", or the model pass as shipped ("model"), with a wave per junction
+        ("model_wave") or a workgroup per judged junction ("model_workgroup")"""
+        j, g = self._junctions_and_gaps(junctions, gaps_kb)
+        ms = np.zeros(int(n), np.float32)
+        ck = C.c_int64()
+        _ck(lib().ig_debug_gap_support_time(self._h, C.c_int32(int(window)), C.c_int32(int(j.size)), _p(j), C.c_int32(int(g.size)), _p(g),
+                                            C.c_int32(GAP_SUPPORT_PASSES.index(which)), C.c_int32(int(n)), _p(ms), C.byref(ck)))
         return ms, int(ck.value)
 
     # ---- placement support: where the contacts say each bin belongs (the rule: placement_support.py)

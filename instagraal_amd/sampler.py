@@ -1194,6 +1194,69 @@ class sampler:  # noqa: N801 - the reference's class name
         res = self.orientation_support(level, segments, window, window_kb, model) if result is None else result
         return osup.inverted_segments(res, n, min_observed)
 
+    # ------------------------------------------------------------ gap support
+    def gap_support(self, level="block", junctions=None, gaps_kb=None, window=None, window_kb=None, model=True):
+        """The distance the contacts put across each join of the current genome (``ig_gap_support``; the rule: ``gap_support.py``):
+        per junction the contacts that span it, the pairs that could, and the two halves of a Poisson log-likelihood under every gap
+        of a grid -- a true join across missing sequence still decays with distance, as P(s + g); a misjoin sits at the trans level.
+        ``level``: "block", the junctions between two blocks of one scaffold (``gap_support.block_junctions``: the only places where
+        a gap can exist), or "bin", every internal junction at which the bin changes; ``junctions``: the caller's own positions,
+        which override ``level``.  ``gaps_kb``: the grid (default ``gap_support.default_gaps`` of the mean sub-fragment length and
+        d_max); ``window``: in positions (default 64, at most 256), or ``window_kb``.  -> the device's dict (window, junction,
+        gaps_kb, status, geometry, observed, pairs, log_q, expected_q, the scalars) plus ``level``, the junction table --
+        ``scaffold`` (the canonical id: ``assembly_contacts.scaffold_names`` names it), ``left_bin``, ``right_bin`` --, ``order``,
+        ``apart_q`` and, with the model, the columns of ``gap_support.derived`` (``ll``, ``ll_apart``, ``best``, ``gap_kb``,
+        ``gap_lo``, ``gap_hi``, ``llr_gap``, ``llr_apart``, ``verdict``).  A level without a junction returns empty arrays (the device is
+        not asked).  No reference counterpart."""
+        from . import gap_support as gs
+        from .hip_lib import model_values_host
+
+        if window is not None and window_kb is not None:
+            raise ValueError("gap_support: window or window_kb, not both")
+        if window_kb is not None:
+            window = min(gs.window_from_kb(window_kb, self.mean_kb()), gs.MAX_WINDOW)
+        w = gs.check_window(gs.DEFAULT_WINDOW if window is None else window)
+        if self.param_simu is None:
+            raise ValueError("gap_support: set the parameters first (set_param_simu)")
+        p8 = np.array([float(self.param_simu[k][0]) for k in PARAM_NAMES], np.float32)
+        gaps = gs.default_gaps(self.mean_kb(), float(self.param_simu["d_max"][0])) if gaps_kb is None else gs.check_gaps(gaps_kb)
+        order = self.ctx.contact_map_order().astype(np.int64)
+        parent = self.np_sub_frags_2_frags["x"].astype(np.int64)
+        g = self.gpu_vect_frags.copy_from_gpu()
+        if junctions is not None:
+            junc, level = np.asarray(junctions), "custom"
+        elif level == "block":
+            junc = gs.block_junctions(order, parent, g.id_c, g.ori, g.id_d, self.np_init_id_c, self.np_init_pos)["junction"]
+        elif level == "bin":
+            junc = gs.bin_junctions(order, parent, g.id_c)["junction"]
+        else:
+            raise ValueError("gap_support: level is 'block' or 'bin' (got %r)" % (level,))
+        if junc.size:
+            res = self.ctx.gap_support(w, junc, gaps, model=model)
+        else:  # (fresh, a block is its contig: nothing to ask the device)
+            K = int(gaps.size)
+            res = dict(window=w, n_junctions=0, junction=np.zeros(0, np.int64), gaps_kb=gaps, status=np.zeros(0, np.int32), geometry=np.zeros((0, 4), np.int32),
+                       observed=np.zeros(0, np.int64), pairs=np.zeros(0, np.int64), log_q=np.zeros((0, K), np.int64),
+                       expected_q=np.zeros((0, K), np.int64) if model else None)
+            res.update((k, 0) for k in gs.SCALARS)
+        res["level"], res["order"] = level, order
+        at = parent[order]
+        res["left_bin"], res["right_bin"] = at[res["junction"] - 1], at[res["junction"]]
+        res["scaffold"] = g.id_c.astype(np.int64)[res["right_bin"]]
+        e_inf, l_inf = model_values_host(p8, np.array([np.inf], np.float32))
+        res["apart_q"] = (int(e_inf[0]), int(l_inf[0]))
+        if model:
+            res.update(gs.derived(res))
+        return res
+
+    def gapped_joins(self, n=20, min_observed=0, result=None, level="block", junctions=None, gaps_kb=None, window=None, window_kb=None):
+        """The ``n`` joins of ``gap_support()`` whose verdict is "gap" or "apart", the most decided first
+        (``gap_support.gapped_joins``: by max(llr_gap, ll_apart - ll[0]), ties by junction)."""
+        from . import gap_support as gs
+
+        res = self.gap_support(level, junctions, gaps_kb, window, window_kb, True) if result is None else result
+        return gs.gapped_joins(res, n, min_observed)
+
     # ----------------------------------------------------------- expected map
     def expected_map(self, max_side=2048):
         """What the model in use (``param_simu``) predicts for the pixels of ``contact_map(max_side)`` (``ig_expected_map``; the

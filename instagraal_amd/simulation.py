@@ -194,7 +194,7 @@ class instagraal_class:
         self.collect_id_fA_sampled.append(id_frag)
 
     def full_em(self, n_cycles, n_neighbours, bomb, id_start_sample_param, save_matrix=False, save_law=False, save_junctions=False,
-                save_contacts=False, save_joins=False, save_residuals=False, save_placements=False, save_orientations=False, save_weights=False):  # IG:196-291
+                save_contacts=False, save_joins=False, save_residuals=False, save_placements=False, save_orientations=False, save_weights=False, save_gaps=False):  # IG:196-291
         sampler = self.simulation.sampler
         if bomb:
             sampler.bomb_the_genome()
@@ -266,6 +266,11 @@ class instagraal_class:
 
             osup.write_orientations(self._out("orientations.txt"), sampler.orientation_support(level="block"), title="level=block")
             osup.write_orientations(self._out("orientations.txt"), sampler.orientation_support(level="bin"), mode="a", title="level=bin")
+        if save_gaps:  # (once, behind the last cycle: the joins between blocks, then between bins, with the gap the contacts put across each)
+            from . import gap_support as gsup
+
+            gsup.write_gaps(self._out("gaps.txt"), sampler.gap_support(level="block"), title="level=block")
+            gsup.write_gaps(self._out("gaps.txt"), sampler.gap_support(level="bin"), mode="a", title="level=bin")
         self.save_behaviour_to_txt()
 
     def save_behaviour_to_txt(self):  # IG:293-330
@@ -282,7 +287,7 @@ class instagraal_class:
 def run_instagraal(hic_folder, reference_fa, output_folder=None, level=4, cycles=100, coverage_std=1, neighborhood=5, device=0,
                    circular=False, bomb=False, pyramid_only=False, save_pickle=False, save_matrix=False, simple=False, save_law=False,
                    save_junctions=False, save_contacts=False, save_joins=False, save_residuals=False, save_placements=False,
-                   save_orientations=False, save_weights=False):
+                   save_orientations=False, save_weights=False, save_gaps=False):
     """IG:502-581 (defaults of cli/main.py: level 4, 100 cycles, 5 neighbours, 1 std).  The three trailing switches of the
     reference's signature (IG:512-514) are accepted: ``save_pickle`` dumps the run object to ``graal.pkl`` as the reference
     tries to (IG:589-594: a warning when it cannot be pickled -- device handles here, h5py handles there); ``save_matrix``
@@ -310,7 +315,11 @@ def run_instagraal(hic_folder, reference_fa, output_folder=None, level=4, cycles
     ends and the positions on either side inside a window of 8 sub-fragments, split into those that keep it as it lies and those that
     would reverse it (``sampler.orientation_support``); ``save_weights`` (an addition too) writes ``weights.txt`` once, behind
     the last cycle: one line per bin of the final genome with its scaffold, start, end and balancing weight -- the raw count of two bins
-    times their two weights is the balanced count (``sampler.balance``)."""
+    times their two weights is the balanced count (``sampler.balance``); ``save_gaps`` (an addition too) writes ``gaps.txt``
+    once, behind the last cycle: one line per join -- those between two co-linear blocks of a scaffold first, those between two bins
+    behind them -- with the contacts observed across it inside a window of 64 sub-fragments, the pairs, the gap in kb under which the
+    model explains them best, its 95 % interval, the two log-likelihood ratios and the verdict "adjacent", "gap" or "apart"
+    (``sampler.gap_support``)."""
     import warnings
 
     if simple and not pyramid_only:
@@ -331,7 +340,7 @@ def run_instagraal(hic_folder, reference_fa, output_folder=None, level=4, cycles
         p2.simulation.level.S_o_A_frags["circ"] += 1
     p2.full_em(n_cycles=cycles, n_neighbours=neighborhood, bomb=bomb, id_start_sample_param=4, save_matrix=save_matrix, save_law=save_law,
                save_junctions=save_junctions, save_contacts=save_contacts, save_joins=save_joins, save_residuals=save_residuals, save_placements=save_placements,
-               save_orientations=save_orientations, save_weights=save_weights)
+               save_orientations=save_orientations, save_weights=save_weights, save_gaps=save_gaps)
     if save_pickle:  # IG:589-594
         import pickle
 
