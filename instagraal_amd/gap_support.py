@@ -28,9 +28,9 @@ addition -- and E_k = ig_rippe(s_k, p) under parameter set 0 (beyond d_max that 
 * ``expected_q[j][k]`` = the sum over the pairs of ig_quantize((double) E_k);
 * ``log_q[j][k]`` = the sum over the spanning contacts of cnt * ig_quantize(ig_log10((double) E_k)),
 
-both int64 in units of 2^-32, added as integers (unsigned wrap on the way; the device's guards make the final value fit), so the
-result does not depend on the order of the additions.  It is a profile PER JUNCTION: a pair that also spans another listed junction
-takes that junction's gap as 0.
+both int64 in units of 2^-32, added as integers (unsigned wrap on the way; the device's guards, the second of them stated here as
+``log_sum_fits``, make the final value fit), so the result does not depend on the order of the additions.  It is a profile PER
+JUNCTION: a pair that also spans another listed junction takes that junction's gap as 0.
 
 The scalars (int64, SCALARS).  Every contact falls in the first class that fits -- ``unplaced`` (an end in a contig that is not
 placed), ``trans``, ``ring``, ``counted`` (cis on a linear contig, in window, spanning at least one judged listed junction),
@@ -116,7 +116,15 @@ def check_junctions(junctions, n_placed, contig_start):
     return j
 
 
-def support_host(dist, stot, contig, placed, position, row, col, cnt, junctions, gaps_kb, window, model, want_expected=True, canonical=None):
+def log_sum_fits(observed_max, max_abs_log_q):
+    """the device's second guard (``ig_gap_support``: "too many contacts across one junction for this model"): a word of ``log_q`` adds
+    at most max_j observed[j] counts times the largest |quantised log10| of a counted contact; the call is refused unless that product
+    stays below 2^62.  Python integers -> bool"""
+    return int(observed_max) * int(max_abs_log_q) < 1 << 62
+
+
+def support_host(dist, stot, contig, placed, position, row, col, cnt, junctions, gaps_kb, window, model, want_expected=True, canonical=None,
+                 check=True):
     """The rule, pair by pair and contact by contact (deliberately not the device's algorithm: no painted counts, no atomics).
 
     dist, stot: f32 [M]; contig: int [M] (any labelling); placed: bool [M]; position: int [M], the position in the genome order,
@@ -124,7 +132,9 @@ def support_host(dist, stot, contig, placed, position, row, col, cnt, junctions,
     model value and the quantised log10 of it (int64 arrays); ``canonical``: int [M], the canonical contig id of every sub-fragment
     (None: ``contig`` is reported).  -> dict: window, n_junctions, junction, gaps_kb, status (int32 [n_j]), geometry (int32 [n_j, 4]),
     observed, pairs (int64 [n_j]), log_q, expected_q (int64 [n_j, K]; expected_q None without ``want_expected``), apart_q (the model's
-    two values at an infinite separation: v_inter) and the int64 scalars named in SCALARS."""
+    two values at an infinite separation: v_inter), max_abs_log_q (the largest |l_q| of a counted contact under any gap) and the int64
+    scalars named in SCALARS.  ValueError where ``log_sum_fits`` fails, as the device refuses (``check=False``: the result comes back,
+    its ``log_q`` wrapped modulo 2^64)."""
     w = check_window(window)
     gaps = check_gaps(gaps_kb)
     K = int(gaps.size)
@@ -177,6 +187,7 @@ def support_host(dist, stot, contig, placed, position, row, col, cnt, junctions,
     observed = np.zeros(n_j, np.int64)
     log_q = np.zeros((n_j, K), np.int64)
     lo, n, v, s = lo[hit], spans[hit], c[hit], sep[hit]
+    out["max_abs_log_q"] = 0
     if n.size:
         first = np.cumsum(n) - n
         which = np.repeat(lo - first, n) + np.arange(int(n.sum()), dtype=np.int64)  # every contact's junctions lo .. lo + n - 1
@@ -184,9 +195,13 @@ def support_host(dist, stot, contig, placed, position, row, col, cnt, junctions,
         shifted = s[:, None] + gaps[None, :]
         assert shifted.dtype == np.float32
         lq = np.asarray(model(shifted.ravel())[1], np.int64).reshape(shifted.shape)
+        out["max_abs_log_q"] = max(abs(int(lq.max())), abs(int(lq.min())))
         with np.errstate(over="ignore"):
             np.add.at(log_q, which, np.repeat(v[:, None] * lq, n, axis=0))
     out["observed"], out["log_q"] = observed, log_q
+    if check and not log_sum_fits(observed.max() if n_j else 0, out["max_abs_log_q"]):
+        raise ValueError("gap support: too many contacts across one junction for this model (%d contacts, the largest |log10| %.6g: their product does "
+                         "not fit the 64-bit sum)" % (int(observed.max()), out["max_abs_log_q"] / Q_ONE))
 
     # ---- the pairs of every contig that holds a listed junction, separation by separation
     expected_q = None

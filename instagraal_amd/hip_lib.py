@@ -119,6 +119,30 @@ def model_values_host(params, s):
     return e_q, l_q
 
 
+def as_int32_exact(a, name="array"):
+    """``a`` as a contiguous int32 array; ValueError unless every value survives the conversion: a whole number within
+    -2^31 .. 2^31 - 1 (a count of 2^31 would wrap to -2^31, 2.5 would truncate to 2).  No device, no library."""
+    src = np.asarray(a)
+    if src.dtype == np.int32:
+        return np.ascontiguousarray(src)
+    if src.dtype == object or not (np.issubdtype(src.dtype, np.integer) or np.issubdtype(src.dtype, np.floating) or src.dtype == np.bool_):
+        raise ValueError("%s: integers expected (got dtype %s)" % (name, src.dtype))
+    if np.issubdtype(src.dtype, np.floating):
+        bad = ~np.isfinite(src) | (src != np.floor(np.where(np.isfinite(src), src, 0))) | (src < -2.0 ** 31) | (src >= 2.0 ** 31)
+    else:
+        bad = np.zeros(src.shape, bool)
+        if src.dtype != np.bool_:
+            info = np.iinfo(src.dtype)
+            if info.max > 2 ** 31 - 1:
+                bad |= src > 2 ** 31 - 1
+            if info.min < -2 ** 31:
+                bad |= src < -2 ** 31
+    if bad.any():
+        k = int(np.flatnonzero(bad)[0])
+        raise ValueError("%s: %d of %d values do not fit int32 (the first: %r at index %d)" % (name, int(bad.sum()), src.size, src.ravel()[k].item(), k))
+    return np.ascontiguousarray(src, np.int32)
+
+
 def _ck(rc):
     if rc != 0:
         raise HipError(lib().ig_last_error().decode())
@@ -328,9 +352,7 @@ class Context:
 
     # ---- upload
     def upload_contacts(self, row, col, cnt, M, rank=0, world=1):
-        row = np.ascontiguousarray(row, np.int32)
-        col = np.ascontiguousarray(col, np.int32)
-        cnt = np.ascontiguousarray(cnt, np.int32)
+        row, col, cnt = as_int32_exact(row, "row"), as_int32_exact(col, "col"), as_int32_exact(cnt, "cnt")
         _ck(lib().ig_upload_contacts(self._h, _p(row), _p(col), _p(cnt), C.c_int64(row.size), C.c_int32(M), C.c_int32(rank),
                                      C.c_int32(world)))
         self.M = int(M)
