@@ -534,6 +534,12 @@ int ig_debug_rows_build(ig_ctx* ctx, const int32_t* lo, const uint64_t* word, in
  * caller's) -- not reduced: word[n_out], sorted inside every row as unsigned 64-bit words (col and count are not written); reduced:
  * col[n_out] and count[n_out] (word is not written) */
 int ig_debug_rows_fetch(ig_ctx* ctx, int64_t* rowptr, int64_t n_rowptr, uint64_t* word, int32_t* col, int64_t* count, int64_t capacity);
+/* tests: the combining idiom of the passes over the contacts (a run of a wave's lanes with an equal destination is summed inside the
+ * wave and issues one atomic) over caller data, unchanged: entry k adds values[k] to out[keys[k]] (a negative key: no entry), n
+ * entries in order, 64 to a wave, 256 to a workgroup.  wide: 0 the sums inside the wave are made in 32 bits (no run may overflow
+ * them), else in 64.  out[n_dest]: the sums; *atomics: the atomics issued -- one per run with a key whose values do not sum to 0.
+ * Refused: a NULL pointer, negative n or n_dest, keys[k] >= n_dest.  Needs a created handle, nothing uploaded. */
+int ig_debug_wave_runs(ig_ctx* ctx, const int32_t* keys, const int64_t* values, int64_t n, int32_t n_dest, int32_t wide, int64_t* out, int64_t* atomics);
 /* join support: the form of the two passes over the contacts of THIS handle's builds: 1 a run of a wave's lanes with the same row
  * issues one atomic per emission, 0 one atomic per emission (the yardstick), negative: the form the library ships.  The result is
  * the same.  The limits of ig_debug_assembly_contacts_limits hold for this feature's sorts too. */

@@ -25,9 +25,10 @@
  * plus the one-move kernels k_scores / k_delta / k_apply / k_post / k_commit (single moves, windowed winners), and the
  * from-scratch pass over all contacts: k_pack_tab_sig / k_nuis_prepare, k_tile_trans, k_full_nz_tiled; the
  * nuisance step's screened pass: k_hist_build / k_hist_walk / k_hist_eval (tier 0), k_full_diff_tiled (tier 1);
- * the reports on the current genome and the two layers they share -- the genome view: k_map_pixels, k_law_records,
+ * the reports on the current genome and the three homes of what they share -- the wave idioms: device helpers, no
+ * kernel (ig_kernels_wave.cuh); the genome view: k_map_pixels, k_law_records,
  * k_law_sorted; the row builder: k_scan64_totals / _tops / _apply, k_lift_classify, k_lift_sort_wave / _lds, k_lift_merge,
- * k_lift_row_bits, k_lift_head_totals, k_lift_reduce (and the tests' k_debug_rows_emit) --; the contact map: k_contact_map, k_map_mirror; the distance
+ * k_lift_row_bits, k_lift_head_totals, k_lift_reduce (and the tests' k_debug_rows_emit, k_debug_wave_runs) --; the contact map: k_contact_map, k_map_mirror; the distance
  * law: k_law_observed, k_law_pairs (4.11); the junction support profile: k_junc_observed, k_junc_count, k_junc_model (4.12); the
  * contacts in genome coordinates: k_lift_heads, k_lift_keys, k_lift_pass (4.13); the join support of the scaffold ends: k_join_heads,
  * k_join_ends, k_join_records, k_join_emit, k_join_model (4.14); the expected contact map: k_emap_count, k_emap_rows, k_emap_list,
@@ -54,6 +55,7 @@
 #include "ig_kernels_screen.cuh"
 #include "ig_kernels_commit.cuh"
 #include "ig_kernels_nuis.cuh"
+#include "ig_kernels_wave.cuh"
 #include "ig_kernels_genome.cuh"
 #include "ig_kernels_rows.cuh"
 #include "ig_kernels_map.cuh"

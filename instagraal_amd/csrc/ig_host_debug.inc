@@ -496,3 +496,44 @@ extern "C" int ig_debug_rows_fetch(ig_ctx* c, int64_t* rowptr, int64_t n_rowptr,
         memcpy(word, d.word.data(), n_out * sizeof(uint64_t));
     return 0;
 }
+
+/* ---- the wave idioms on caller data (tests/test_hip_wave_runs.py): wave_runs and wave_run_sum through k_debug_wave_runs on a bare
+ * handle.  The grid is capped so that a hundred thousand entries take the grid-stride loop more than once. */
+#define DEBUG_WAVE_BLOCKS 64
+
+extern "C" int ig_debug_wave_runs(ig_ctx* c, const int32_t* keys, const int64_t* values, int64_t n, int32_t n_dest, int32_t wide, int64_t* out, int64_t* atomics)
+{
+    IG_JOIN(c);
+    HIPCK(hipSetDevice(c->device));
+    const char* who = "ig_debug_wave_runs";
+    if (n < 0 || n_dest < 0) return fail("%s: %lld entries for %d words: neither may be negative", who, (long long)n, n_dest);
+    if (!atomics || (n > 0 && (!keys || !values)) || (n_dest > 0 && !out)) return fail("%s: NULL argument", who);
+    if (c->nuis_in_flight || c->chain_busy) return fail("%s: a nuisance step or a chain is in flight", who);
+    for (int64_t k = 0; k < n; k++)
+        if (keys[k] >= n_dest) return fail("%s: entry %lld has the key %d, there are %d words", who, (long long)k, keys[k], n_dest);
+    int* d_key = nullptr;
+    long long* d_val = nullptr;
+    unsigned long long* d_out = nullptr; /* the sums, then one word: the atomics issued */
+    const int rc = [&]() -> int {
+        DALLOC(d_key, (size_t)std::max<int64_t>(n, 1));
+        DALLOC(d_val, (size_t)std::max<int64_t>(n, 1));
+        DALLOC(d_out, (size_t)n_dest + 1);
+        HIPCK(hipMemsetAsync(d_out, 0, ((size_t)n_dest + 1) * sizeof(unsigned long long), c->stream));
+        if (n > 0) {
+            HIPCK(hipMemcpyAsync(d_key, keys, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+            HIPCK(hipMemcpyAsync(d_val, values, (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+            const dim3 grid((unsigned)std::min<int64_t>((n + LIFT_THREADS - 1) / LIFT_THREADS, DEBUG_WAVE_BLOCKS)), block(LIFT_THREADS);
+            if (wide) hipLaunchKernelGGL((k_debug_wave_runs<long long>), grid, block, 0, c->stream, d_key, d_val, (long long)n, d_out, d_out + n_dest);
+            else hipLaunchKernelGGL((k_debug_wave_runs<int>), grid, block, 0, c->stream, d_key, d_val, (long long)n, d_out, d_out + n_dest);
+        }
+        if (n_dest > 0) HIPCK(hipMemcpyAsync(out, d_out, (size_t)n_dest * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+        HIPCK(hipMemcpyAsync(atomics, d_out + n_dest, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+        HIPCK(hipStreamSynchronize(c->stream));
+        return 0;
+    }();
+    hipStreamSynchronize(c->stream);
+    hipFree(d_key);
+    hipFree(d_val);
+    hipFree(d_out);
+    return rc;
+}

@@ -220,9 +220,7 @@ extern "C" int ig_debug_gap_support_time(ig_ctx* c, int32_t window, int32_t n_ju
         HIPCK(hipMemcpy(h.data(), b.expq, words * sizeof(long long), hipMemcpyDeviceToHost));
     }
     if (checksum) { /* of the last pass: every word weighted by its place: every form of a pass must agree on it */
-        unsigned long long s = 0;
-        for (size_t k = 0; k < h.size(); k++) s += (unsigned long long)h[k] * (unsigned long long)(k + 1);
-        *checksum = (long long)s;
+        *checksum = (long long)weighted_checksum(h.data(), h.size());
     }
     return 0;
 }

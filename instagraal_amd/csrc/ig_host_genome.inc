@@ -1,6 +1,7 @@
 /* ig_host_genome.inc -- part of ig_hip.hip (one translation unit; included there in order): the genome view (GenomeBuf;
  * ig_kernels_genome.cuh), the tables of the current genome every report starts from, and the small helpers the reports over it
- * share (the window check, the model pass's overflow guard, the event-timed repeats of the ig_debug_*_time entry points). */
+ * share (the window check, the model pass's overflow guard, the event-timed repeats and the checksum of the ig_debug_*_time entry
+ * points). */
 
 static void free_genome_buffers(ig_ctx* c)
 {
@@ -135,6 +136,15 @@ static int check_model_values(ig_ctx* c, const char* who, const unsigned long lo
 static int check_model_sum(ig_ctx* c, const char* who, const unsigned long long* d_maxq, int window)
 {
     return check_model_values(c, who, d_maxq, (unsigned long long)window * (unsigned long long)(window + 1) / 2);
+}
+
+/* the checksum of the ig_debug_*_time entry points: the n words of h, each weighted by its place (1, 2, ...), modulo 2^64: every
+ * form of a pass must agree on it */
+static unsigned long long weighted_checksum(const long long* h, size_t n)
+{
+    unsigned long long s = 0;
+    for (size_t k = 0; k < n; k++) s += (unsigned long long)h[k] * (unsigned long long)(k + 1);
+    return s;
 }
 
 /* n repetitions of enqueue() -- launches on the library's stream, non-zero: stop -- between two events, waited for each: the

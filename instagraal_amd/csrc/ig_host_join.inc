@@ -260,10 +260,9 @@ extern "C" int ig_debug_join_support_time(ig_ctx* c, int32_t window, int32_t n, 
         if (join_build(c, "ig_debug_join_support_time", window, c->have_params, ms_n + (size_t)r * JOIN_PASSES, sc)) return -1;
     if (checksum) { /* of the observed part of the last result: the rows, the columns and the counts, every word weighted by its place */
         JoinBuf& j = c->join;
-        unsigned long long s = 0, place = 1;
         std::vector<long long> rows((size_t)(2 * j.n_contigs + 1));
         HIPCK(hipMemcpy(rows.data(), j.rows.rowptr, rows.size() * sizeof(long long), hipMemcpyDeviceToHost));
-        for (long long v : rows) s += (unsigned long long)v * place++;
+        unsigned long long s = weighted_checksum(rows.data(), rows.size()), place = rows.size() + 1; /* behind the rows: column, observed, column, ... */
         std::vector<int32_t> col((size_t)j.n_links);
         std::vector<int64_t> obs((size_t)j.n_links);
         if (ig_join_support_fetch(c, 0, j.n_links, col.data(), obs.data(), nullptr, nullptr)) return -1;

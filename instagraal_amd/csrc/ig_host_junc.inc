@@ -140,9 +140,7 @@ extern "C" int ig_debug_junction_profile_time(ig_ctx* c, int32_t window, int32_t
         std::vector<long long> h((size_t)T + JUNC_N_OBS, 0);
         if (T > 0) HIPCK(hipMemcpy(h.data(), c->junc.prof, (size_t)T * sizeof(long long), hipMemcpyDeviceToHost));
         HIPCK(hipMemcpy(h.data() + T, c->junc.sc, JUNC_N_OBS * sizeof(long long), hipMemcpyDeviceToHost));
-        unsigned long long s = 0;
-        for (size_t k = 0; k < h.size(); k++) s += (unsigned long long)h[k] * (unsigned long long)(k + 1);
-        *checksum = (long long)s;
+        *checksum = (long long)weighted_checksum(h.data(), h.size());
     }
     return 0;
 }

@@ -126,10 +126,7 @@ extern "C" int ig_debug_distance_law_time(ig_ctx* c, const float* edges, int32_t
     if (checksum) { /* of the last observed pass, every word weighted by its place: both forms of the kernel must agree on it */
         std::vector<long long> h(LAW_MAX_BINS + LAW_NS);
         HIPCK(hipMemcpy(h.data(), c->law.out, h.size() * sizeof(long long), hipMemcpyDeviceToHost));
-        unsigned long long s = 0;
-        for (int b2 = 0; b2 < n_edges - 1; b2++) s += (unsigned long long)h[LAW_OUT_OBS + b2] * (unsigned long long)(b2 + 1);
-        for (int k = 0; k < LAW_NS; k++) s += (unsigned long long)h[LAW_OUT_OSC + k] * (unsigned long long)(LAW_MAX_BINS + 1 + k);
-        *checksum = (long long)s;
+        *checksum = (long long)weighted_checksum(h.data(), h.size()); /* (the bins behind the last edge are 0: law_enqueue_observed zeroes them all) */
     }
     return 0;
 }

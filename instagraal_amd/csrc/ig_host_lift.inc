@@ -220,10 +220,9 @@ extern "C" int ig_debug_assembly_contacts_time(ig_ctx* c, int32_t level, int32_t
         if (lift_build(c, "ig_debug_assembly_contacts_time", level, ms_n + (size_t)r * LIFT_PASSES, sc)) return -1;
     if (checksum) { /* of the last result: the rows, the columns and the counts, every word weighted by its place */
         LiftBuf& l = c->lift;
-        unsigned long long s = 0, place = 1;
         std::vector<long long> rows((size_t)l.n_units + 1);
         HIPCK(hipMemcpy(rows.data(), l.rows.rowptr, rows.size() * sizeof(long long), hipMemcpyDeviceToHost));
-        for (long long v : rows) s += (unsigned long long)v * place++;
+        unsigned long long s = weighted_checksum(rows.data(), rows.size()), place = rows.size() + 1; /* behind the rows: column, count, column, ... */
         const int64_t piece = 1 << 22;
         std::vector<int32_t> col((size_t)std::min<int64_t>(l.n_entries, piece));
         std::vector<int64_t> cnt(col.size());

@@ -176,9 +176,7 @@ extern "C" int ig_debug_orientation_support_time(ig_ctx* c, int32_t window, int3
         if (n_seg > 0) HIPCK(hipMemcpy(h.data(), o.expq, 2 * (size_t)n_seg * sizeof(long long), hipMemcpyDeviceToHost));
     }
     if (checksum) { /* of the last pass: every word weighted by its place: every form of a pass must agree on it */
-        unsigned long long s = 0;
-        for (size_t k = 0; k < h.size(); k++) s += (unsigned long long)h[k] * (unsigned long long)(k + 1);
-        *checksum = (long long)s;
+        *checksum = (long long)weighted_checksum(h.data(), h.size());
     }
     return 0;
 }

@@ -196,10 +196,9 @@ extern "C" int ig_debug_placement_support_time(ig_ctx* c, int32_t window, int32_
     for (int r = 0; r < n; r++)
         if (place_call(c, "ig_debug_placement_support_time", window, min_hosts, ms_n + (size_t)r * PLACE_PASSES, oi, ol, sc)) return -1;
     if (checksum) { /* of the last result: every word of the arrays weighted by its place */
-        unsigned long long s = 0, place = 1;
-        for (int32_t v : vi) s += (unsigned long long)(long long)v * place++;
-        for (int64_t v : vl) s += (unsigned long long)v * place++;
-        *checksum = (long long)s;
+        std::vector<long long> all(vi.begin(), vi.end());
+        all.insert(all.end(), vl.begin(), vl.end());
+        *checksum = (long long)weighted_checksum(all.data(), all.size());
     }
     return 0;
 }

@@ -46,10 +46,7 @@ __global__ void __launch_bounds__(BAL_THREADS) k_bal_emit(const int* __restrict_
                                                           unsigned long long* __restrict__ out_sc)
 {
     __shared__ unsigned long long sc[BAL_NS];
-    if (!SCATTER) {
-        if (threadIdx.x < BAL_NS) sc[threadIdx.x] = 0ull;
-        __syncthreads();
-    }
+    if (!SCATTER) class_zero<BAL_NS>(sc);
     unsigned long long r_unpl = 0, r_within = 0, r_band = 0, r_kept = 0, r_ent = 0;
     const long long stride = (long long)gridDim.x * BAL_THREADS;
     for (long long k = (long long)blockIdx.x * BAL_THREADS + threadIdx.x; k < Z; k += stride) {
@@ -79,7 +76,7 @@ __global__ void __launch_bounds__(BAL_THREADS) k_bal_emit(const int* __restrict_
     if (r_band) atomicAdd(&sc[BAL_BAND_OBS], r_band);
     if (r_kept) atomicAdd(&sc[BAL_KEPT_OBS], r_kept);
     if (r_ent) atomicAdd(&sc[BAL_ENTRIES], r_ent);
-    rows_flush<BAL_NS>(sc, out_sc);
+    class_flush<BAL_NS>(sc, out_sc);
 }
 
 /* the rows and what a term of the sum is made of.  RAW: the term is values[e] (ig_debug_lane_sums: the ordered sum over caller data);

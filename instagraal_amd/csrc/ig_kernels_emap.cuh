@@ -31,27 +31,6 @@ __device__ __forceinline__ void emap_load_tab(double* tab)
     __syncthreads();
 }
 
-__device__ __forceinline__ unsigned long long emap_wave_sum(unsigned long long v)
-{
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) v += __shfl_xor(v, d, 64);
-    return v;
-}
-__device__ __forceinline__ unsigned long long emap_wave_max(unsigned long long v)
-{
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const unsigned long long o = __shfl_xor(v, d, 64);
-        v = o > v ? o : v;
-    }
-    return v;
-}
-/* (the maximum only grows: whoever cannot raise what is there already leaves the word alone) */
-__device__ __forceinline__ void emap_raise(unsigned long long* maxq, unsigned long long mx)
-{
-    if (mx > *(volatile unsigned long long*)maxq) atomicMax(maxq, mx);
-}
-
 /* what every pair at or beyond d_max gets: ig_rippe's clamp of 0 from below by v_inter */
 __device__ __forceinline__ long long emap_q_far(const ig_params& p) { return ig_quantize((double)ig_fmaxf(0.0f, p.v_inter)); }
 
@@ -77,8 +56,8 @@ __global__ void __launch_bounds__(EMAP_THREADS) k_emap_count(const float* __rest
             cnt[a] = (unsigned long long)(max(end - 1, r) / bin - a + 1);
         }
     }
-    lin = emap_wave_sum(lin);
-    ring = emap_wave_sum(ring);
+    lin = wave_sum_u64(lin);
+    ring = wave_sum_u64(ring);
     if ((threadIdx.x & 63) == 0) {
         if (lin) atomicAdd(&sc[EMAP_SC_LINEAR], lin);
         if (ring) atomicAdd(&sc[EMAP_SC_RING], ring);
@@ -126,8 +105,8 @@ __global__ void __launch_bounds__(EMAP_THREADS) k_emap_rows(const float* __restr
             if (acc) atomicAdd(&cis_q[row + pb], acc);
         }
     }
-    mx = emap_wave_max(mx);
-    if ((threadIdx.x & 63) == 0) emap_raise(&sc[EMAP_SC_MAXQ], mx);
+    mx = wave_max_u64(mx);
+    if ((threadIdx.x & 63) == 0) raise_max(&sc[EMAP_SC_MAXQ], mx);
 }
 
 /* The work list of the tile form from the exclusive prefix sums off[0 .. side] of k_emap_count's counts: entry t is the tile
@@ -182,7 +161,7 @@ __global__ void __launch_bounds__(EMAP_THREADS) k_emap_tiles(const int2* __restr
                 cis_pairs[cell] = pairs;
                 ring_pairs[cell] = 0ull;
                 atomicAdd(&sc[EMAP_SC_TILES_CONST], 1ull);
-                emap_raise(&sc[EMAP_SC_MAXQ], (unsigned long long)(q < 0 ? -q : q));
+                raise_max(&sc[EMAP_SC_MAXQ], (unsigned long long)(q < 0 ? -q : q));
             }
             return;
         }
@@ -231,10 +210,10 @@ __global__ void __launch_bounds__(EMAP_THREADS) k_emap_tiles(const int2* __restr
             mx = aq > mx ? aq : mx;
         }
     }
-    acc = emap_wave_sum(acc);
-    n_cis = emap_wave_sum(n_cis);
-    n_ring = emap_wave_sum(n_ring);
-    mx = emap_wave_max(mx);
+    acc = wave_sum_u64(acc);
+    n_cis = wave_sum_u64(n_cis);
+    n_ring = wave_sum_u64(n_ring);
+    mx = wave_max_u64(mx);
     if (lane == 0) {
         red[wave][0] = acc;
         red[wave][1] = n_cis;
@@ -253,7 +232,7 @@ __global__ void __launch_bounds__(EMAP_THREADS) k_emap_tiles(const int2* __restr
         cis_pairs[cell] = n_cis;
         ring_pairs[cell] = n_ring;
         atomicAdd(&sc[EMAP_SC_TILES_EVAL], 1ull);
-        emap_raise(&sc[EMAP_SC_MAXQ], mx);
+        raise_max(&sc[EMAP_SC_MAXQ], mx);
     }
 }
 
@@ -264,6 +243,6 @@ __global__ void __launch_bounds__(EMAP_THREADS) k_emap_checksum(const unsigned l
     unsigned long long s = 0;
     for (long long k = (long long)blockIdx.x * EMAP_THREADS + threadIdx.x; k < n; k += (long long)gridDim.x * EMAP_THREADS)
         s += img[k] * (unsigned long long)(k + 1);
-    s = emap_wave_sum(s);
+    s = wave_sum_u64(s);
     if ((threadIdx.x & 63) == 0 && s) atomicAdd(out, s);
 }

@@ -110,21 +110,21 @@ __global__ void __launch_bounds__(GAP_THREADS) k_gap_observed(const int* __restr
 {
     __shared__ unsigned long long sc[GAP_N_OBS];
     __shared__ float sg[GAP_MAX_GAPS];
-    if (threadIdx.x < GAP_N_OBS) sc[threadIdx.x] = 0ull;
     if (threadIdx.x < GAP_MAX_GAPS) sg[threadIdx.x] = threadIdx.x < n_gaps ? gaps[threadIdx.x] : 0.0f;
-    __syncthreads();
+    class_zero<GAP_N_OBS>(sc); /* (its barrier covers the gaps too) */
     const ig_params p = g->par[0];
     unsigned long long r_unpl = 0, r_trans = 0, r_ring = 0, r_counted = 0, r_uncounted = 0, r_contrib = 0, mx = 0;
     const long long stride = (long long)gridDim.x * GAP_THREADS;
     for (long long k = (long long)blockIdx.x * GAP_THREADS + threadIdx.x; k < Z; k += stride) {
         const int i = crow[k];
-        if (world != 1 && i % world != rank) continue;
+        if (!contact_is_mine(i, rank, world)) continue;
         const int2 e = cc[k];
         const int4 a = rec[i], b = rec[e.x];
         const unsigned long long cv = (unsigned long long)(long long)e.y;
-        if (a.w < 0 || b.w < 0) r_unpl += cv;
-        else if (a.z != b.z) r_trans += cv;
-        else if (__int_as_float(a.y) != 0.0f) r_ring += cv;
+        const GenomePair cls = genome_pair_class(a, b);
+        if (cls == PAIR_UNPLACED) r_unpl += cv;
+        else if (cls == PAIR_TRANS) r_trans += cv;
+        else if (cls == PAIR_RING) r_ring += cv;
         else {
             const int pa = min(a.w, b.w), pb = max(a.w, b.w);
             const int lo = nj[pa], hi = pb - pa <= window ? nj[pb] : lo;
@@ -151,18 +151,9 @@ __global__ void __launch_bounds__(GAP_THREADS) k_gap_observed(const int* __restr
     if (r_counted) atomicAdd(&sc[GAP_COUNTED], r_counted);
     if (r_uncounted) atomicAdd(&sc[GAP_UNCOUNTED], r_uncounted);
     if (r_contrib) atomicAdd(&sc[GAP_CONTRIB], r_contrib);
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const unsigned long long o = __shfl_xor(mx, d, 64);
-        mx = o > mx ? o : mx;
-    }
-    /* (the maximum only grows: a wave that cannot raise what is there already leaves the word alone) */
-    if ((threadIdx.x & 63) == 0 && mx > *(volatile unsigned long long*)&out_sc[GAP_DEV_MAXL]) atomicMax(&out_sc[GAP_DEV_MAXL], mx);
-    __syncthreads();
-    if (threadIdx.x < GAP_N_OBS) {
-        const unsigned long long v = sc[threadIdx.x];
-        if (v) atomicAdd(&out_sc[threadIdx.x], v);
-    }
+    mx = wave_max_u64(mx);
+    if ((threadIdx.x & 63) == 0) raise_max(&out_sc[GAP_DEV_MAXL], mx);
+    class_flush<GAP_N_OBS>(sc, out_sc);
 }
 
 /* The model part, no atomics on the arrays.  A judged junction j with `left` positions in front and `right` behind has the pairs
@@ -220,7 +211,7 @@ __global__ void __launch_bounds__(GAP_THREADS) k_gap_model(const float* __restri
             mx = ae > mx ? ae : mx;
         }
 #pragma unroll
-        for (int d = 1; d < 64; d <<= 1) acc += __shfl_xor(acc, d, 64);
+        for (int d = 1; d < 64; d <<= 1) acc += __shfl_xor(acc, d, 64); /* (inline: through wave_sum_u64 the loop over the gaps is scheduled another way) */
         if (G == 64) {
             if (mine && sub == 0) expq[(size_t)s * n_gaps + q] = acc;
         } else if ((threadIdx.x & 63) == 0)
@@ -234,11 +225,6 @@ __global__ void __launch_bounds__(GAP_THREADS) k_gap_model(const float* __restri
             expq[(size_t)s * n_gaps + threadIdx.x] = a;
         }
     }
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const unsigned long long o = __shfl_xor(mx, d, 64);
-        mx = o > mx ? o : mx;
-    }
-    /* (the maximum only grows: a wave that cannot raise what is there already leaves the word alone) */
-    if ((threadIdx.x & 63) == 0 && mx > *(volatile unsigned long long*)maxq) atomicMax(maxq, mx);
+    mx = wave_max_u64(mx);
+    if ((threadIdx.x & 63) == 0) raise_max(maxq, mx);
 }

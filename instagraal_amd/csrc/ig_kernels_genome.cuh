@@ -36,6 +36,18 @@ __global__ void k_law_records(Tables t, const int* __restrict__ pix, int M, int4
     rec[s] = make_int4(__float_as_int(t.dist[s]), __float_as_int(t.stot[s]), t.cp[s].x, pix[s]);
 }
 
+/* what the records a, b of a contact's two ends say of it, the first that fits: an end that is not placed; two contigs; one contig
+ * that is a ring (s_tot != 0: a pair on it has two separations); one linear contig, the only class with a separation and with
+ * positions pa <= pb.  Every pass over the contacts that reads the records keeps its own counters per class. */
+enum GenomePair { PAIR_UNPLACED, PAIR_TRANS, PAIR_RING, PAIR_CIS };
+__device__ __forceinline__ GenomePair genome_pair_class(const int4& a, const int4& b)
+{
+    if (a.w < 0 || b.w < 0) return PAIR_UNPLACED;
+    if (a.z != b.z) return PAIR_TRANS;
+    if (__int_as_float(a.y) != 0.0f) return PAIR_RING;
+    return PAIR_CIS;
+}
+
 /* the same by POSITION r of the genome order (order[r] = sub-fragment): ds[r] = its dist, meta[r] = (first position of its contig,
  * sub-fragments of its contig; negated: a ring) */
 __global__ void k_law_sorted(Tables t, const int* __restrict__ order, int M, int T, float* __restrict__ ds, int2* __restrict__ meta)

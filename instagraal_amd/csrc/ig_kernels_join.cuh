@@ -100,10 +100,7 @@ __global__ void __launch_bounds__(JOIN_THREADS) k_join_emit(const int* __restric
                                                             unsigned long long* __restrict__ out_sc, int rank, int world)
 {
     __shared__ unsigned long long sc[JOIN_NS];
-    if (!SCATTER) {
-        if (threadIdx.x < JOIN_NS) sc[threadIdx.x] = 0ull;
-        __syncthreads();
-    }
+    if (!SCATTER) class_zero<JOIN_NS>(sc);
     const int lane = threadIdx.x & 63;
     unsigned long long r_in = 0, r_out = 0, r_cis = 0, r_ring = 0, r_unpl = 0, r_contrib = 0, r_ent = 0;
     const long long stride = (long long)gridDim.x * JOIN_THREADS;
@@ -113,7 +110,7 @@ __global__ void __launch_bounds__(JOIN_THREADS) k_join_emit(const int* __restric
         bool live = false; /* a trans contact between two linear placed contigs */
         if (k < Z) {
             const int i = crow[k];
-            if (world == 1 || i % world == rank) {
+            if (contact_is_mine(i, rank, world)) {
                 const int2 e = cc[k];
                 const int4 a = rec[i], b = rec[e.x];
                 const unsigned long long cv = (unsigned long long)(long long)e.y;
@@ -159,7 +156,7 @@ __global__ void __launch_bounds__(JOIN_THREADS) k_join_emit(const int* __restric
     if (r_unpl) atomicAdd(&sc[JOIN_UNPLACED_OBS], r_unpl);
     if (r_contrib) atomicAdd(&sc[JOIN_CONTRIBUTIONS], r_contrib);
     if (r_ent) atomicAdd(&sc[JOIN_ENTRIES], r_ent);
-    rows_flush<JOIN_NS>(sc, out_sc);
+    class_flush<JOIN_NS>(sc, out_sc);
 }
 
 /* pairs of a link between ends of contigs of na and nb positions: depth u = 0 .. ua - 1, ua = min(w, na), pairs with
@@ -226,6 +223,7 @@ __global__ void __launch_bounds__(JOIN_THREADS) k_join_model(const unsigned long
             }
         }
     }
+    /* (one loop for the maximum and the sum: their shuffles interleave; wave_max_u64 behind wave_sum_u64 measured slower) */
 #pragma unroll
     for (int d = 1; d < 64; d <<= 1) {
         const unsigned long long o = __shfl_xor(mx, d, 64);
@@ -236,6 +234,5 @@ __global__ void __launch_bounds__(JOIN_THREADS) k_join_model(const unsigned long
         pairs[link] = (unsigned long long)P;
         expected_q[link] = acc;
     }
-    /* (the maximum only grows: a wave that cannot raise what is there already leaves the word alone) */
-    if ((threadIdx.x & 63) == 0 && mx > *(volatile unsigned long long*)maxq) atomicMax(maxq, mx);
+    if ((threadIdx.x & 63) == 0) raise_max(maxq, mx);
 }

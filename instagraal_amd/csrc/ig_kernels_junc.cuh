@@ -32,8 +32,8 @@
  * COMBINE = false, the yardstick: one atomic per end.
  *
  * COMBINE = true: the lanes of a wave hold 64 consecutive contacts, mostly of one row, whose + ends are then ONE word: equal +
- * destinations next to each other are summed inside the wave first (the run-head ballot and the segmented shuffle scan of
- * k_contact_map) and only the head of a run issues the atomic.  The - ends are neighbouring words and go out as they are.
+ * destinations next to each other are summed inside the wave first (wave_runs and wave_run_sum, ig_kernels_wave.cuh) and only
+ * the head of a run issues the atomic.  The - ends are neighbouring words and go out as they are.
  * V: int where 64 counts cannot overflow one, else long long.
  *
  * The five classes of contact are summed in registers and reach memory once per workgroup.  A sharded handle takes the rows
@@ -44,8 +44,7 @@ __global__ void __launch_bounds__(JUNC_THREADS) k_junc_observed(const int* __res
                                                                 unsigned long long* __restrict__ out_sc, int rank, int world)
 {
     __shared__ unsigned long long sc[JUNC_N_OBS];
-    if (threadIdx.x < JUNC_N_OBS) sc[threadIdx.x] = 0ull;
-    __syncthreads();
+    class_zero<JUNC_N_OBS>(sc);
     const int lane = threadIdx.x & 63;
     unsigned long long r_in = 0, r_beyond = 0, r_trans = 0, r_ring = 0, r_unpl = 0;
     const long long stride = (long long)gridDim.x * JUNC_THREADS;
@@ -55,13 +54,14 @@ __global__ void __launch_bounds__(JUNC_THREADS) k_junc_observed(const int* __res
         unsigned long long cv = 0;
         if (k < Z) {
             const int i = crow[k];
-            if (world == 1 || i % world == rank) {
+            if (contact_is_mine(i, rank, world)) {
                 const int2 e = cc[k];
                 const int4 a = rec[i], b = rec[e.x];
                 cv = (unsigned long long)(long long)e.y;
-                if (a.w < 0 || b.w < 0) r_unpl += cv;
-                else if (a.z != b.z) r_trans += cv;
-                else if (__int_as_float(a.y) != 0.0f) r_ring += cv;
+                const GenomePair cls = genome_pair_class(a, b);
+                if (cls == PAIR_UNPLACED) r_unpl += cv;
+                else if (cls == PAIR_TRANS) r_trans += cv;
+                else if (cls == PAIR_RING) r_ring += cv;
                 else {
                     const int pa = min(a.w, b.w), pb = max(a.w, b.w);
                     if (pb - pa <= window) {
@@ -79,30 +79,16 @@ __global__ void __launch_bounds__(JUNC_THREADS) k_junc_observed(const int* __res
             continue;
         }
         V v = plus >= 0 ? (V)(long long)cv : (V)0;
-        const int left = __shfl_up(plus, 1, 64);
-        const bool head = lane == 0 || left != plus;
-        const unsigned long long heads = __ballot(head);
-        if (heads != ~0ull) {
-            const unsigned long long above = lane == 63 ? 0ull : heads >> (lane + 1);
-            const int run_end = above ? lane + __ffsll((long long)above) : 64; /* first lane behind this lane's run */
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) {
-                const V o = __shfl_down(v, d, 64);
-                if (lane + d < run_end) v += o;
-            }
-        }
-        if (head && plus >= 0 && v != 0) atomicAdd(&diff[plus], (unsigned long long)(long long)v);
+        const WaveRuns runs = wave_runs(plus, lane);
+        v = wave_run_sum<V>(runs, v, lane);
+        if (runs.head && plus >= 0 && v != 0) atomicAdd(&diff[plus], (unsigned long long)(long long)v);
     }
     if (r_in) atomicAdd(&sc[JUNC_IN_OBS], r_in);
     if (r_beyond) atomicAdd(&sc[JUNC_BEYOND_OBS], r_beyond);
     if (r_trans) atomicAdd(&sc[JUNC_TRANS_OBS], r_trans);
     if (r_ring) atomicAdd(&sc[JUNC_RING_OBS], r_ring);
     if (r_unpl) atomicAdd(&sc[JUNC_UNPLACED_OBS], r_unpl);
-    __syncthreads();
-    if (threadIdx.x < JUNC_N_OBS) {
-        const unsigned long long v = sc[threadIdx.x];
-        if (v) atomicAdd(&out_sc[threadIdx.x], v);
-    }
+    class_flush<JUNC_N_OBS>(sc, out_sc);
 }
 
 /* the internal junctions: positions of a placed contig that is not a ring, its first left out */
@@ -160,6 +146,7 @@ __global__ void __launch_bounds__(JUNC_THREADS) k_junc_model(const float* __rest
             }
         }
     }
+    /* (one loop for the maximum and the sum: their shuffles interleave; wave_max_u64 behind wave_sum_u64 measured slower) */
 #pragma unroll
     for (int d = 1; d < 64; d <<= 1) {
         const unsigned long long o = __shfl_xor(mx, d, 64);
@@ -174,6 +161,5 @@ __global__ void __launch_bounds__(JUNC_THREADS) k_junc_model(const float* __rest
             d_exp[0] = 0ull;
         }
     }
-    /* (the maximum only grows: a wave that cannot raise what is there already leaves the word alone) */
-    if ((threadIdx.x & 63) == 0 && mx > *(volatile unsigned long long*)maxq) atomicMax(maxq, mx);
+    if ((threadIdx.x & 63) == 0) raise_max(maxq, mx);
 }

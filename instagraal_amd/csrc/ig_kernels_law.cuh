@@ -50,18 +50,15 @@ __device__ __forceinline__ void law_lds_setup(const float* __restrict__ edges, i
     __syncthreads();
 }
 
-/* the workgroup's histogram and scalars to memory: native 64-bit atomics, non-zero entries only */
+/* the workgroup's scalars and histogram to memory: native 64-bit atomics, non-zero entries only (class_flush's barrier stands in
+ * front of both) */
 __device__ __forceinline__ void law_lds_flush(const unsigned long long* hist, const unsigned long long* sc, int nb, unsigned long long* __restrict__ out_hist,
                                               unsigned long long* __restrict__ out_sc)
 {
-    __syncthreads();
+    class_flush<LAW_NS>(sc, out_sc);
     for (int i = threadIdx.x; i < nb; i += blockDim.x) {
         const unsigned long long v = hist[i];
         if (v) atomicAdd(&out_hist[i], v);
-    }
-    if (threadIdx.x < LAW_NS) {
-        const unsigned long long v = sc[threadIdx.x];
-        if (v) atomicAdd(&out_sc[threadIdx.x], v);
     }
 }
 
@@ -86,14 +83,15 @@ __global__ void __launch_bounds__(LAW_THREADS) k_law_observed(const int* __restr
     const long long stride = (long long)gridDim.x * LAW_THREADS;
     for (long long k = (long long)blockIdx.x * LAW_THREADS + threadIdx.x; k < Z; k += stride) {
         const int i = crow[k];
-        if (world != 1 && i % world != rank) continue;
+        if (!contact_is_mine(i, rank, world)) continue;
         const int2 c = cc[k];
         const int4 a = rec[i], b = rec[c.x];
         const unsigned long long v = (unsigned long long)(long long)c.y;
+        const GenomePair cls = genome_pair_class(a, b);
         int which; /* >= 0: a bin, else -1 - scalar */
-        if (a.w < 0 || b.w < 0) which = -1 - LAW_UNPLACED_OBS;
-        else if (a.z != b.z) which = -1 - LAW_TRANS_OBS;
-        else if (__int_as_float(a.y) != 0.0f) which = -1 - LAW_RING_OBS;
+        if (cls == PAIR_UNPLACED) which = -1 - LAW_UNPLACED_OBS;
+        else if (cls == PAIR_TRANS) which = -1 - LAW_TRANS_OBS;
+        else if (cls == PAIR_RING) which = -1 - LAW_RING_OBS;
         else {
             const float s = fabsf(__int_as_float(a.x) - __int_as_float(b.x));
             const int ub = law_upper_bound(e, n_edges, s);

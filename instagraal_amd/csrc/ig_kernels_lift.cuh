@@ -56,10 +56,7 @@ __global__ void __launch_bounds__(LIFT_THREADS) k_lift_pass(const int* __restric
                                                             unsigned long long* __restrict__ out_sc, int rank, int world)
 {
     __shared__ unsigned long long sc[LIFT_NS];
-    if (!SCATTER) {
-        if (threadIdx.x < LIFT_NS) sc[threadIdx.x] = 0ull;
-        __syncthreads();
-    }
+    if (!SCATTER) class_zero<LIFT_NS>(sc);
     const int lane = threadIdx.x & 63;
     unsigned long long r_in = 0, r_kept = 0, r_ckept = 0, r_unpl = 0, r_cunpl = 0;
     const long long stride = (long long)gridDim.x * LIFT_THREADS;
@@ -68,7 +65,7 @@ __global__ void __launch_bounds__(LIFT_THREADS) k_lift_pass(const int* __restric
         int lo = -1, hi = 0, cnt = 0; /* lo = -1: nothing to place */
         if (k < Z) {
             const int i = crow[k];
-            if (world == 1 || i % world == rank) {
+            if (contact_is_mine(i, rank, world)) {
                 const int2 e = cc[k];
                 const int a = key[i], b = key[e.x];
                 const unsigned long long cv = (unsigned long long)(long long)e.y;
@@ -98,6 +95,6 @@ __global__ void __launch_bounds__(LIFT_THREADS) k_lift_pass(const int* __restric
     if (r_ckept) atomicAdd(&sc[LIFT_CONTACTS_KEPT], r_ckept);
     if (r_unpl) atomicAdd(&sc[LIFT_ENTRIES_UNPLACED], r_unpl);
     if (r_cunpl) atomicAdd(&sc[LIFT_CONTACTS_UNPLACED], r_cunpl);
-    rows_flush<LIFT_NS>(sc, out_sc);
+    class_flush<LIFT_NS>(sc, out_sc);
 }
 

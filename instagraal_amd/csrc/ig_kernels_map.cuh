@@ -19,11 +19,9 @@
  *
  * COMBINE = true: the image is symmetric, so only image[min][max] is accumulated (k_map_mirror writes the other half and doubles
  * the diagonal), and equal destinations are combined inside the wave first: the lanes of a wave hold 64 CONSECUTIVE contacts, i.e.
- * mostly one row, and neighbouring columns fall into the same pixel -- runs of lanes with an equal key.  The run heads are found
- * with one ballot, every lane learns where its run ends from the ballot's bits, a segmented shuffle-down scan (6 steps whatever
- * the number of runs) leaves each run's total in its head, and only the heads issue an atomic.  A wave whose 64 keys all differ
- * from their neighbours skips the scan.  V: int where 64 counts cannot overflow one (the host knows the largest count), else
- * long long. */
+ * mostly one row, and neighbouring columns fall into the same pixel -- runs of lanes with an equal key.  wave_runs finds them,
+ * wave_run_sum leaves each run's total in its head (ig_kernels_wave.cuh), and only the heads issue an atomic.  V: int where 64
+ * counts cannot overflow one (the host knows the largest count), else long long. */
 template <bool COMBINE, typename V>
 __global__ void __launch_bounds__(MAP_THREADS) k_contact_map(const int* __restrict__ crow, const int2* __restrict__ cc, long long Z,
                                                              const int* __restrict__ pix, int side, unsigned long long* __restrict__ image,
@@ -40,7 +38,7 @@ __global__ void __launch_bounds__(MAP_THREADS) k_contact_map(const int* __restri
         if (k < Z) {
             const int i = crow[k];
             const int2 e = cc[k];
-            if (world == 1 || i % world == rank) {
+            if (contact_is_mine(i, rank, world)) {
                 pi = pix[i];
                 pj = pix[e.x];
                 if (pi >= 0 && pj >= 0) {
@@ -58,19 +56,9 @@ __global__ void __launch_bounds__(MAP_THREADS) k_contact_map(const int* __restri
             }
             continue;
         }
-        const unsigned long long left = __shfl_up(key, 1, 64);
-        const bool head = lane == 0 || left != key;
-        const unsigned long long heads = __ballot(head);
-        if (heads != ~0ull) {
-            const unsigned long long above = lane == 63 ? 0ull : heads >> (lane + 1);
-            const int run_end = above ? lane + __ffsll((long long)above) : 64; /* first lane behind this lane's run */
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) {
-                const V o = __shfl_down(v, d, 64);
-                if (lane + d < run_end) v += o;
-            }
-        }
-        if (head && key != none && v != 0) atomicAdd(&image[key], (unsigned long long)(long long)v);
+        const WaveRuns runs = wave_runs(key, lane);
+        v = wave_run_sum<V>(runs, v, lane);
+        if (runs.head && key != none && v != 0) atomicAdd(&image[key], (unsigned long long)(long long)v);
     }
 }
 

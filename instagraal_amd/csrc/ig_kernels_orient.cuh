@@ -93,8 +93,8 @@ __global__ void __launch_bounds__(ORIENT_THREADS) k_orient_paint(const int* __re
  *
  * COMBINE = true: the lanes of a wave hold 64 consecutive contacts, mostly of one row, and the end of a contact that lies at its ROW
  * mostly falls into the same arm with the other end in the same flank: equal destinations of the row end next to each other are
- * summed inside the wave first (the run-head ballot and the segmented shuffle scan of k_junc_observed) and only the head of a run
- * issues the atomic.  The column end goes out as it is.  V: int where 64 counts cannot overflow one, else long long.
+ * summed inside the wave first (wave_runs and wave_run_sum, ig_kernels_wave.cuh) and only the head of a run issues the atomic.
+ * The column end goes out as it is.  V: int where 64 counts cannot overflow one, else long long.
  *
  * The six classes of contact and the entries are summed in registers and reach memory once per workgroup.  A sharded handle takes
  * the rows i % world == rank: the ranks' quadrants and class sums add up. */
@@ -104,8 +104,7 @@ __global__ void __launch_bounds__(ORIENT_THREADS) k_orient_observed(const int* _
                                                                     unsigned long long* __restrict__ obs, unsigned long long* __restrict__ out_sc, int rank, int world)
 {
     __shared__ unsigned long long sc[ORIENT_N_OBS];
-    if (threadIdx.x < ORIENT_N_OBS) sc[threadIdx.x] = 0ull;
-    __syncthreads();
+    class_zero<ORIENT_N_OBS>(sc);
     const int lane = threadIdx.x & 63;
     unsigned long long r_unpl = 0, r_trans = 0, r_ring = 0, r_within = 0, r_counted = 0, r_uncounted = 0, r_entries = 0;
     const long long stride = (long long)gridDim.x * ORIENT_THREADS;
@@ -115,13 +114,14 @@ __global__ void __launch_bounds__(ORIENT_THREADS) k_orient_observed(const int* _
         unsigned long long cv = 0;
         if (k < Z) {
             const int i = crow[k];
-            if (world == 1 || i % world == rank) {
+            if (contact_is_mine(i, rank, world)) {
                 const int2 e = cc[k];
                 const int4 a = rec[i], b = rec[e.x];
                 cv = (unsigned long long)(long long)e.y;
-                if (a.w < 0 || b.w < 0) r_unpl += cv;
-                else if (a.z != b.z) r_trans += cv;
-                else if (__int_as_float(a.y) != 0.0f) r_ring += cv;
+                const GenomePair cls = genome_pair_class(a, b);
+                if (cls == PAIR_UNPLACED) r_unpl += cv;
+                else if (cls == PAIR_TRANS) r_trans += cv;
+                else if (cls == PAIR_RING) r_ring += cv;
                 else {
                     const int pa = min(a.w, b.w), pb = max(a.w, b.w);
                     const int sa = seg[pa], sb = seg[pb];
@@ -153,19 +153,9 @@ __global__ void __launch_bounds__(ORIENT_THREADS) k_orient_observed(const int* _
             continue;
         }
         V v = d_row >= 0 ? (V)(long long)cv : (V)0;
-        const int left = __shfl_up(d_row, 1, 64);
-        const bool head = lane == 0 || left != d_row;
-        const unsigned long long heads = __ballot(head);
-        if (heads != ~0ull) {
-            const unsigned long long above = lane == 63 ? 0ull : heads >> (lane + 1);
-            const int run_end = above ? lane + __ffsll((long long)above) : 64; /* first lane behind this lane's run */
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) {
-                const V o = __shfl_down(v, d, 64);
-                if (lane + d < run_end) v += o;
-            }
-        }
-        if (head && d_row >= 0 && v != 0) atomicAdd(&obs[d_row], (unsigned long long)(long long)v);
+        const WaveRuns runs = wave_runs(d_row, lane);
+        v = wave_run_sum<V>(runs, v, lane);
+        if (runs.head && d_row >= 0 && v != 0) atomicAdd(&obs[d_row], (unsigned long long)(long long)v);
     }
     if (r_unpl) atomicAdd(&sc[ORIENT_UNPLACED], r_unpl);
     if (r_trans) atomicAdd(&sc[ORIENT_TRANS], r_trans);
@@ -174,11 +164,7 @@ __global__ void __launch_bounds__(ORIENT_THREADS) k_orient_observed(const int* _
     if (r_counted) atomicAdd(&sc[ORIENT_COUNTED], r_counted);
     if (r_uncounted) atomicAdd(&sc[ORIENT_UNCOUNTED], r_uncounted);
     if (r_entries) atomicAdd(&sc[ORIENT_ENTRIES], r_entries);
-    __syncthreads();
-    if (threadIdx.x < ORIENT_N_OBS) {
-        const unsigned long long v = sc[threadIdx.x];
-        if (v) atomicAdd(&out_sc[threadIdx.x], v);
-    }
+    class_flush<ORIENT_N_OBS>(sc, out_sc);
 }
 
 /* The model part, no atomics on the arrays.  With q(i, k) = ig_quantize((double) ig_rippe(fabsf(ds_i - ds_k), p)) under the parameter
@@ -222,6 +208,7 @@ __global__ void __launch_bounds__(ORIENT_THREADS) k_orient_model(const float* __
             }
         }
     }
+    /* (one loop for the maximum and the sums: their shuffles interleave, as in k_junc_model) */
 #pragma unroll
     for (int d = 1; d < 64; d <<= 1) {
         const unsigned long long o = __shfl_xor(mx, d, 64);
@@ -251,6 +238,5 @@ __global__ void __launch_bounds__(ORIENT_THREADS) k_orient_model(const float* __
             expq[2 * (size_t)s + 1] = c;
         }
     }
-    /* (the maximum only grows: a wave that cannot raise what is there already leaves the word alone) */
-    if ((threadIdx.x & 63) == 0 && mx > *(volatile unsigned long long*)maxq) atomicMax(maxq, mx);
+    if ((threadIdx.x & 63) == 0) raise_max(maxq, mx);
 }

@@ -68,10 +68,7 @@ __global__ void __launch_bounds__(PLACE_THREADS) k_place_emit(const int* __restr
                                                               unsigned long long n_ent, unsigned long long* __restrict__ out_sc)
 {
     __shared__ unsigned long long sc[PLACE_NS];
-    if (!SCATTER) {
-        if (threadIdx.x < PLACE_NS) sc[threadIdx.x] = 0ull;
-        __syncthreads();
-    }
+    if (!SCATTER) class_zero<PLACE_NS>(sc);
     unsigned long long r_unpl = 0, r_ring = 0, r_within = 0, r_counted = 0, r_ent = 0;
     const long long stride = (long long)gridDim.x * PLACE_THREADS;
     for (long long k = (long long)blockIdx.x * PLACE_THREADS + threadIdx.x; k < Z; k += stride) {
@@ -104,7 +101,7 @@ __global__ void __launch_bounds__(PLACE_THREADS) k_place_emit(const int* __restr
     if (r_within) atomicAdd(&sc[PLACE_WITHIN_OBS], r_within);
     if (r_counted) atomicAdd(&sc[PLACE_COUNTED_OBS], r_counted);
     if (r_ent) atomicAdd(&sc[PLACE_ENTRIES], r_ent);
-    rows_flush<PLACE_NS>(sc, out_sc);
+    class_flush<PLACE_NS>(sc, out_sc);
 }
 
 /* a guest's row and what the rule needs of the guest */

@@ -127,38 +127,23 @@ struct LiftLong { /* a long row: where it lies in the entries, in the scratch bu
 
 __device__ __forceinline__ unsigned long long lift_pack(int col, int cnt) { return ((unsigned long long)(unsigned)col << 32) | (unsigned long long)(unsigned)cnt; }
 
-/* ---- the two idioms of an emit kernel (k_lift_pass, k_join_emit, k_place_emit) */
+/* ---- the slot idiom of an emit kernel (k_lift_pass, k_join_emit; the scalars' head and tail are class_zero and class_flush) */
 
 /* The combined form of taking a slot in row lo (lo < 0: the lane has no entry; whole waves call together): a run of a wave's lanes
- * with an equal lo issues ONE atomic, by its head and for the run's length (the run-head ballot of k_contact_map), and its lanes
+ * with an equal lo (wave_runs, ig_kernels_wave.cuh) issues ONE atomic, by its head and for the run's length, and its lanes
  * take consecutive slots from what the head drew -- neighbouring words, written together.  counter: the rows' counts (SCATTER =
  * false: the returned slot means nothing) or their cursors (SCATTER = true).  The yardstick, one atomic per entry, is one line and
  * stays in the kernels, where the compiler nests the scatter's store under the atomic's own test. */
 template <bool SCATTER>
 __device__ __forceinline__ unsigned long long rows_slot(unsigned long long* counter, int lo, int lane)
 {
-    const int left = __shfl_up(lo, 1, 64);
-    const bool head = lane == 0 || left != lo;
-    const unsigned long long heads = __ballot(head);
-    const unsigned long long above = lane == 63 ? 0ull : heads >> (lane + 1);
-    const int run_end = above ? lane + __ffsll((long long)above) : 64; /* first lane behind this lane's run */
+    const WaveRuns r = wave_runs(lo, lane);
     unsigned long long base = 0;
-    if (head && lo >= 0) base = atomicAdd(&counter[lo], (unsigned long long)(run_end - lane));
+    if (r.head && lo >= 0) base = atomicAdd(&counter[lo], (unsigned long long)(r.run_end - lane));
     if (!SCATTER) return 0ull;
-    const unsigned long long upto = lane == 63 ? heads : heads & ((2ull << lane) - 1ull); /* (lane 0 is a head) */
+    const unsigned long long upto = lane == 63 ? r.heads : r.heads & ((2ull << lane) - 1ull); /* (lane 0 is a head) */
     const int start = 63 - __clzll((long long)upto); /* the head of this lane's run */
     return __shfl(base, start, 64) + (unsigned long long)(lane - start);
-}
-
-/* the tail of a counting pass: the workgroup's NS scalars, summed in LDS, reach memory with one atomic per non-zero word */
-template <int NS>
-__device__ __forceinline__ void rows_flush(const unsigned long long* sc, unsigned long long* __restrict__ out_sc)
-{
-    __syncthreads();
-    if (threadIdx.x < NS) {
-        const unsigned long long v = sc[threadIdx.x];
-        if (v) atomicAdd(&out_sc[threadIdx.x], v);
-    }
 }
 
 /* The work lists of the three forms from the rows' lengths.  FILL = false: the sizes only (cls[]); FILL = true: the lists, each
@@ -380,10 +365,7 @@ __global__ void __launch_bounds__(LIFT_THREADS) k_debug_rows_emit(const int* __r
                                                                   unsigned long long n_ent, unsigned long long* __restrict__ out_sc)
 {
     __shared__ unsigned long long sc[1];
-    if (!SCATTER) {
-        if (threadIdx.x < 1) sc[threadIdx.x] = 0ull;
-        __syncthreads();
-    }
+    if (!SCATTER) class_zero<1>(sc);
     const int lane = threadIdx.x & 63;
     unsigned long long r_ent = 0;
     const long long stride = (long long)gridDim.x * LIFT_THREADS;
@@ -403,5 +385,30 @@ __global__ void __launch_bounds__(LIFT_THREADS) k_debug_rows_emit(const int* __r
     }
     if (SCATTER) return;
     if (r_ent) atomicAdd(&sc[0], r_ent);
-    rows_flush<1>(sc, out_sc);
+    class_flush<1>(sc, out_sc);
+}
+
+/* ---- the tests' kernel over wave_runs / wave_run_sum (ig_debug_wave_runs), shaped like the combined loop of k_junc_observed: entry
+ * k adds val[k] to out[key[k]] (a negative key: no entry), a run of a wave's lanes with an equal key through ONE atomic, by its
+ * head, none where the run's values sum to 0.  *n_atomics: the atomics issued.  V: the type the sums are made in. */
+template <typename V>
+__global__ void __launch_bounds__(LIFT_THREADS) k_debug_wave_runs(const int* __restrict__ key, const long long* __restrict__ val, long long n,
+                                                                  unsigned long long* __restrict__ out, unsigned long long* __restrict__ n_atomics)
+{
+    const int lane = threadIdx.x & 63;
+    unsigned long long issued = 0;
+    const long long stride = (long long)gridDim.x * LIFT_THREADS;
+    const long long nr = (n + 63) & ~63LL; /* whole waves stay in the loop together (the shuffles need every lane) */
+    for (long long k = (long long)blockIdx.x * LIFT_THREADS + threadIdx.x; k < nr; k += stride) {
+        const int dest = k < n ? key[k] : -1;
+        V v = dest >= 0 ? (V)val[k] : (V)0;
+        const WaveRuns runs = wave_runs(dest, lane);
+        v = wave_run_sum<V>(runs, v, lane);
+        if (runs.head && dest >= 0 && v != 0) {
+            atomicAdd(&out[dest], (unsigned long long)(long long)v);
+            issued++;
+        }
+    }
+    issued = wave_sum_u64(issued);
+    if (lane == 0 && issued) atomicAdd(n_atomics, issued);
 }

@@ -18,7 +18,7 @@ SRC = os.path.join(HERE, "csrc", "ig_hip.hip")
 SRC_HOST = os.path.join(HERE, "csrc", "ig_draw.cpp")  # host-only part: the candidate draw
 DEPS = [SRC, SRC_HOST] + [os.path.join(HERE, "csrc", f) for f in ("ig_ops.cuh", "ig_common.cuh", "ig_model.cuh", "ig_kernels_setup.cuh",
                                                           "ig_kernels_score.cuh", "ig_kernels_screen.cuh", "ig_kernels_commit.cuh",
-                                                          "ig_kernels_nuis.cuh", "ig_kernels_genome.cuh", "ig_kernels_rows.cuh", "ig_kernels_map.cuh", "ig_kernels_law.cuh", "ig_kernels_junc.cuh", "ig_kernels_lift.cuh", "ig_kernels_join.cuh", "ig_kernels_emap.cuh", "ig_kernels_place.cuh", "ig_kernels_orient.cuh", "ig_kernels_bal.cuh", "ig_kernels_gap.cuh", "ig_host_core.inc", "ig_host_upload.inc", "ig_host_genome.inc", "ig_host_rows.inc",
+                                                          "ig_kernels_nuis.cuh", "ig_kernels_wave.cuh", "ig_kernels_genome.cuh", "ig_kernels_rows.cuh", "ig_kernels_map.cuh", "ig_kernels_law.cuh", "ig_kernels_junc.cuh", "ig_kernels_lift.cuh", "ig_kernels_join.cuh", "ig_kernels_emap.cuh", "ig_kernels_place.cuh", "ig_kernels_orient.cuh", "ig_kernels_bal.cuh", "ig_kernels_gap.cuh", "ig_host_core.inc", "ig_host_upload.inc", "ig_host_genome.inc", "ig_host_rows.inc",
                                                           "ig_host_map.inc", "ig_host_law.inc", "ig_host_junc.inc", "ig_host_lift.inc", "ig_host_join.inc", "ig_host_emap.inc", "ig_host_place.inc", "ig_host_orient.inc", "ig_host_bal.inc", "ig_host_gap.inc",
                                                           "ig_host_batch.inc", "ig_host_nuis.inc", "ig_host_debug.inc")] + \
        [os.path.join(ROOT, "include", f) for f in ("ig_detmath.h", "ig_detmath_tables.h", "instagraal_hip.h")]
@@ -886,6 +886,19 @@ class Context:
         _ck(lib().ig_debug_rows_fetch(self._h, _p(out["rowptr"]), C.c_int64(out["rowptr"].size), _p(out.get("word")), _p(out.get("col")), _p(out.get("count")),
                                       C.c_int64(out["n_out"])))
         return out
+
+    def debug_wave_runs(self, keys, values, n_dest, wide=False):
+        """the combining idiom of the passes over the contacts over caller data (tests/test_hip_wave_runs.py): entry k adds
+        ``values[k]`` to ``out[keys[k]]`` (a negative key: no entry), a run of a wave's lanes with an equal key through one atomic
+        -> (out int64 [n_dest], the atomics issued).  ``wide``: the sums inside the wave in 64 bits, else in 32"""
+        keys = np.ascontiguousarray(keys, np.int32)
+        values = np.ascontiguousarray(values, np.int64)
+        if keys.ndim != 1 or keys.shape != values.shape:
+            raise HipError("debug_wave_runs: keys and values are vectors of one length")
+        out, n_at = np.zeros(max(int(n_dest), 0), np.int64), C.c_int64()
+        _ck(lib().ig_debug_wave_runs(self._h, _p(keys), _p(values), C.c_int64(keys.size), C.c_int32(int(n_dest)), C.c_int32(int(bool(wide))), _p(out),
+                                     C.byref(n_at)))
+        return out, int(n_at.value)
 
     # ---- join support: which scaffold ends the contacts would link (the rule: join_support.py)
     def join_support(self, window, model=True):
