@@ -13,20 +13,7 @@
 #include <cstring>
 #include <vector>
 
-#define ig_fail_msg harness_copy_of_ig_fail_msg /* ig_common.cuh defines it (for ig_draw.cpp): the library object has the real one */
-#include "../../instagraal_amd/csrc/ig_common.cuh"
-#undef ig_fail_msg
-#include "fake_hip_runtime.h"
-
-#define CHECK(x)                                                                                                           \
-    do {                                                                                                                   \
-        if (!(x)) {                                                                                                        \
-            std::fprintf(stderr, "%s:%d: CHECK failed: %s   [last error: %s]\n", __FILE__, __LINE__, #x, ig_last_error()); \
-            return 1;                                                                                                      \
-        }                                                                                                                  \
-    } while (0)
-
-typedef unsigned long long u64;
+#include "harness_common.h"
 // mirrors of the device structs (ig_kernels_rows.cuh, ig_kernels_bal.cuh: device code, not included here)
 struct Item {
     long long off;
@@ -318,21 +305,9 @@ int main()
     fake_hip::set_model("k_bal_update", model_update);
     fake_hip::set_model("k_bal_var", model_var);
 
-    // a genome of 40 bins of two sub-fragments each in one contig per bin, a few contacts
-    const int N = 40, M = 80;
-    std::vector<float> sub((size_t)M * 4);
-    std::vector<int32_t> soa((size_t)17 * N, 0), row, col, cnt;
-    for (int f = 0; f < N; f++) {
-        const int v[17] = {0, 0, f, 0, 2000, 2, 0, f, -1, -1, 1, 2, 2000, 1, 0, 1, f};
-        for (int k = 0; k < 17; k++) soa[(size_t)k * N + f] = v[k];
-        for (int w = 0; w < 2; w++) {
-            float* s = &sub[(size_t)4 * (2 * f + w)];
-            s[0] = (float)f, s[1] = 0.5f + (float)w, s[2] = 1.5f - (float)w, s[3] = (float)w;
-        }
-    }
-    for (int a = 0; a < M; a++)
-        for (int b = a + 1; b < M; b += 7) row.push_back(a), col.push_back(b), cnt.push_back(1 + (a + b) % 5);
-    const int64_t Z = (int64_t)row.size();
+    const Fixture fx;
+    const int M = Fixture::M;
+    const int64_t Z = fx.Z;
 
     ig_ctx* c = nullptr;
     CHECK(ig_create(0, &c) == 0 && c);
@@ -340,11 +315,7 @@ int main()
     double one = 1.0, out1 = 0.0;
     int32_t n_it = -7, conv = -7;
     {
-        CHECK(build(c, 1, 2048, 2, b) != 0 && std::strstr(ig_last_error(), "contacts") && b.sc[0] == -7); // nothing uploaded yet
-        CHECK(ig_upload_subfrag_table(c, sub.data(), M) == 0);
-        CHECK(ig_upload_contacts(c, row.data(), col.data(), cnt.data(), Z, M, 0, 1) == 0);
-        CHECK(build(c, 1, 2048, 2, b) != 0 && std::strstr(ig_last_error(), "state") && b.sc[0] == -7);
-        CHECK(ig_upload_state(c, soa.data(), N) == 0);
+        if (bring_up_ladder(fx, c, [&](bool) { return build(c, 1, 2048, 2, b); }, [&] { return b.sc[0] == -7; }, true, PARAMS_NEVER)) return 1;
         for (int bad : {0, -1}) CHECK(build(c, 1, 2048, bad, b) != 0 && std::strstr(ig_last_error(), "ignore_diags") && b.sc[0] == -7);
         for (int bad : {-1, 3}) CHECK(build(c, bad, 2048, 2, b) != 0 && std::strstr(ig_last_error(), "level"));
         CHECK(build(c, 2, 0, 2, b) != 0 && std::strstr(ig_last_error(), "max_side"));
@@ -431,20 +402,20 @@ int main()
     }
     g_free_bytes = (size_t)1 << 34;
     // every allocation of a build and of a run fails once: an error, nothing leaked, and the next call works
-    int failed = 0;
-    for (int n = 0; n < 56; n++) {
-        fake_hip::fail_allocation_in(n);
-        int rc = build(c, n % 3, 16, 2, b);
-        if (!rc) {
-            std::vector<double> b0((size_t)b.U, 1.0), bb((size_t)b.U), marg((size_t)b.U), var(20);
-            rc = ig_balance_run(c, b0.data(), 1e-5, 20, bb.data(), marg.data(), var.data(), &n_it, &conv);
-        }
-        fake_hip::fail_allocation_in(-1);
-        failed += rc != 0;
-        CHECK(build(c, 1, 2048, 2, b) == 0);
-        if (run_and_check(c, b, 1e-5, 200, 7)) return 1;
+    {
+        int turn = 0;
+        const auto build_and_run = [&] {
+            int rc = build(c, turn++ % 3, 16, 2, b);
+            if (!rc) {
+                std::vector<double> b0((size_t)b.U, 1.0), bb((size_t)b.U), marg((size_t)b.U), var(20);
+                rc = ig_balance_run(c, b0.data(), 1e-5, 20, bb.data(), marg.data(), var.data(), &n_it, &conv);
+            }
+            return rc;
+        };
+        const auto nothing_to_keep = [] { return true; }; // (a run that fails comes behind a build that wrote its outputs)
+        if (allocation_failure_sweep(fx, c, 56, 56, 0, 20, build_and_run, nothing_to_keep, [&] { return build(c, 1, 2048, 2, b) == 0 && run_and_check(c, b, 1e-5, 200, 7) == 0; }))
+            return 1;
     }
-    CHECK(failed >= 20);
     // the timed entry points and the ordered sum on caller data
     std::vector<float> ms(3 * 8);
     CHECK(ig_debug_balance_time(c, 0, 3, ms.data()) == 0 && ig_debug_balance_time(c, 1, 3, ms.data()) == 0);

@@ -11,20 +11,7 @@
 #include <cstring>
 #include <vector>
 
-#define ig_fail_msg harness_copy_of_ig_fail_msg /* ig_common.cuh defines it (for ig_draw.cpp): the library object has the real one */
-#include "../../instagraal_amd/csrc/ig_common.cuh"
-#undef ig_fail_msg
-#include "fake_hip_runtime.h"
-
-#define CHECK(x)                                                                                                           \
-    do {                                                                                                                   \
-        if (!(x)) {                                                                                                        \
-            std::fprintf(stderr, "%s:%d: CHECK failed: %s   [last error: %s]\n", __FILE__, __LINE__, #x, ig_last_error()); \
-            return 1;                                                                                                      \
-        }                                                                                                                  \
-    } while (0)
-
-typedef unsigned long long u64;
+#include "harness_common.h"
 enum { SC_LINEAR = 0, SC_RING = 1, SC_MAXQ = 2, SC_EVAL = 3, SC_CONST = 4, SC_NONMONO = 5 }; // EmapBuf.sc (ig_kernels_emap.cuh: device code, not included here)
 
 static long long g_per_pixel = -1; // tiles every pixel lists; -1: the pixels from itself on (the whole triangle)
@@ -126,27 +113,14 @@ int main()
     fake_hip::set_model("k_map_mirror", model_mirror);
     fake_hip::set_model("k_emap_checksum", model_checksum);
 
-    // a genome of 40 bins of two sub-fragments each in one contig per bin: T = 80 positions
-    const int N = 40, M = 80;
-    std::vector<float> sub((size_t)M * 4);
-    std::vector<int32_t> soa((size_t)17 * N, 0);
-    for (int f = 0; f < N; f++) {
-        const int v[17] = {0, 0, f, 0, 2000, 2, 0, f, -1, -1, 1, 2, 2000, 1, 0, 1, f};
-        for (int k = 0; k < 17; k++) soa[(size_t)k * N + f] = v[k];
-        for (int w = 0; w < 2; w++) {
-            float* s = &sub[(size_t)4 * (2 * f + w)];
-            s[0] = (float)f, s[1] = 0.5f + (float)w, s[2] = 1.5f - (float)w, s[3] = (float)w;
-        }
-    }
+    const Fixture fx;
     ig_ctx* c = nullptr;
     CHECK(ig_create(0, &c) == 0 && c);
     Out o;
-    CHECK(run(c, 8, 64, o) != 0 && std::strstr(ig_last_error(), "state")); // nothing uploaded yet
-    CHECK(ig_upload_subfrag_table(c, sub.data(), M) == 0);
-    CHECK(ig_upload_state(c, soa.data(), N) == 0); // (no contact is uploaded: none is read)
-    CHECK(run(c, 8, 64, o) != 0 && std::strstr(ig_last_error(), "parameters") && o.side == -7);
-    float p8[8] = {50.0f, 9.6f, 1e-3f, -1.5f, 2.0f, 250.0f, 3.0e5f, 5e-3f};
-    CHECK(ig_set_params(c, p8, 1.8f, 0) == 0);
+    const auto small = [&] { return run(c, 8, 64, o); };
+    // (no contact is uploaded: none is read)
+    if (bring_up_ladder(fx, c, [&](bool) { return small(); }, [&] { return o.side == -7; }, false, PARAMS_ALWAYS)) return 1;
+    CHECK(fx.params(c) == 0);
     for (int bad : {0, -3}) CHECK(run(c, bad, 64, o) != 0 && std::strstr(ig_last_error(), "max_side") && o.side == -7);
     CHECK(ig_expected_map(c, 8, o.img[0].data(), o.img[1].data(), o.img[2].data(), 64, nullptr, &o.bin, o.sc) != 0);
     CHECK(ig_expected_map(c, 8, o.img[0].data(), o.img[1].data(), o.img[2].data(), 64, &o.side, &o.bin, nullptr) != 0);
@@ -197,18 +171,7 @@ int main()
     // every allocation of a call fails once: an error, nothing leaked, and the next call works
     for (int form = 1; form <= 2; form++) {
         CHECK(ig_debug_expected_map_form(c, form) == 0);
-        int failed = 0;
-        for (int n = 0; n < 24; n++) {
-            fake_hip::fail_allocation_in(n);
-            const int rc = run(c, 8, 64, o);
-            fake_hip::fail_allocation_in(-1);
-            if (rc) {
-                CHECK(std::strstr(ig_last_error(), "hipMalloc") && o.img[0][0] == -7);
-                failed++;
-            }
-            CHECK(run(c, 8, 64, o) == 0 && o.side == 8);
-        }
-        CHECK(failed >= (form == 2 ? 6 : 2));
+        if (allocation_failure_sweep(fx, c, 24, 24, 0, form == 2 ? 6 : 2, small, [&] { return o.img[0][0] == -7; }, [&] { return small() == 0 && o.side == 8; })) return 1;
     }
     // the time entry point
     std::vector<float> ms(3);
@@ -220,10 +183,7 @@ int main()
     CHECK(ig_debug_expected_map_time(c, 8, 2, 1, ms.data(), &ck) != 0 && std::strstr(ig_last_error(), "work list"));
     g_per_pixel = -1;
     // a failed call right in front of ig_destroy: whatever it left is freed there (LeakSanitizer looks at the exit)
-    fake_hip::fail_allocation_in(3);
-    (void)run(c, 8, 64, o);
-    fake_hip::fail_allocation_in(-1);
-    ig_destroy(c);
+    (void)failed_call_before_destroy(c, 3, small);
     std::printf("emap harness ok (%ld launches, %ld allocations)\n", fake_hip::launches(), fake_hip::allocations());
     return 0;
 }

@@ -16,10 +16,7 @@
 #include <cstring>
 #include <vector>
 
-#define ig_fail_msg harness_copy_of_ig_fail_msg /* ig_common.cuh defines it (for ig_draw.cpp): the library object has the real one */
-#include "../../instagraal_amd/csrc/ig_common.cuh"
-#undef ig_fail_msg
-#include "fake_hip_runtime.h"
+#include "harness_common.h"
 
 static uint64_t rs = 0x2545F4914F6CDD1Dull;
 static uint32_t rnd()
@@ -29,15 +26,6 @@ static uint32_t rnd()
     rs ^= rs << 17;
     return (uint32_t)(rs >> 11);
 }
-static int g_line_fail = 0;
-#define CHECK(x)                                                                                           \
-    do {                                                                                                   \
-        if (!(x)) {                                                                                        \
-            std::fprintf(stderr, "%s:%d: CHECK failed: %s   [last error: %s]\n", __FILE__, __LINE__, #x, ig_last_error()); \
-            g_line_fail = __LINE__;                                                                        \
-            return 1;                                                                                      \
-        }                                                                                                  \
-    } while (0)
 
 // ---- a small random problem through the real ABI -------------------------------------------------------------------------
 struct Problem {

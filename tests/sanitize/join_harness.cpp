@@ -12,20 +12,7 @@
 #include <cstring>
 #include <vector>
 
-#define ig_fail_msg harness_copy_of_ig_fail_msg /* ig_common.cuh defines it (for ig_draw.cpp): the library object has the real one */
-#include "../../instagraal_amd/csrc/ig_common.cuh"
-#undef ig_fail_msg
-#include "fake_hip_runtime.h"
-
-#define CHECK(x)                                                                                                           \
-    do {                                                                                                                   \
-        if (!(x)) {                                                                                                        \
-            std::fprintf(stderr, "%s:%d: CHECK failed: %s   [last error: %s]\n", __FILE__, __LINE__, #x, ig_last_error()); \
-            return 1;                                                                                                      \
-        }                                                                                                                  \
-    } while (0)
-
-typedef unsigned long long u64;
+#include "harness_common.h"
 // mirrors of the device structs (ig_kernels_rows.cuh, ig_kernels_join.cuh: device code, not included here)
 struct Item {
     long long off;
@@ -234,37 +221,19 @@ int main()
     fake_hip::set_model("k_lift_reduce", model_reduce);
     fake_hip::set_model("k_join_model", model_model);
 
-    // a genome of 40 bins of two sub-fragments each in one contig per bin, a few contacts
-    const int N = 40, M = 80;
-    std::vector<float> sub((size_t)M * 4);
-    std::vector<int32_t> soa((size_t)17 * N, 0), row, col, cnt;
-    for (int f = 0; f < N; f++) {
-        const int v[17] = {0, 0, f, 0, 2000, 2, 0, f, -1, -1, 1, 2, 2000, 1, 0, 1, f};
-        for (int k = 0; k < 17; k++) soa[(size_t)k * N + f] = v[k];
-        for (int w = 0; w < 2; w++) {
-            float* s = &sub[(size_t)4 * (2 * f + w)];
-            s[0] = (float)f, s[1] = 0.5f + (float)w, s[2] = 1.5f - (float)w, s[3] = (float)w;
-        }
-    }
-    for (int a = 0; a < M; a++)
-        for (int b = a + 1; b < M; b += 7) row.push_back(a), col.push_back(b), cnt.push_back(1 + (a + b) % 5);
-    const int64_t Z = (int64_t)row.size();
+    const Fixture fx;
+    const int64_t Z = fx.Z;
 
     ig_ctx* c = nullptr;
     CHECK(ig_create(0, &c) == 0 && c);
     int64_t n_ends, n_links, sc[8];
     int32_t i32[4];
     int64_t i64[4];
-    CHECK(ig_join_support_build(c, 64, 0, &n_ends, &n_links, sc) != 0); // nothing uploaded yet
     CHECK(ig_join_support_fetch(c, 0, 0, i32, i64, nullptr, nullptr) != 0 && std::strstr(ig_last_error(), "nothing is built"));
     CHECK(ig_join_support_rows(c, i64, 4) != 0 && ig_join_support_ends(c, i32, i32, 4) != 0 && ig_join_support_release(c) == 0);
-    CHECK(ig_upload_subfrag_table(c, sub.data(), M) == 0);
-    CHECK(ig_upload_contacts(c, row.data(), col.data(), cnt.data(), Z, M, 0, 1) == 0);
-    CHECK(ig_join_support_build(c, 64, 0, &n_ends, &n_links, sc) != 0 && std::strstr(ig_last_error(), "state"));
-    CHECK(ig_upload_state(c, soa.data(), N) == 0);
-    CHECK(ig_join_support_build(c, 64, 1, &n_ends, &n_links, sc) != 0 && std::strstr(ig_last_error(), "parameters"));
-    float p8[8] = {50.0f, 9.6f, 1e-3f, -1.5f, 2.0f, 250.0f, 3.0e5f, 5e-3f};
-    CHECK(ig_set_params(c, p8, 1.8f, 0) == 0);
+    const auto fresh_build = [&](bool model) { return n_ends = n_links = -7, ig_join_support_build(c, 64, model, &n_ends, &n_links, sc); };
+    if (bring_up_ladder(fx, c, fresh_build, [&] { return n_ends == -7 && n_links == -7; }, true, PARAMS_WITH_MODEL)) return 1;
+    CHECK(fx.params(c) == 0);
     for (int bad : {0, 1025, -3}) CHECK(ig_join_support_build(c, bad, 1, &n_ends, &n_links, sc) != 0 && std::strstr(ig_last_error(), "window"));
     CHECK(ig_join_support_build(c, 64, 1, nullptr, &n_links, sc) != 0 && ig_join_support_build(c, 64, 1, &n_ends, &n_links, nullptr) != 0);
 
@@ -321,7 +290,7 @@ int main()
     CHECK(ig_assembly_contacts_build(c, 1, &nu, &ne, sc) == 0 || std::strlen(ig_last_error()) > 0);
     CHECK(ig_assembly_contacts_build(c, 0, &nu, &ne, sc) == 0 || std::strlen(ig_last_error()) > 0);
     if (build_and_read(c, 64, 1, 300)) return 1;
-    CHECK(ig_upload_contacts(c, row.data(), col.data(), cnt.data(), Z, M, 0, 1) == 0);
+    CHECK(fx.contacts(c) == 0);
     CHECK(ig_join_support_fetch(c, 0, 0, i32, i64, nullptr, nullptr) != 0 && std::strstr(ig_last_error(), "nothing is built"));
     if (build_and_read(c, 64, 1, 300)) return 1;
     ig_destroy(c);

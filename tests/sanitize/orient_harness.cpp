@@ -11,20 +11,7 @@
 #include <cstring>
 #include <vector>
 
-#define ig_fail_msg harness_copy_of_ig_fail_msg /* ig_common.cuh defines it (for ig_draw.cpp): the library object has the real one */
-#include "../../instagraal_amd/csrc/ig_common.cuh"
-#undef ig_fail_msg
-#include "fake_hip_runtime.h"
-
-#define CHECK(x)                                                                                                           \
-    do {                                                                                                                   \
-        if (!(x)) {                                                                                                        \
-            std::fprintf(stderr, "%s:%d: CHECK failed: %s   [last error: %s]\n", __FILE__, __LINE__, #x, ig_last_error()); \
-            return 1;                                                                                                      \
-        }                                                                                                                  \
-    } while (0)
-
-typedef unsigned long long u64;
+#include "harness_common.h"
 enum { N_OBS = 7, CTL_ERR = 0, CTL_LARGE = 1 }; // ig_kernels_orient.cuh: device code, not included here
 
 static int g_n_seg = 0;          // what the last k_orient_segments saw: the other kernels size their writes by it, as the real ones do by seg[] and the lists
@@ -137,37 +124,17 @@ int main()
     fake_hip::set_model("k_orient_modelILi64E", model_model<64>);
     fake_hip::set_model("k_orient_modelILi256E", model_model<256>);
 
-    // a genome of 40 bins of two sub-fragments each in one contig per bin, a few contacts: T = 80 positions
-    const int N = 40, M = 80;
-    std::vector<float> sub((size_t)M * 4);
-    std::vector<int32_t> soa((size_t)17 * N, 0), row, col, cnt;
-    for (int f = 0; f < N; f++) {
-        const int v[17] = {0, 0, f, 0, 2000, 2, 0, f, -1, -1, 1, 2, 2000, 1, 0, 1, f};
-        for (int k = 0; k < 17; k++) soa[(size_t)k * N + f] = v[k];
-        for (int w = 0; w < 2; w++) {
-            float* s = &sub[(size_t)4 * (2 * f + w)];
-            s[0] = (float)f, s[1] = 0.5f + (float)w, s[2] = 1.5f - (float)w, s[3] = (float)w;
-        }
-    }
-    for (int a = 0; a < M; a++)
-        for (int b = a + 1; b < M; b += 7) row.push_back(a), col.push_back(b), cnt.push_back(1 + (a + b) % 5);
-    const int64_t Z = (int64_t)row.size();
+    const Fixture fx;
 
     ig_ctx* c = nullptr;
     CHECK(ig_create(0, &c) == 0 && c);
     Out o;
     std::vector<int32_t> first, last;
     pairs_of(3, first, last);
-    CHECK(run(c, 8, 0, first, last, o) != 0 && o.untouched()); // nothing uploaded yet
-    CHECK(ig_upload_subfrag_table(c, sub.data(), M) == 0);
-    CHECK(run(c, 8, 0, first, last, o) != 0 && std::strstr(ig_last_error(), "contacts") && o.untouched());
-    CHECK(ig_upload_contacts(c, row.data(), col.data(), cnt.data(), Z, M, 0, 1) == 0);
-    CHECK(run(c, 8, 0, first, last, o) != 0 && std::strstr(ig_last_error(), "state") && o.untouched());
-    CHECK(ig_upload_state(c, soa.data(), N) == 0);
-    CHECK(run(c, 8, 1, first, last, o) != 0 && std::strstr(ig_last_error(), "parameters") && o.untouched());
+    const auto untouched = [&] { return o.untouched(); };
+    if (bring_up_ladder(fx, c, [&](bool model) { return run(c, 8, model, first, last, o); }, untouched, true, PARAMS_WITH_MODEL)) return 1;
     CHECK(run(c, 8, 0, first, last, o) == 0 && o.n_placed == 80 && o.exq[0] == -7); // (without the model no parameters are needed)
-    float p8[8] = {50.0f, 9.6f, 1e-3f, -1.5f, 2.0f, 250.0f, 3.0e5f, 5e-3f};
-    CHECK(ig_set_params(c, p8, 1.8f, 0) == 0);
+    CHECK(fx.params(c) == 0);
 
     // a window out of range
     for (int bad : {0, 1025, -3}) CHECK(run(c, bad, 1, first, last, o) != 0 && std::strstr(ig_last_error(), "window") && o.untouched());
@@ -234,25 +201,9 @@ int main()
     CHECK(run(c, 1024, 1, first, last, o) == 0);
     g_maxq = 1;
     // every allocation of a call fails once: an error, nothing written, nothing leaked, and the next call works
-    int failed = 0;
-    for (int n = 0; n < 32; n++) {
-        pairs_of(12, first, last);
-        if (n % 4 == 0) { // (a new handle: the genome view's and the feature's buffers are made again)
-            ig_destroy(c);
-            c = nullptr;
-            CHECK(ig_create(0, &c) == 0 && ig_upload_subfrag_table(c, sub.data(), M) == 0 && ig_upload_contacts(c, row.data(), col.data(), cnt.data(), Z, M, 0, 1) == 0);
-            CHECK(ig_upload_state(c, soa.data(), N) == 0 && ig_set_params(c, p8, 1.8f, 0) == 0);
-        }
-        fake_hip::fail_allocation_in(n % 24);
-        const int rc = run(c, 8, 1, first, last, o);
-        fake_hip::fail_allocation_in(-1);
-        if (rc) {
-            CHECK(std::strstr(ig_last_error(), "hipMalloc") && o.untouched());
-            failed++;
-        }
-        CHECK(run(c, 8, 1, first, last, o) == 0 && o.sc[7] == (int64_t)first.size());
-    }
-    CHECK(failed >= 4);
+    pairs_of(12, first, last);
+    const auto model_call = [&] { return run(c, 8, 1, first, last, o); };
+    if (allocation_failure_sweep(fx, c, 32, 24, 4, 4, model_call, untouched, [&] { return run(c, 8, 1, first, last, o) == 0 && o.sc[7] == (int64_t)first.size(); })) return 1;
     // the time entry point: both passes, every form
     std::vector<float> ms(3);
     int64_t ck = 0;
@@ -277,13 +228,8 @@ int main()
     CHECK(ig_debug_orientation_support_time(c, 1024, 40, first.data(), last.data(), 1, 0, 1, ms.data(), &ck) != 0 && std::strstr(ig_last_error(), "too large"));
     g_maxq = 1;
     // a failed call right in front of ig_destroy: whatever it left is freed there (LeakSanitizer looks at the exit)
-    ig_destroy(c);
-    CHECK(ig_create(0, &c) == 0 && ig_upload_subfrag_table(c, sub.data(), M) == 0 && ig_upload_contacts(c, row.data(), col.data(), cnt.data(), Z, M, 0, 1) == 0);
-    CHECK(ig_upload_state(c, soa.data(), N) == 0 && ig_set_params(c, p8, 1.8f, 0) == 0);
-    fake_hip::fail_allocation_in(12);
-    (void)run(c, 8, 1, first, last, o);
-    fake_hip::fail_allocation_in(-1);
-    ig_destroy(c);
+    if (fx.fresh(c)) return 1;
+    (void)failed_call_before_destroy(c, 12, model_call);
     std::printf("orient harness ok (%ld launches, %ld allocations)\n", fake_hip::launches(), fake_hip::allocations());
     return 0;
 }

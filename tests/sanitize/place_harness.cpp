@@ -12,20 +12,7 @@
 #include <cstring>
 #include <vector>
 
-#define ig_fail_msg harness_copy_of_ig_fail_msg /* ig_common.cuh defines it (for ig_draw.cpp): the library object has the real one */
-#include "../../instagraal_amd/csrc/ig_common.cuh"
-#undef ig_fail_msg
-#include "fake_hip_runtime.h"
-
-#define CHECK(x)                                                                                                           \
-    do {                                                                                                                   \
-        if (!(x)) {                                                                                                        \
-            std::fprintf(stderr, "%s:%d: CHECK failed: %s   [last error: %s]\n", __FILE__, __LINE__, #x, ig_last_error()); \
-            return 1;                                                                                                      \
-        }                                                                                                                  \
-    } while (0)
-
-typedef unsigned long long u64;
+#include "harness_common.h"
 // mirrors of the device structs (ig_kernels_rows.cuh, ig_kernels_join.cuh: device code, not included here)
 struct Item {
     long long off;
@@ -277,31 +264,15 @@ int main()
     fake_hip::set_model("k_lift_reduce", model_reduce);
     fake_hip::set_model("k_place_scan", model_scan);
 
-    // a genome of 40 bins of two sub-fragments each in one contig per bin, a few contacts
-    const int N = 40, M = 80;
-    std::vector<float> sub((size_t)M * 4);
-    std::vector<int32_t> soa((size_t)17 * N, 0), row, col, cnt;
-    for (int f = 0; f < N; f++) {
-        const int v[17] = {0, 0, f, 0, 2000, 2, 0, f, -1, -1, 1, 2, 2000, 1, 0, 1, f};
-        for (int k = 0; k < 17; k++) soa[(size_t)k * N + f] = v[k];
-        for (int w = 0; w < 2; w++) {
-            float* s = &sub[(size_t)4 * (2 * f + w)];
-            s[0] = (float)f, s[1] = 0.5f + (float)w, s[2] = 1.5f - (float)w, s[3] = (float)w;
-        }
-    }
-    for (int a = 0; a < M; a++)
-        for (int b = a + 1; b < M; b += 7) row.push_back(a), col.push_back(b), cnt.push_back(1 + (a + b) % 5);
-    const int64_t Z = (int64_t)row.size();
+    const Fixture fx;
+    const int N = Fixture::N;
+    const int64_t Z = fx.Z;
 
     ig_ctx* c = nullptr;
     CHECK(ig_create(0, &c) == 0 && c);
     {
         Out o(N);
-        CHECK(call(c, 64, 64, o) != 0 && std::strstr(ig_last_error(), "contacts") && o.untouched()); // nothing uploaded yet
-        CHECK(ig_upload_subfrag_table(c, sub.data(), M) == 0);
-        CHECK(ig_upload_contacts(c, row.data(), col.data(), cnt.data(), Z, M, 0, 1) == 0);
-        CHECK(call(c, 64, 64, o) != 0 && std::strstr(ig_last_error(), "state") && o.untouched());
-        CHECK(ig_upload_state(c, soa.data(), N) == 0);
+        if (bring_up_ladder(fx, c, [&](bool) { return call(c, 64, 64, o); }, [&] { return o.untouched(); }, true, PARAMS_NEVER)) return 1;
         for (int bad : {0, 1025, -3}) CHECK(call(c, bad, 1, o) != 0 && std::strstr(ig_last_error(), "window") && o.untouched());
         for (int bad : {0, 129, -1}) CHECK(call(c, 64, bad, o) != 0 && std::strstr(ig_last_error(), "min_hosts") && o.untouched());
         CHECK(call(c, 1024, 2049, o) != 0 && call(c, 1, 3, o) != 0 && o.untouched());
@@ -363,19 +334,11 @@ int main()
     CHECK(call(c, 1, 1, o) != 0 && std::strstr(ig_last_error(), "counts too large for this window") && o.untouched());
     g_counted = 1000;
     // every allocation of a call fails once: an error, nothing written, nothing leaked, and the next call works
-    int failed = 0;
-    for (int n = 0; n < 64; n++) {
+    {
         Out q(N);
-        fake_hip::fail_allocation_in(n);
-        const int rc = call(c, 64, 64, q);
-        fake_hip::fail_allocation_in(-1);
-        if (rc) {
-            CHECK(q.untouched());
-            failed++;
-        }
-        if (call_and_read(c, 64, 64, N, 300)) return 1;
+        const auto fresh_outputs = [&] { return q = Out(N), call(c, 64, 64, q); };
+        if (allocation_failure_sweep(fx, c, 64, 64, 0, 20, fresh_outputs, [&] { return q.untouched(); }, [&] { return call_and_read(c, 64, 64, N, 300) == 0; })) return 1;
     }
-    CHECK(failed >= 20);
     // the time entry point; the join support and the lift through the functions they share with this feature
     std::vector<float> ms(2 * 10);
     int64_t ck = 0;
@@ -386,10 +349,7 @@ int main()
     CHECK(ig_join_support_build(c, 64, 0, &nu, &ne, sc8) == 0 || std::strlen(ig_last_error()) > 0);
     if (call_and_read(c, 64, 64, N, 300)) return 1;
     // ig_destroy behind a failed call
-    fake_hip::fail_allocation_in(9);
-    CHECK(call(c, 64, 64, o) != 0);
-    fake_hip::fail_allocation_in(-1);
-    ig_destroy(c);
+    CHECK(failed_call_before_destroy(c, 9, [&] { return call(c, 64, 64, o); }) != 0);
     std::printf("place harness ok (%ld launches, %ld allocations)\n", fake_hip::launches(), fake_hip::allocations());
     return 0;
 }

@@ -25,19 +25,7 @@ ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 sys.path.insert(0, ROOT)
 import numpy as np
 
-
-def make(cfg, moves):
-    from instagraal_amd import synth
-    from instagraal_amd.sampler import sampler as hip_sampler
-
-    prob = synth.make_problem(*synth.CONFIGS[cfg])
-    s = hip_sampler(**prob.sampler_kwargs(), device_id=0, coo=(prob.coo_row, prob.coo_col, prob.coo_cnt))
-    s.set_param_simu(dict(prob.params))
-    s.eval_likelihood_init()
-    np.random.seed(0)
-    if moves:
-        s.step_sampler_batch(np.resize(np.random.permutation(prob.n_frags), moves).astype(np.int32), 5)
-    return prob, s
+import _report_bench as kit
 
 
 def min_bytes(Z, K, U, n_out, level):
@@ -51,7 +39,7 @@ def measure(cfg, moves, reps, warmup, hbm_gbs):
     from instagraal_amd import assembly_contacts as ac
     from instagraal_amd.hip_lib import ASSEMBLY_CONTACTS_PASSES as PASSES
 
-    prob, s = make(cfg, moves)
+    prob, s = kit.make_sampler(cfg, moves)
     Z, M = int(prob.coo_row.size), int(prob.n_sub_frags)
     order = s.ctx.contact_map_order().astype(np.int64)
     position = ac.positions_of(order, M)
@@ -60,19 +48,18 @@ def measure(cfg, moves, reps, warmup, hbm_gbs):
         out = dict(config=cfg, moves_before=moves, contacts=Z, sub_fragments=M, level=level)
         s.ctx.debug_assembly_contacts_limits(0, 0)
         # the two forms of the passes over the contacts alternate in blocks (other work shares the machine: a drift hits both alike)
-        ms_a, ms_b, blocks = [], [], 4
-        per = (reps + blocks - 1) // blocks
-        for _ in range(blocks):
-            s.ctx.debug_assembly_contacts_combine(True)
-            a_, ck = s.ctx.debug_assembly_contacts_time(level, n=warmup + per)
-            s.ctx.debug_assembly_contacts_combine(False)
-            b_, ck_one = s.ctx.debug_assembly_contacts_time(level, n=warmup + per)
-            assert ck == ck_one, "the two forms of the passes over the contacts disagree"
-            ms_a.append(a_[warmup:])
-            ms_b.append(b_[warmup:])
+        seen = {}
+
+        def timed(combine):
+            def form(n):
+                s.ctx.debug_assembly_contacts_combine(combine)
+                t, seen["checksum"] = s.ctx.debug_assembly_contacts_time(level, n=n)
+                return t, seen["checksum"]
+            return form
+
+        ms, one = kit.alternate(timed(True), timed(False), reps, warmup, disagree="the two forms of the passes over the contacts disagree")
+        ck = seen["checksum"]  # (of every build so far: they agreed block by block)
         s.ctx.debug_assembly_contacts_combine(True)
-        ms = np.concatenate([np.zeros((warmup, len(PASSES)), np.float32)] + ms_a)  # (the rows behind `warmup` are the timed ones)
-        one = np.concatenate(ms_b)
         out["count_one_atomic_per_contact_us"] = round(1e3 * float(np.median(one[:, 0])), 2)
         out["scatter_one_atomic_per_contact_us"] = round(1e3 * float(np.median(one[:, 2])), 2)
         out["timed_repetitions"] = int(one.shape[0])
@@ -82,23 +69,18 @@ def measure(cfg, moves, reps, warmup, hbm_gbs):
         lens = np.diff(res["rowptr"])
         out.update(n_units=U, entries_kept=K, entries_out=n_out, entries_unplaced=res["entries_unplaced"], forms=forms,
                    row_length_max_of_the_result=int(lens.max()) if lens.size else 0)
-        med = np.median(ms[warmup:], axis=0)
+        med = np.median(ms, axis=0)
         for k, name in enumerate(PASSES):
             out[name + "_us"] = round(1e3 * float(med[k]), 2)
-            out[name + "_min_us"] = round(1e3 * float(ms[warmup:, k].min()), 2)
-        out["all_passes_us"] = round(1e3 * float(np.median(ms[warmup:].sum(axis=1))), 2)
+            out[name + "_min_us"] = round(1e3 * float(ms[:, k].min()), 2)
+        out["all_passes_us"] = round(1e3 * float(np.median(ms.sum(axis=1))), 2)
         b = min_bytes(Z, K, U, n_out, level)
         out["bytes_min"] = b
         sort_us = out["sort_short_us"] + out["sort_lds_us"] + out["sort_long_us"]
         frac = lambda nbytes, us: round(nbytes / (us * 1e-6) / (hbm_gbs * 1e9), 4) if us > 0 else None  # noqa: E731
         out["fraction_of_hbm_rate"] = dict(count=frac(b["count"], out["count_us"]), scatter=frac(b["scatter"], out["scatter_us"]), sort=frac(b["sort"], sort_us),
                                            reduce=frac(b["reduce"], out["reduce_us"]) if level == "bin" else None, whole=frac(b["whole"], out["all_passes_us"]))
-        t = []
-        for _ in range(max(reps // 4, 2)):
-            t0 = time.perf_counter()
-            s.ctx.assembly_contacts(level)
-            t.append(time.perf_counter() - t0)
-        out["build_call_host_clock_ms"] = round(1e3 * float(np.median(t)), 2)
+        out["build_call_host_clock_ms"] = kit.host_clock_ms(lambda: s.ctx.assembly_contacts(level), max(reps // 4, 2), 0)
         # yardstick (b): every row through the long form
         s.ctx.debug_assembly_contacts_limits(1, 1)
         ms_b, ck_b = s.ctx.debug_assembly_contacts_time(level, n=max(warmup, 1) + max(reps // 4, 2))

@@ -16,7 +16,6 @@ marginals' time in GB/s.  No time is promised; the default form (BAL_SHIP_FORM) 
 import argparse
 import json
 import os
-import re
 import sys
 import time
 
@@ -24,23 +23,13 @@ ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 sys.path.insert(0, ROOT)
 import numpy as np
 
+import _report_bench as kit
+
 FORMS = ("wave", "packed")
 
 
-def make(cfg):
-    from instagraal_amd import synth
-    from instagraal_amd.sampler import sampler as hip_sampler
-
-    prob = synth.make_problem(*synth.CONFIGS[cfg])
-    s = hip_sampler(**prob.sampler_kwargs(), device_id=0, coo=(prob.coo_row, prob.coo_col, prob.coo_cnt))
-    s.set_param_simu(dict(prob.params))
-    s.eval_likelihood_init()
-    return prob, s
-
-
 def shipped_form():
-    src = open(os.path.join(ROOT, "instagraal_amd", "csrc", "ig_host_bal.inc")).read()
-    return ("default", "wave", "packed")[int(re.search(r"#define BAL_SHIP_FORM (\d+)", src).group(1))]
+    return ("default", "wave", "packed")[kit.shipped_flag("ig_host_bal.inc", "BAL_SHIP_FORM")]
 
 
 def us(ms):
@@ -51,7 +40,7 @@ def measure(shape, levels, reps, warmup, ignore_diags):
     from instagraal_amd import balance as bal
     from instagraal_amd.hip_lib import BALANCE_BUILD_PASSES as PASSES
 
-    prob, s = make(shape)
+    prob, s = kit.make_sampler(shape, 0)
     ctx = s.ctx
     rows = []
     for level in levels:

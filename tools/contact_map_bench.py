@@ -22,22 +22,10 @@ from concurrent.futures import ThreadPoolExecutor
 sys.path.insert(0, os.path.abspath(os.path.join(os.path.dirname(__file__), "..")))
 import numpy as np
 
+import _report_bench as kit
+
 MAX_SIDE = 2048
 THREADS = 16
-
-
-def make(cfg, moves):
-    from instagraal_amd import synth
-    from instagraal_amd.sampler import sampler as hip_sampler
-
-    prob = synth.make_problem(*synth.CONFIGS[cfg])
-    s = hip_sampler(**prob.sampler_kwargs(), device_id=0, coo=(prob.coo_row, prob.coo_col, prob.coo_cnt))
-    s.set_param_simu(dict(prob.params))
-    s.eval_likelihood_init()
-    np.random.seed(0)
-    if moves:
-        s.step_sampler_batch(np.resize(np.random.permutation(prob.n_frags), moves).astype(np.int32), 5)
-    return prob, s
 
 
 def host_map(prob, order, max_side):
@@ -62,7 +50,7 @@ def host_map(prob, order, max_side):
 
 
 def measure(cfg, moves, reps, warmup):
-    prob, s = make(cfg, moves)
+    prob, s = kit.make_sampler(cfg, moves)
     Z, M = int(prob.coo_row.size), int(prob.n_sub_frags)
     out = dict(config=cfg, moves_before=moves, contacts=Z, sub_fragments=M, max_side=MAX_SIDE)
     image, b = s.contact_map(MAX_SIDE)
@@ -71,14 +59,8 @@ def measure(cfg, moves, reps, warmup):
     for key, combine in (("pass_combined_us", True), ("pass_one_atomic_per_end_us", False)):
         ms, tot = s.ctx.debug_contact_map_time(MAX_SIDE, combine=combine, n=warmup + reps)
         assert tot == int(image.sum())
-        out[key] = round(1e3 * float(np.median(ms[warmup:])), 2)
-        out[key.replace("_us", "_min_us")] = round(1e3 * float(ms[warmup:].min()), 2)
-    t = []
-    for _ in range(warmup + reps):
-        t0 = time.perf_counter()
-        s.contact_map(MAX_SIDE)
-        t.append(time.perf_counter() - t0)
-    out["whole_call_host_clock_ms"] = round(1e3 * float(np.median(t[warmup:])), 2)
+        kit.put_times(out, key, ms[warmup:])
+    out["whole_call_host_clock_ms"] = kit.host_clock_ms(lambda: s.contact_map(MAX_SIDE), reps, warmup)
     order = s.ctx.contact_map_order()
     t = []
     for _ in range(3):
@@ -133,7 +115,7 @@ def main():
     if a.merge_stats:
         return merge_stats(a.merge_stats, a.out)
     if a.trace_run:
-        prob, s = make(a.trace_run, a.moves)
+        prob, s = kit.make_sampler(a.trace_run, a.moves)
         for combine in (True, False):
             ms, _ = s.ctx.debug_contact_map_time(MAX_SIDE, combine=combine, n=8)
             print("combine", combine, "median %.1f us" % (1e3 * float(np.median(ms[3:]))))
@@ -144,8 +126,7 @@ def main():
                    "k_contact_map + k_map_mirror (tools/contact_map_bench.py); host figures: numpy on this box's CPUs, %d threads"
                    % (a.reps, a.warmup, THREADS))
     doc["results"] = [measure(cfg, a.moves, a.reps, a.warmup) for cfg in a.configs.split(",") if cfg]
-    json.dump(doc, open(a.out, "w"), indent=1)
-    print(json.dumps(doc["results"], indent=1))
+    kit.write_doc(doc, a.out, show=doc["results"])
 
 
 if __name__ == "__main__":

@@ -12,7 +12,6 @@ estimate's linear ones; median of 20 after 3 warm-ups, hipEvents around zero + k
   python tools/distance_law_bench.py [--configs cfg3,cfg3_late] [--out profiles/r08_distance_law.json]
 """
 import argparse
-import json
 import os
 import sys
 import time
@@ -20,19 +19,7 @@ import time
 sys.path.insert(0, os.path.abspath(os.path.join(os.path.dirname(__file__), "..")))
 import numpy as np
 
-
-def make(cfg, moves):
-    from instagraal_amd import synth
-    from instagraal_amd.sampler import sampler as hip_sampler
-
-    prob = synth.make_problem(*synth.CONFIGS[cfg])
-    s = hip_sampler(**prob.sampler_kwargs(), device_id=0, coo=(prob.coo_row, prob.coo_col, prob.coo_cnt))
-    s.set_param_simu(dict(prob.params))
-    s.eval_likelihood_init()
-    np.random.seed(0)
-    if moves:
-        s.step_sampler_batch(np.resize(np.random.permutation(prob.n_frags), moves).astype(np.int32), 5)
-    return prob, s
+import _report_bench as kit
 
 
 def host_observed(s, prob, edges):
@@ -50,7 +37,7 @@ def host_observed(s, prob, edges):
 def measure(cfg, moves, reps, warmup):
     from instagraal_amd import distance_law as dlaw
 
-    prob, s = make(cfg, moves)
+    prob, s = kit.make_sampler(cfg, moves)
     Z, M = int(prob.coo_row.size), int(prob.n_sub_frags)
     longest = float(s.ctx.debug_tables()[0].max())
     rows = []
@@ -63,14 +50,8 @@ def measure(cfg, moves, reps, warmup):
         ms_b, _, ck_b = s.ctx.debug_distance_law_time(edges, privatised=False, n=warmup + reps, pairs=False)
         assert ck_a == ck_b
         for key, ms in (("observed_privatised_us", ms_a), ("observed_one_atomic_per_contact_us", ms_b), ("pairs_us", ms_p)):
-            out[key] = round(1e3 * float(np.median(ms[warmup:])), 2)
-            out[key.replace("_us", "_min_us")] = round(1e3 * float(ms[warmup:].min()), 2)
-        t = []
-        for _ in range(warmup + reps):
-            t0 = time.perf_counter()
-            s.ctx.distance_law(edges)
-            t.append(time.perf_counter() - t0)
-        out["whole_call_host_clock_ms"] = round(1e3 * float(np.median(t[warmup:])), 2)
+            kit.put_times(out, key, ms[warmup:])
+        out["whole_call_host_clock_ms"] = kit.host_clock_ms(lambda: s.ctx.distance_law(edges), reps, warmup)
         t = []
         for _ in range(3):
             t0 = time.perf_counter()
@@ -96,8 +77,7 @@ def main():
     doc = dict(what=("the distance law's passes on one MI355X: median of %d after %d warm-ups, hipEvents around zero + kernel "
                      "(tools/distance_law_bench.py); host figures: numpy on this box's CPUs, one thread, on the host clock" % (a.reps, a.warmup)))
     doc["results"] = [r for cfg in a.configs.split(",") if cfg for r in measure(cfg, a.moves, a.reps, a.warmup)]
-    json.dump(doc, open(a.out, "w"), indent=1)
-    print(json.dumps(doc["results"], indent=1))
+    kit.write_doc(doc, a.out, show=doc["results"])
 
 
 if __name__ == "__main__":

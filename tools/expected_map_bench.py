@@ -16,9 +16,7 @@ form (EMAP_TILE_MIN_BIN in csrc/ig_host_emap.inc, 0: never) and whether the figu
   python tools/expected_map_bench.py [--configs cfg3,cfg3_late] [--out profiles/r12_expected_map.json]
 """
 import argparse
-import json
 import os
-import re
 import sys
 import time
 
@@ -26,21 +24,9 @@ ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 sys.path.insert(0, ROOT)
 import numpy as np
 
+import _report_bench as kit
+
 FORMS = ("rows", "tiles", "tiles_plain")
-
-
-def make(cfg, moves):
-    from instagraal_amd import synth
-    from instagraal_amd.sampler import sampler as hip_sampler
-
-    prob = synth.make_problem(*synth.CONFIGS[cfg])
-    s = hip_sampler(**prob.sampler_kwargs(), device_id=0, coo=(prob.coo_row, prob.coo_col, prob.coo_cnt))
-    s.set_param_simu(dict(prob.params))
-    s.eval_likelihood_init()
-    np.random.seed(0)
-    if moves:
-        s.step_sampler_batch(np.resize(np.random.permutation(prob.n_frags), moves).astype(np.int32), 5)
-    return prob, s
 
 
 def numpy_model_q(p):
@@ -59,7 +45,7 @@ def numpy_model_q(p):
 def measure(cfg, moves, reps, warmup, sides):
     from instagraal_amd import expected_map as em
 
-    prob, s = make(cfg, moves)
+    prob, s = kit.make_sampler(cfg, moves)
     rows = []
     ds, contig, stot, _, _ = s.ctx.debug_tables()
     order = s.ctx.contact_map_order().astype(np.int64)
@@ -80,26 +66,12 @@ def measure(cfg, moves, reps, warmup, sides):
         assert int(ref["cis_pairs"].sum()) == 2 * ref["linear_cis_pairs"]
         out.update(n_placed=ref["n_placed"], side=ref["side"], bin=ref["bin"], linear_cis_pairs=ref["linear_cis_pairs"], ring_pairs=ref["ring_pairs_total"])
         # the forms alternate in blocks (other work shares the machine: a drift hits all alike)
-        ms, blocks = {f: [] for f in FORMS}, 4
-        per = (reps + blocks - 1) // blocks
-        sums = set()
-        for _ in range(blocks):
-            for form in FORMS:
-                t, ck = s.ctx.debug_expected_map_time(max_side, form, warmup + per)
-                ms[form].append(t[warmup:])
-                sums.add(ck)
-        assert len(sums) == 1
-        for form in FORMS:
-            t = np.concatenate(ms[form])
+        timed = lambda form: lambda n: s.ctx.debug_expected_map_time(max_side, form, n)  # noqa: E731
+        for form, ms in zip(FORMS, kit.alternate_blocks([timed(form) for form in FORMS], reps, warmup)):
+            t = np.concatenate(ms)
             out["timed_builds"] = int(t.size)
-            out[form + "_ms"] = round(float(np.median(t)), 4)
-            out[form + "_min_ms"] = round(float(t.min()), 4)
-        t = []
-        for _ in range(warmup + 5):
-            t0 = time.perf_counter()
-            s.ctx.expected_map(max_side)
-            t.append(time.perf_counter() - t0)
-        out["whole_call_host_clock_ms"] = round(1e3 * float(np.median(t[warmup:])), 2)
+            kit.put_times(out, form + "_ms", t)
+        out["whole_call_host_clock_ms"] = kit.host_clock_ms(lambda: s.ctx.expected_map(max_side), 5, warmup)
         out["model_values_per_second_rows"] = round(ref["linear_cis_pairs"] / (1e-3 * out["rows_ms"]), 0) if out["rows_ms"] > 0 else None
         rows.append(out)
     host = dict(config=cfg, linear_cis_pairs=rows[0]["linear_cis_pairs"], inputs=(ds, stot, contig, position), params=dict(prob.params), max_side=min(sides))
@@ -136,15 +108,13 @@ def main():
         doc["numpy_rule_on_the_host"] = dict(config=h["config"], max_side=h["max_side"], linear_cis_pairs=want["linear_cis_pairs"],
                                              seconds=round(time.perf_counter() - t0, 2),
                                              note="expected_map.expected_host with a numpy model: the enumeration's cost; the other shapes were not measured on the host")
-    src = open(os.path.join(ROOT, "instagraal_amd", "csrc", "ig_host_emap.inc")).read()
-    min_bin = int(re.search(r"#define EMAP_TILE_MIN_BIN (\d+)", src).group(1))
+    min_bin = kit.shipped_flag("ig_host_emap.inc", "EMAP_TILE_MIN_BIN")
     doc["tile_form_shipped_from_bin"] = min_bin if min_bin else "never (the row form ships everywhere)"
     tiles_win = {(r["config"], r["max_side"]): r["tiles_ms"] <= r["rows_ms"] for r in doc["results"]}
     doc["tiles_not_above_rows"] = {"%s@%d" % k: bool(v) for k, v in tiles_win.items()}
     shipped_tiles = {(r["config"], r["max_side"]): bool(min_bin) and r["bin"] >= min_bin and r["bin"] > 1 for r in doc["results"]}
     doc["shipped_form_is_what_the_figures_ask_for"] = all(shipped_tiles[k] == tiles_win[k] for k in tiles_win)
-    json.dump(doc, open(a.out, "w"), indent=1)
-    print(json.dumps(doc, indent=1))
+    kit.write_doc(doc, a.out)
 
 
 if __name__ == "__main__":

@@ -17,31 +17,18 @@ import argparse
 import json
 import os
 import sys
-import time
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 sys.path.insert(0, ROOT)
 import numpy as np
 
-
-def make(cfg, moves):
-    from instagraal_amd import synth
-    from instagraal_amd.sampler import sampler as hip_sampler
-
-    prob = synth.make_problem(*synth.CONFIGS[cfg])
-    s = hip_sampler(**prob.sampler_kwargs(), device_id=0, coo=(prob.coo_row, prob.coo_col, prob.coo_cnt))
-    s.set_param_simu(dict(prob.params))
-    s.eval_likelihood_init()
-    np.random.seed(0)
-    if moves:
-        s.step_sampler_batch(np.resize(np.random.permutation(prob.n_frags), moves).astype(np.int32), 5)
-    return prob, s
+import _report_bench as kit
 
 
 def measure(cfg, moves, reps, warmup, windows, levels):
     from instagraal_amd import gap_support as gs, hip_lib
 
-    prob, s = make(cfg, moves)
+    prob, s = kit.make_sampler(cfg, moves)
     Z, M = int(prob.coo_row.size), int(prob.n_sub_frags)
     total = int(prob.coo_cnt.astype(np.int64).sum())
     rows = []
@@ -63,30 +50,16 @@ def measure(cfg, moves, reps, warmup, windows, levels):
                        verdicts={v: int((res["verdict"] == v).sum()) for v in ("adjacent", "gap", "apart", "none")})
             # the forms of the model pass alternate in blocks (other work shares the machine: a drift hits all alike)
             forms = ("model", "model_wave", "model_workgroup")
-            ms = {f: [] for f in forms}
-            blocks = 4
-            per = (reps + blocks - 1) // blocks
-            for _ in range(blocks):
-                cks = []
-                for f in forms:
-                    t, ck = s.ctx.debug_gap_support_time(w, j, gaps, which=f, n=warmup + per)
-                    ms[f].append(t[warmup:])
-                    cks.append(ck)
-                assert cks[0] == cks[1] == cks[2]
+            timed = lambda f: lambda n: s.ctx.debug_gap_support_time(w, j, gaps, which=f, n=n)  # noqa: E731
+            ms = dict(zip(forms, kit.alternate_blocks([timed(f) for f in forms], reps, warmup)))
             ms_o, _ = s.ctx.debug_gap_support_time(w, j, gaps, which="observed", n=warmup + reps)
             ms_jo, ms_jm, _, _ = s.ctx.debug_junction_profile_time(w, combine=False, n=warmup + reps, model=True, scan=False)
             out["timed_repetitions"] = int(np.concatenate(ms["model"]).size)
             for key, t in (("observed_us", ms_o[warmup:]), ("model_us", np.concatenate(ms["model"])), ("model_wave_us", np.concatenate(ms["model_wave"])),
                            ("model_workgroup_us", np.concatenate(ms["model_workgroup"])), ("junction_observed_one_atomic_per_end_us", ms_jo[warmup:]),
                            ("junction_model_us", ms_jm[warmup:])):
-                out[key] = round(1e3 * float(np.median(t)), 2)
-                out[key.replace("_us", "_min_us")] = round(1e3 * float(t.min()), 2)
-            t = []
-            for _ in range(warmup + reps):
-                t0 = time.perf_counter()
-                s.ctx.gap_support(w, j, gaps)
-                t.append(time.perf_counter() - t0)
-            out["whole_call_host_clock_ms"] = round(1e3 * float(np.median(t[warmup:])), 2)
+                kit.put_times(out, key, t)
+            out["whole_call_host_clock_ms"] = kit.host_clock_ms(lambda: s.ctx.gap_support(w, j, gaps), reps, warmup)
             out["bytes_streamed"] = 12 * Z + 16 * M  # row + (column, count) per contact; the 16-byte records once (gathers: L2)
             rows.append(out)
             print(json.dumps(out), flush=True)
@@ -112,9 +85,7 @@ def main():
     windows = [int(w) for w in a.windows.split(",") if w]
     levels = [x for x in a.levels.split(",") if x]
     doc["results"] = [r for cfg in a.configs.split(",") if cfg for r in measure(cfg, a.moves, a.reps, a.warmup, windows, levels)]
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    json.dump(doc, open(a.out, "w"), indent=1)
-    print(json.dumps(doc, indent=1))
+    kit.write_doc(doc, a.out)
 
 
 if __name__ == "__main__":

@@ -22,24 +22,14 @@ ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 sys.path.insert(0, ROOT)
 import numpy as np
 
+import _report_bench as kit
+
 SHAPES = dict(cfg3=("cfg3", 2000, False), cfg3_late=("cfg3_late", 0, False), bombed_start=("cfg3", 0, True),
               small=("small", 300, False), small_bombed=("small", 0, True))  # (the small ones: a dry run of the tool)
 
 
 def make(cfg, moves, bomb):
-    from instagraal_amd import synth
-    from instagraal_amd.sampler import sampler as hip_sampler
-
-    prob = synth.make_problem(*synth.CONFIGS[cfg])
-    s = hip_sampler(**prob.sampler_kwargs(), device_id=0, coo=(prob.coo_row, prob.coo_col, prob.coo_cnt))
-    s.set_param_simu(dict(prob.params))
-    s.eval_likelihood_init()
-    np.random.seed(0)
-    if bomb:
-        s.bomb_the_genome()
-    if moves:
-        s.step_sampler_batch(np.resize(np.random.permutation(prob.n_frags), moves).astype(np.int32), 5)
-    return prob, s
+    return kit.make_sampler(cfg, moves, prepare=(lambda s: s.bomb_the_genome()) if bomb else None)
 
 
 def host_inputs(s, prob):
@@ -62,8 +52,6 @@ def measure(shape, windows, reps, warmup, host):
     prob, s = make(cfg, moves, bomb)
     Z = int(prob.coo_row.size)
     rows = []
-    blocks = 4
-    per = (reps + blocks - 1) // blocks
     # the yardstick: the lift's passes over the same contacts, one atomic per contact and combined
     lift = {}
     for combine in (False, True):
@@ -75,15 +63,13 @@ def measure(shape, windows, reps, warmup, host):
     t = host_inputs(s, prob) if host else None
     for w in windows:
         out = dict(shape=shape, config=cfg, moves_before=moves, bombed=bomb, contacts=Z, window=w)
-        ms_by = {True: [], False: []}
-        sums = set()
-        for _ in range(blocks):  # the two forms alternate in blocks (other work shares the machine: a drift hits both alike)
-            for combine in (True, False):
+        def timed(combine):
+            def call(n):
                 s.ctx.debug_join_support_combine(combine)
-                ms, ck = s.ctx.debug_join_support_time(w, n=warmup + per)
-                ms_by[combine].append(ms[warmup:])
-                sums.add(ck)
-        assert len(sums) == 1, "the two forms of the emit kernel disagree"
+                return s.ctx.debug_join_support_time(w, n=n)
+            return call
+
+        ms_by = dict(zip((True, False), kit.alternate(timed(True), timed(False), reps, warmup, disagree="the two forms of the emit kernel disagree")))
         s.ctx.debug_join_support_combine(None)
         res = s.ctx.join_support(w)
         forms = s.ctx.debug_join_support_forms()
@@ -91,9 +77,9 @@ def measure(shape, windows, reps, warmup, host):
         s.ctx.join_support_release()
         out.update(n_contigs=res["n_contigs"], n_links=res["n_links"], contributions=res["contributions"], forms=forms,
                    in_reach_observed=res["in_reach_observed"], out_of_reach_observed=res["out_of_reach_observed"],
-                   pairs_total=int(pairs.sum()), pairs_max=int(pairs.max()) if pairs.size else 0, timed_builds_per_form=int(per * blocks))
+                   pairs_total=int(pairs.sum()), pairs_max=int(pairs.max()) if pairs.size else 0, timed_builds_per_form=int(ms_by[True].shape[0]))
         for combine, name in ((False, "one_atomic_per_emission"), (True, "combined")):
-            m = np.concatenate(ms_by[combine])
+            m = ms_by[combine]
             med = np.median(m, axis=0)
             out[name] = {p + "_us": round(1e3 * float(med[k]), 2) for k, p in enumerate(PASSES)}
             out[name]["all_passes_us"] = round(1e3 * float(np.median(m.sum(axis=1))), 2)
@@ -116,10 +102,7 @@ def measure(shape, windows, reps, warmup, host):
 
 def shipped_form():
     """JOIN_SHIP_COMBINE of the source the library is built from"""
-    import re
-
-    src = open(os.path.join(ROOT, "instagraal_amd", "csrc", "ig_host_join.inc")).read()
-    return "combined" if int(re.search(r"#define JOIN_SHIP_COMBINE (\d)", src).group(1)) else "one_atomic_per_emission"
+    return "combined" if kit.shipped_flag("ig_host_join.inc", "JOIN_SHIP_COMBINE") else "one_atomic_per_emission"
 
 
 def main():

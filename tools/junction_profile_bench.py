@@ -15,35 +15,20 @@ form the library was built with (JUNC_SHIP_COMBINE in csrc/ig_host_junc.inc) and
   python tools/junction_profile_bench.py [--configs cfg3,cfg3_late] [--out profiles/r09_junction_profile.json]
 """
 import argparse
-import json
 import os
-import re
 import sys
-import time
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 sys.path.insert(0, ROOT)
 import numpy as np
 
-
-def make(cfg, moves):
-    from instagraal_amd import synth
-    from instagraal_amd.sampler import sampler as hip_sampler
-
-    prob = synth.make_problem(*synth.CONFIGS[cfg])
-    s = hip_sampler(**prob.sampler_kwargs(), device_id=0, coo=(prob.coo_row, prob.coo_col, prob.coo_cnt))
-    s.set_param_simu(dict(prob.params))
-    s.eval_likelihood_init()
-    np.random.seed(0)
-    if moves:
-        s.step_sampler_batch(np.resize(np.random.permutation(prob.n_frags), moves).astype(np.int32), 5)
-    return prob, s
+import _report_bench as kit
 
 
 def measure(cfg, moves, reps, warmup, windows):
     from instagraal_amd import distance_law as dlaw, junction_profile as jp
 
-    prob, s = make(cfg, moves)
+    prob, s = kit.make_sampler(cfg, moves)
     Z, M = int(prob.coo_row.size), int(prob.n_sub_frags)
     total = int(prob.coo_cnt.astype(np.int64).sum())
     edges = dlaw.default_edges(s.mean_kb(), float(s.ctx.debug_tables()[0].max()))
@@ -56,28 +41,20 @@ def measure(cfg, moves, reps, warmup, windows):
         out.update(n_placed=prof["n_placed"], internal_junctions=prof["internal_junctions"],
                    in_window_share_of_counts=round(prof["in_window_observed"] / total, 4))
         # the two forms of the observed pass alternate in blocks (other work shares the machine: a drift hits both alike)
-        ms_a, ms_b, blocks = [], [], 4
-        per = (reps + blocks - 1) // blocks
-        for _ in range(blocks):
-            a_, _, _, ck_a = s.ctx.debug_junction_profile_time(w, combine=True, n=warmup + per, model=False, scan=False)
-            b_, _, _, ck_b = s.ctx.debug_junction_profile_time(w, combine=False, n=warmup + per, model=False, scan=False)
-            assert ck_a == ck_b
-            ms_a.append(a_[warmup:])
-            ms_b.append(b_[warmup:])
-        ms_a, ms_b = np.concatenate(ms_a), np.concatenate(ms_b)
+        def observed(combine):
+            def timed(n):
+                ms, _, _, ck = s.ctx.debug_junction_profile_time(w, combine=combine, n=n, model=False, scan=False)
+                return ms, ck
+            return timed
+
+        ms_a, ms_b = kit.alternate(observed(True), observed(False), reps, warmup)
         _, ms_m, ms_s, _ = s.ctx.debug_junction_profile_time(w, combine=True, n=warmup + reps)
         ms_m, ms_s, ms_l = ms_m[warmup:], ms_s[warmup:], ms_law[warmup:]
         out["timed_repetitions"] = int(ms_a.size)
         for key, ms in (("observed_combined_us", ms_a), ("observed_one_atomic_per_end_us", ms_b), ("model_us", ms_m), ("scan_us", ms_s),
                         ("law_observed_privatised_us", ms_l)):
-            out[key] = round(1e3 * float(np.median(ms)), 2)
-            out[key.replace("_us", "_min_us")] = round(1e3 * float(ms.min()), 2)
-        t = []
-        for _ in range(warmup + reps):
-            t0 = time.perf_counter()
-            s.ctx.junction_profile(w)
-            t.append(time.perf_counter() - t0)
-        out["whole_call_host_clock_ms"] = round(1e3 * float(np.median(t[warmup:])), 2)
+            kit.put_times(out, key, ms)
+        out["whole_call_host_clock_ms"] = kit.host_clock_ms(lambda: s.ctx.junction_profile(w), reps, warmup)
         out["bytes_streamed"] = 12 * Z + 16 * M  # row + (column, count) per contact; the 16-byte records once (gathers: L2)
         rows.append(out)
     s.free_gpu()
@@ -99,13 +76,8 @@ def main():
     windows = [int(w) for w in a.windows.split(",") if w]
     doc["results"] = [r for cfg in a.configs.split(",") if cfg for r in measure(cfg, a.moves, a.reps, a.warmup, windows)]
     ok = all(r["observed_combined_us"] <= r["observed_one_atomic_per_end_us"] for r in doc["results"])
-    src = open(os.path.join(ROOT, "instagraal_amd", "csrc", "ig_host_junc.inc")).read()
-    built = bool(int(re.search(r"#define JUNC_SHIP_COMBINE (\d)", src).group(1)))
-    doc["combined_not_above_yardstick_everywhere"] = ok
-    doc["observed_pass_shipped"] = "combined" if built else "one_atomic_per_end"
-    doc["shipped_form_is_what_the_figures_ask_for"] = built == ok
-    json.dump(doc, open(a.out, "w"), indent=1)
-    print(json.dumps(doc, indent=1))
+    kit.ship_verdict(doc, ok, bool(kit.shipped_flag("ig_host_junc.inc", "JUNC_SHIP_COMBINE")))
+    kit.write_doc(doc, a.out)
 
 
 if __name__ == "__main__":

@@ -19,33 +19,19 @@ ask for.
 import argparse
 import json
 import os
-import re
 import sys
-import time
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 sys.path.insert(0, ROOT)
 import numpy as np
 
-
-def make(cfg, moves):
-    from instagraal_amd import synth
-    from instagraal_amd.sampler import sampler as hip_sampler
-
-    prob = synth.make_problem(*synth.CONFIGS[cfg])
-    s = hip_sampler(**prob.sampler_kwargs(), device_id=0, coo=(prob.coo_row, prob.coo_col, prob.coo_cnt))
-    s.set_param_simu(dict(prob.params))
-    s.eval_likelihood_init()
-    np.random.seed(0)
-    if moves:
-        s.step_sampler_batch(np.resize(np.random.permutation(prob.n_frags), moves).astype(np.int32), 5)
-    return prob, s
+import _report_bench as kit
 
 
 def measure(cfg, moves, reps, warmup, windows, levels):
     from instagraal_amd import orientation_support as osup
 
-    prob, s = make(cfg, moves)
+    prob, s = kit.make_sampler(cfg, moves)
     Z, M = int(prob.coo_row.size), int(prob.n_sub_frags)
     total = int(prob.coo_cnt.astype(np.int64).sum())
     rows = []
@@ -60,28 +46,15 @@ def measure(cfg, moves, reps, warmup, windows, levels):
                        model_terms=int(2 * res["pairs"][res["status"] == 0].sum()),
                        workgroup_segments=int((2 * res["pairs"][res["status"] == 0] > 4096).sum()))
             # the two forms of the observed pass alternate in blocks (other work shares the machine: a drift hits both alike)
-            ms_a, ms_b, blocks = [], [], 4
-            per = (reps + blocks - 1) // blocks
-            for _ in range(blocks):
-                a_, ck_a = s.ctx.debug_orientation_support_time(w, f, l, which="observed", form="combined", n=warmup + per)
-                b_, ck_b = s.ctx.debug_orientation_support_time(w, f, l, which="observed", form="atomic", n=warmup + per)
-                assert ck_a == ck_b
-                ms_a.append(a_[warmup:])
-                ms_b.append(b_[warmup:])
-            ms_a, ms_b = np.concatenate(ms_a), np.concatenate(ms_b)
+            ms_a, ms_b = kit.alternate(lambda n: s.ctx.debug_orientation_support_time(w, f, l, which="observed", form="combined", n=n),
+                                       lambda n: s.ctx.debug_orientation_support_time(w, f, l, which="observed", form="atomic", n=n), reps, warmup)
             ms_m, _ = s.ctx.debug_orientation_support_time(w, f, l, which="model", form="default", n=warmup + reps)
             ms_j, _, _, _ = s.ctx.debug_junction_profile_time(w, combine=False, n=warmup + reps, model=False, scan=False)
             out["timed_repetitions"] = int(ms_a.size)
             for key, ms in (("observed_combined_us", ms_a), ("observed_one_atomic_per_end_us", ms_b), ("model_us", ms_m[warmup:]),
                             ("junction_observed_one_atomic_per_end_us", ms_j[warmup:])):
-                out[key] = round(1e3 * float(np.median(ms)), 2)
-                out[key.replace("_us", "_min_us")] = round(1e3 * float(ms.min()), 2)
-            t = []
-            for _ in range(warmup + reps):
-                t0 = time.perf_counter()
-                s.ctx.orientation_support(w, f, l)
-                t.append(time.perf_counter() - t0)
-            out["whole_call_host_clock_ms"] = round(1e3 * float(np.median(t[warmup:])), 2)
+                kit.put_times(out, key, ms)
+            out["whole_call_host_clock_ms"] = kit.host_clock_ms(lambda: s.ctx.orientation_support(w, f, l), reps, warmup)
             out["bytes_streamed"] = 12 * Z + 16 * M  # row + (column, count) per contact; the 16-byte records once (gathers: L2)
             rows.append(out)
             print(json.dumps(out), flush=True)
@@ -106,14 +79,8 @@ def main():
     levels = [x for x in a.levels.split(",") if x]
     doc["results"] = [r for cfg in a.configs.split(",") if cfg for r in measure(cfg, a.moves, a.reps, a.warmup, windows, levels)]
     ok = all(r["observed_combined_us"] <= r["observed_one_atomic_per_end_us"] for r in doc["results"])
-    src = open(os.path.join(ROOT, "instagraal_amd", "csrc", "ig_host_orient.inc")).read()
-    built = bool(int(re.search(r"#define ORIENT_SHIP_COMBINE (\d)", src).group(1)))
-    doc["combined_not_above_yardstick_everywhere"] = ok
-    doc["observed_pass_shipped"] = "combined" if built else "one_atomic_per_end"
-    doc["shipped_form_is_what_the_figures_ask_for"] = built == ok
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    json.dump(doc, open(a.out, "w"), indent=1)
-    print(json.dumps(doc, indent=1))
+    kit.ship_verdict(doc, ok, bool(kit.shipped_flag("ig_host_orient.inc", "ORIENT_SHIP_COMBINE")))
+    kit.write_doc(doc, a.out)
 
 
 if __name__ == "__main__":

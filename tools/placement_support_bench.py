@@ -16,45 +16,30 @@ PLACE_WAVE_ENTRIES changes only on that evidence.
 import argparse
 import json
 import os
-import re
 import sys
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 sys.path.insert(0, ROOT)
 import numpy as np
 
+import _report_bench as kit
+
 SHAPES = dict(cfg3=("cfg3", 2000), cfg3_late=("cfg3_late", 0), small=("small", 300), bigctg=("bigctg", 0))  # (the last two: a dry run of the tool)
 FORMS = ("thread", "wave", "default")
 
 
-def make(cfg, moves):
-    from instagraal_amd import synth
-    from instagraal_amd.sampler import sampler as hip_sampler
-
-    prob = synth.make_problem(*synth.CONFIGS[cfg])
-    s = hip_sampler(**prob.sampler_kwargs(), device_id=0, coo=(prob.coo_row, prob.coo_col, prob.coo_cnt))
-    s.set_param_simu(dict(prob.params))
-    s.eval_likelihood_init()
-    np.random.seed(0)
-    if moves:
-        s.step_sampler_batch(np.resize(np.random.permutation(prob.n_frags), moves).astype(np.int32), 5)
-    return prob, s
-
-
 def wave_entries():
     """PLACE_WAVE_ENTRIES of the source the library is built from"""
-    src = open(os.path.join(ROOT, "instagraal_amd", "csrc", "ig_kernels_place.cuh")).read()
-    return int(re.search(r"#define PLACE_WAVE_ENTRIES (\d+)", src).group(1))
+    return kit.shipped_flag("ig_kernels_place.cuh", "PLACE_WAVE_ENTRIES")
 
 
 def measure(shape, windows, reps, warmup):
     from instagraal_amd.hip_lib import ASSEMBLY_CONTACTS_PASSES as LIFT, PLACEMENT_SUPPORT_PASSES as PASSES
 
     cfg, moves = SHAPES[shape]
-    prob, s = make(cfg, moves)
+    prob, s = kit.make_sampler(cfg, moves)
     Z = int(prob.coo_row.size)
     blocks = 4
-    per = (reps + blocks - 1) // blocks
     s.ctx.debug_assembly_contacts_combine(False)  # the yardstick: the lift's passes over the same contacts, one atomic per contact
     ms, _ = s.ctx.debug_assembly_contacts_time("sub", n=warmup + reps)
     lift = np.median(ms[warmup:], axis=0)
@@ -63,19 +48,17 @@ def measure(shape, windows, reps, warmup):
     rows = []
     for w in windows:
         out = dict(shape=shape, config=cfg, moves_before=moves, contacts=Z, bins=int(prob.n_frags), window=w, min_hosts=w)
-        ms_by = {f: [] for f in FORMS}
-        sums = set()
-        for _ in range(blocks):  # the forms alternate in blocks (other work shares the machine: a drift hits all alike)
-            for form in FORMS:
+        def timed(form):
+            def call(n):
                 s.ctx.debug_placement_support_form(form)
-                ms, ck = s.ctx.debug_placement_support_time(w, n=warmup + per)
-                ms_by[form].append(ms[warmup:])
-                sums.add(ck)
-        assert len(sums) == 1, "the forms of the scan disagree"
+                return s.ctx.debug_placement_support_time(w, n=n)
+            return call
+
+        ms_by = dict(zip(FORMS, kit.alternate_blocks([timed(f) for f in FORMS], reps, warmup, blocks, "the forms of the scan disagree")))
         s.ctx.debug_placement_support_form("default")
         res = s.ctx.placement_support(w)
         out.update(n_contigs=res["n_contigs"], n_guests=res["n_guests"], entries=res["entries"], forms=s.ctx.debug_placement_support_forms(),
-                   with_a_best_site=int((res["best_contig"] >= 0).sum()), timed_calls_per_form=int(per * blocks))
+                   with_a_best_site=int((res["best_contig"] >= 0).sum()), timed_calls_per_form=int(sum(len(b) for b in ms_by[FORMS[0]])))
         for form in FORMS:
             m = np.concatenate(ms_by[form])
             med = np.median(m, axis=0)
