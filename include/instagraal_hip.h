@@ -301,7 +301,8 @@ int ig_junction_profile(ig_ctx* ctx, int32_t window, int64_t* observed, int64_t*
  * ig_assembly_contacts_release, by the next build (also one that fails: no stale result is ever visible), by ig_upload_contacts
  * and by ig_destroy.  ig_assembly_contacts_rows copies rowptr (capacity: words of room, n_units + 1 needed),
  * ig_assembly_contacts_fetch the entries first .. first + n - 1 (so that a host takes 5 10^8 entries in pieces); without a built
- * result, out of range, or with a level other than 0 and 1 they return an error and write nothing.
+ * result, out of range, or with a level other than 0 and 1 they return an error and write nothing.  They serve the snapshots of
+ * ig_assembly_contacts_build_units and ig_assembly_contacts_coarsen (below) as they serve one of level 1.
  * Device memory: 8 bytes per kept entry while the result lives (level 1: 12 per summed entry), 16 during a build that has long rows.
  * Guards and effects as ig_contact_map: reads the CURRENT coordinates, changes nothing a move reads, synchronous, an error while a
  * nuisance step or a chain is in flight.  A sharded handle (ig_set_shard) takes its shard's rows: the ranks' results, merged entry by
@@ -636,6 +637,40 @@ int ig_model_values_host(const float params[8], const float* s, int64_t n, int64
  * scalars; else expected_q), each weighted by its place: every form of the model pass must agree on it */
 int ig_debug_gap_support_time(ig_ctx* ctx, int32_t window, int32_t n_junc, const int32_t* junction, int32_t n_gaps, const float* gaps_kb, int32_t pass, int32_t n,
                               float* ms_n, int64_t* checksum);
+
+/* ---- fixed-resolution maps of the current genome: the contacts at a caller's unit per position, and a built level coarsened to
+ * the next (the rule: instagraal_amd/zoom_levels.py).  The device reproduces the rule's arrays byte for byte. */
+/* ig_assembly_contacts_build at level 1 with the caller's units: unit[n_positions] is the unit of every position of
+ * ig_contact_map_order, non-decreasing along the order, inside 0 .. n_units - 1; it may step by more than one (the rows of the
+ * units without a position are empty).  Refused on the host before any work on the device: n_units of 2^31 or more, a table that is
+ * not monotone or out of range; then n_positions != T.  The result is a snapshot as ig_assembly_contacts_build's (n_units rows):
+ * ig_assembly_contacts_rows, _fetch and _release serve it, the same scalars, the same guards, sharding as there.  The earlier
+ * snapshot is gone whatever happens. */
+int ig_assembly_contacts_build_units(ig_ctx* ctx, const int32_t* unit, int64_t n_positions, int64_t n_units, int64_t* n_entries, int64_t scalars[8]);
+/* Replaces the built, summed snapshot (ig_assembly_contacts_build at level 1, _build_units, or an earlier coarsening) by its
+ * coarsening: entry (lo, hi, c) goes to (coarse_of_unit[lo], coarse_of_unit[hi]), equal entries are summed in 64 bits (a count may
+ * exceed 2^32).  coarse_of_unit[n_units]: non-decreasing, inside 0 .. n_coarse - 1; n_units: the snapshot's.  The contacts are not
+ * read again.  scalars: {0, 1 the entries read, 2 contacts_kept, 3, 4, 5 as the snapshot's build gave them, 6 n_coarse, 7
+ * entries_out = *n_entries}.  Refused, with NOTHING left built: no snapshot, a level 0 snapshot, another n_units, a map that is not
+ * monotone or out of range, a coarse row of 2^32 entries or more before summing.  Device memory during the call: the old and the
+ * new level, 8 bytes per old entry (16 with long rows), a bit per entry.  On a sharded handle the coarsening of the shard's snapshot
+ * is that shard of the coarsened whole.  Writes nothing a move reads. */
+int ig_assembly_contacts_coarsen(ig_ctx* ctx, const int32_t* coarse_of_unit, int64_t n_units, int64_t n_coarse, int64_t* n_entries, int64_t scalars[8]);
+/* ig_balance_build at level 1 with the caller's units (the table as for ig_assembly_contacts_build_units, the same refusals);
+ * ig_balance_rows, _fetch, _run and _release then work on it unchanged. */
+int ig_balance_build_units(ig_ctx* ctx, const int32_t* unit, int64_t n_positions, int64_t n_units, int32_t ignore_diags, int64_t* n_entries, int64_t scalars[8]);
+/* tests: the coarsening over caller data, unchanged: the CSR level rowptr[n_rows + 1] (from 0, non-decreasing), col and count
+ * [rowptr[n_rows]] (columns inside 0 .. n_rows - 1) under coarse_of_unit[n_rows] into n_coarse rows; the limits of
+ * ig_debug_assembly_contacts_limits hold; forms: as ig_debug_assembly_contacts_forms, of the segments.  The result waits on the host
+ * for ig_debug_zoom_fetch; nothing stays on the device.  Needs a created handle, nothing uploaded. */
+int ig_debug_zoom_coarsen(ig_ctx* ctx, const int64_t* rowptr, const int32_t* col, const int64_t* count, int64_t n_rows, const int32_t* coarse_of_unit,
+                          int64_t n_coarse, int64_t* n_out, int64_t forms[8]);
+/* the last ig_debug_zoom_coarsen's result: rowptr[n_coarse + 1] (n_rowptr: the caller's capacity), col and count [n_out] (capacity) */
+int ig_debug_zoom_fetch(ig_ctx* ctx, int64_t* rowptr, int64_t n_rowptr, int32_t* col, int64_t* count, int64_t capacity);
+/* the coarsening of the built snapshot under coarse_of_unit (NULL: two units to one, n_units and n_coarse are not read) n times, hipEvents
+ * around each pass: ms_n[n][6] = {segment starts, words, sort short, sort lds, sort long, reduce}.  The snapshot is read only and stays
+ * as it is; *checksum (may be NULL): the rows, columns and counts of the last repeat, each word weighted by its place */
+int ig_debug_zoom_time(ig_ctx* ctx, const int32_t* coarse_of_unit, int64_t n_units, int64_t n_coarse, int32_t n, float* ms_n, int64_t* checksum);
 #ifdef __cplusplus
 }
 #endif

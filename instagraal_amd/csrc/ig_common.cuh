@@ -413,11 +413,13 @@ struct LiftBuf {
     unsigned long long* incl = nullptr;  /* [M + 1] ... and their running sum */
     unsigned long long* htot = nullptr;  /* that scan's chunk totals */
     unsigned long long* sc = nullptr;    /* LIFT_NS scalars of the passes over the contacts */
+    int* unit = nullptr;                 /* [T] level 2: the caller's unit of every position, one build's */
     int M = 0;
     RowBuf rows;                         /* reserved for M rows with the buffers above */
     bool valid = false;
-    int level = 0;
+    int level = 0;                       /* 0 positions, 1 placed bins, 2 a caller's units or a coarsening (ig_host_zoom.inc) */
     long long n_placed = 0, n_units = 0, n_entries = 0;
+    long long contacts_kept = 0, unplaced[2] = {0, 0}; /* of the build the snapshot comes from: a coarsening carries them over */
     long long forms[8] = {0, 0, 0, 0, 0, 0, 0, 0}; /* the last build's LIFT_C_* words */
     int short_max = 0, lds_max = 0;       /* ig_debug_assembly_contacts_limits, 0: the default */
     bool no_combine = false;              /* ig_debug_assembly_contacts_combine(0): one atomic per contact in the two passes */
@@ -476,6 +478,7 @@ struct BalBuf {
     /* the snapshot: rows.rowptr [U + 1], rows.out_col and rows.out_cnt [n_entries], and the totals on the host */
     RowBuf rows;
     std::vector<long long> h_total;
+    int* unit = nullptr;                 /* [T] a build with the caller's unit of every position (ig_balance_build_units) */
     bool valid = false;
     int level = 0;
     long long n_placed = 0, n_units = 0, n_entries = 0;
@@ -649,6 +652,7 @@ struct ig_ctx {
     OrientBuf orient;
     GapBuf gap;
     DebugRows debug_rows;
+    DebugRows debug_zoom; /* the last ig_debug_zoom_coarsen's result (ig_debug_zoom_fetch) */
     int* batch_out; /* committed moves, pending slot, (unused), candidates, predicted deltas used, contigs */
     int *host_bo, *host_bo_dev; /* the same in mapped host memory (+ [7] = sequence number of the decide launch), and its device address */
     int bo_seq;

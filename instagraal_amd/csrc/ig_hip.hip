@@ -68,8 +68,9 @@
 #include "ig_kernels_orient.cuh"
 #include "ig_kernels_bal.cuh"
 #include "ig_kernels_gap.cuh"
+#include "ig_kernels_zoom.cuh"
 
-/* ================================================================== host side (one translation unit, seventeen parts) */
+/* ================================================================== host side (one translation unit, eighteen parts) */
 #include "ig_host_core.inc"
 #include "ig_host_upload.inc"
 #include "ig_host_genome.inc"
@@ -84,6 +85,7 @@
 #include "ig_host_orient.inc"
 #include "ig_host_bal.inc"
 #include "ig_host_gap.inc"
+#include "ig_host_zoom.inc"
 #include "ig_host_batch.inc"
 #include "ig_host_nuis.inc"
 #include "ig_host_debug.inc"

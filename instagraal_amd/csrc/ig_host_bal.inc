@@ -27,7 +27,8 @@ static void bal_free_build(ig_ctx* c)
     hipFree(p.htot);
     hipFree(p.sc);
     hipFree(p.total);
-    p.key = nullptr;
+    hipFree(p.unit);
+    p.key = p.unit = nullptr;
     p.head = p.incl = p.htot = p.sc = p.total = nullptr;
     rows_free_temp(p.rows);
     rows_free_reserve(p.rows);
@@ -62,8 +63,11 @@ static void free_bal_buffers(ig_ctx* c)
     bal_release_snapshot(c);
 }
 
-/* The build up to the snapshot's fields: the units and every sub-fragment's key, then the rows (rows_build) from k_bal_emit. */
-static int bal_build_impl(ig_ctx* c, const char* who, int level, int max_side, int ignore_diags, float* ms, long long scalars[8])
+/* The build up to the snapshot's fields: the units and every sub-fragment's key, then the rows (rows_build) from k_bal_emit.
+ * unit_tab (ig_balance_build_units, ig_host_zoom.inc; else null; level is 1 then): the caller's unit of each of n_positions
+ * positions, checked by the caller to be non-decreasing and inside 0 .. n_units_tab - 1. */
+static int bal_build_impl(ig_ctx* c, const char* who, int level, int max_side, int ignore_diags, float* ms, long long scalars[8], const int32_t* unit_tab = nullptr,
+                          long long n_positions = 0, long long n_units_tab = 0)
 {
     BalBuf& p = c->bal;
     if (!c->have_contacts) return fail("%s: upload the contacts first", who);
@@ -79,13 +83,20 @@ static int bal_build_impl(ig_ctx* c, const char* who, int level, int max_side, i
         if (genome_positions(c, who, 0, &T)) return -1;
         U = T;
     }
+    if (unit_tab) {
+        if (n_positions != T) return fail("%s: the unit table has %lld entries, the genome %d positions", who, n_positions, T);
+        U = n_units_tab;
+    }
     const int M = c->M;
     LiftTimer timer(c, ms, BAL_PASSES);
     DALLOC(p.key, (size_t)M);
     DALLOC(p.sc, (size_t)BAL_NS);
     HIPCK(hipMemsetAsync(p.sc, 0, BAL_NS * sizeof(unsigned long long), c->stream));
     timer.begin();
-    if (level == 1 && T > 0) {
+    if (unit_tab) {
+        DALLOC(p.unit, (size_t)std::max(T, 1));
+        if (T > 0) HIPCK(hipMemcpyAsync(p.unit, unit_tab, (size_t)T * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    } else if (level == 1 && T > 0) {
         DALLOC(p.head, (size_t)T + 1);
         DALLOC(p.incl, (size_t)T + 1);
         DALLOC(p.htot, (size_t)scan_chunks(T + 1));
@@ -98,8 +109,11 @@ static int bal_build_impl(ig_ctx* c, const char* who, int level, int max_side, i
         U = (long long)n_units;
     }
     /* (level 2: the view's pixels are the units already; k_lift_keys keeps those inside 0 .. U - 1) */
-    hipLaunchKernelGGL(k_lift_keys, dim3((M + LIFT_THREADS - 1) / LIFT_THREADS), dim3(LIFT_THREADS), 0, c->stream, c->genome.pix, M, level == 2 ? (int)U : T,
-                       level == 1 && T > 0 ? p.incl : nullptr, p.key);
+    if (unit_tab)
+        hipLaunchKernelGGL(k_zoom_keys, dim3((M + LIFT_THREADS - 1) / LIFT_THREADS), dim3(LIFT_THREADS), 0, c->stream, c->genome.pix, M, T, p.unit, p.key);
+    else
+        hipLaunchKernelGGL(k_lift_keys, dim3((M + LIFT_THREADS - 1) / LIFT_THREADS), dim3(LIFT_THREADS), 0, c->stream, c->genome.pix, M, level == 2 ? (int)U : T,
+                           level == 1 && T > 0 ? p.incl : nullptr, p.key);
     timer.end(BAL_P_UNITS);
     const int Ui = (int)U;
     DALLOC(p.total, (size_t)U);
@@ -139,13 +153,14 @@ static int bal_build_impl(ig_ctx* c, const char* who, int level, int max_side, i
     return 0;
 }
 
-static int bal_build(ig_ctx* c, const char* who, int level, int max_side, int ignore_diags, float* ms, long long scalars[8])
+static int bal_build(ig_ctx* c, const char* who, int level, int max_side, int ignore_diags, float* ms, long long scalars[8], const int32_t* unit_tab = nullptr,
+                     long long n_positions = 0, long long n_units_tab = 0)
 {
     free_bal_buffers(c); /* whatever happens, the result of an earlier build is gone */
     if (level < 0 || level > 2) return fail("%s: level is 0 (sub-fragments), 1 (bins) or 2 (the pixels of the contact map), got %d", who, level);
     if (level == 2 && max_side < 1) return fail("%s: max_side must be >= 1 (got %d)", who, max_side);
     if (ignore_diags < 1) return fail("%s: ignore_diags must be >= 1: the device holds no diagonal (got %d)", who, ignore_diags);
-    const int rc = bal_build_impl(c, who, level, max_side, ignore_diags, ms, scalars);
+    const int rc = bal_build_impl(c, who, level, max_side, ignore_diags, ms, scalars, unit_tab, n_positions, n_units_tab);
     bal_free_build(c);
     if (rc) {
         bal_release_snapshot(c);

@@ -19,6 +19,7 @@ static void lift_release_snapshot(ig_ctx* c)
     rows_free_result(l.rows);
     l.valid = false;
     l.n_units = l.n_entries = 0;
+    l.contacts_kept = l.unplaced[0] = l.unplaced[1] = 0;
 }
 
 /* everything but the settings of ig_debug_assembly_contacts_limits / _combine, which belong to the handle */
@@ -31,6 +32,7 @@ static void free_lift_buffers(ig_ctx* c)
     hipFree(l.incl);
     hipFree(l.htot);
     hipFree(l.sc);
+    hipFree(l.unit);
     const int short_max = l.short_max, lds_max = l.lds_max;
     const bool no_combine = l.no_combine;
     l = LiftBuf{};
@@ -40,8 +42,10 @@ static void free_lift_buffers(ig_ctx* c)
 }
 
 /* The build, up to the snapshot's fields: the units and every sub-fragment's key, then the rows (rows_build) from k_lift_pass.  The
- * caller frees what it leaves behind (rows_free_temp) and, on an error, the half-built snapshot. */
-static int lift_build_impl(ig_ctx* c, const char* who, int level, float* ms)
+ * caller frees what it leaves behind (rows_free_temp, l.unit) and, on an error, the half-built snapshot.
+ * unit_tab (level 2, ig_host_zoom.inc; else null): the caller's unit of each of n_positions positions, checked by the caller to be
+ * non-decreasing and inside 0 .. n_units_tab - 1; the rows are summed as at level 1. */
+static int lift_build_impl(ig_ctx* c, const char* who, int level, float* ms, const int32_t* unit_tab = nullptr, long long n_positions = 0, long long n_units_tab = 0)
 {
     LiftBuf& l = c->lift;
     if (!c->have_contacts) return fail("%s: upload the contacts first", who);
@@ -58,9 +62,10 @@ static int lift_build_impl(ig_ctx* c, const char* who, int level, float* ms)
         if (rows_reserve(l.rows, M)) return -1;
         l.M = M;
     }
+    if (unit_tab && n_positions != T) return fail("%s: the unit table has %lld entries, the genome %d positions", who, n_positions, T);
     LiftTimer timer(c, ms, LIFT_PASSES);
     /* the units */
-    long long U = T;
+    long long U = unit_tab ? n_units_tab : T;
     if (level == 1 && T > 0) {
         hipLaunchKernelGGL(k_lift_heads, dim3((T + LIFT_THREADS - 1) / LIFT_THREADS), dim3(LIFT_THREADS), 0, c->stream, c->sub_tab, c->genome.order, T, l.head);
         scan64_enqueue(c, l.head, l.incl, 0, T, 1, l.htot);
@@ -70,8 +75,15 @@ static int lift_build_impl(ig_ctx* c, const char* who, int level, float* ms)
         if (n_units < 1 || n_units > (unsigned long long)T) return fail("%s: %llu units over %d positions (inconsistent tables)", who, n_units, T);
         U = (long long)n_units;
     }
-    hipLaunchKernelGGL(k_lift_keys, dim3((M + LIFT_THREADS - 1) / LIFT_THREADS), dim3(LIFT_THREADS), 0, c->stream, c->genome.pix, M, T, level == 1 ? l.incl : nullptr,
-                       l.key);
+    if (unit_tab) {
+        hipFree(l.unit);
+        l.unit = nullptr;
+        DALLOC(l.unit, (size_t)std::max(T, 1));
+        if (T > 0) HIPCK(hipMemcpyAsync(l.unit, unit_tab, (size_t)T * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+        hipLaunchKernelGGL(k_zoom_keys, dim3((M + LIFT_THREADS - 1) / LIFT_THREADS), dim3(LIFT_THREADS), 0, c->stream, c->genome.pix, M, T, l.unit, l.key);
+    } else
+        hipLaunchKernelGGL(k_lift_keys, dim3((M + LIFT_THREADS - 1) / LIFT_THREADS), dim3(LIFT_THREADS), 0, c->stream, c->genome.pix, M, T, level == 1 ? l.incl : nullptr,
+                           l.key);
     const int Ui = (int)U;
     HIPCK(hipMemsetAsync(l.sc, 0, LIFT_NS * sizeof(unsigned long long), c->stream));
     auto emit = [&](bool scatter, unsigned long long* slots, unsigned long long* ent, unsigned long long n_ent) {
@@ -87,7 +99,7 @@ static int lift_build_impl(ig_ctx* c, const char* who, int level, float* ms)
             hipLaunchKernelGGL((k_lift_pass<true, true>), grid, block, 0, c->stream, c->crow, c->cc, c->Z, l.key, Ui, slots, ent, n_ent, l.sc, c->rank, c->world);
     };
     auto check = [&](long long K) { return K < 0 || K > c->Z ? fail("%s: %lld entries kept of %lld (device error)", who, K, (long long)c->Z) : 0; };
-    const RowsSpec spec = {l.sc, LIFT_NS, LIFT_ENTRIES_KEPT, 0, "", level == 1, {LIFT_P_COUNT, LIFT_P_SCAN, LIFT_P_SCATTER, LIFT_P_SORT_SHORT, LIFT_P_REDUCE}};
+    const RowsSpec spec = {l.sc, LIFT_NS, LIFT_ENTRIES_KEPT, 0, "", level != 0, {LIFT_P_COUNT, LIFT_P_SCAN, LIFT_P_SCATTER, LIFT_P_SORT_SHORT, LIFT_P_REDUCE}};
     unsigned long long sc[LIFT_NS];
     long long K = 0, n_out = 0;
     if (rows_build(c, who, l.rows, Ui, spec, sc, check, emit, timer, l.forms, &K, &n_out)) return -1;
@@ -100,12 +112,15 @@ static int lift_build_impl(ig_ctx* c, const char* who, int level, float* ms)
 }
 
 /* scalars: the eight words of assembly_contacts.SCALARS */
-static int lift_build(ig_ctx* c, const char* who, int level, float* ms, long long scalars[8])
+static int lift_build(ig_ctx* c, const char* who, int level, float* ms, long long scalars[8], const int32_t* unit_tab = nullptr, long long n_positions = 0,
+                      long long n_units_tab = 0)
 {
     lift_release_snapshot(c); /* whatever happens, the result of an earlier build is gone */
-    if (level != 0 && level != 1) return fail("%s: level is 0 (sub-fragments) or 1 (bins), got %d", who, level);
-    const int rc = lift_build_impl(c, who, level, ms);
+    if (unit_tab ? level != 2 : level != 0 && level != 1) return fail("%s: level is 0 (sub-fragments) or 1 (bins), got %d", who, level);
+    const int rc = lift_build_impl(c, who, level, ms, unit_tab, n_positions, n_units_tab);
     rows_free_temp(c->lift.rows);
+    hipFree(c->lift.unit);
+    c->lift.unit = nullptr;
     if (rc) {
         lift_release_snapshot(c);
         return rc;
@@ -120,6 +135,9 @@ static int lift_build(ig_ctx* c, const char* who, int level, float* ms, long lon
     scalars[5] = l.n_placed;
     scalars[6] = l.n_units;
     scalars[7] = l.n_entries;
+    l.contacts_kept = scalars[LIFT_CONTACTS_KEPT];
+    l.unplaced[0] = scalars[LIFT_ENTRIES_UNPLACED];
+    l.unplaced[1] = scalars[LIFT_CONTACTS_UNPLACED];
     l.valid = true;
     return 0;
 }
@@ -159,7 +177,7 @@ extern "C" int ig_assembly_contacts_fetch(ig_ctx* c, int64_t first, int64_t n, i
         return fail("ig_assembly_contacts_fetch: entries %lld .. %lld are out of range (the result has %lld)", (long long)first, (long long)first + (long long)n, l.n_entries);
     if (n == 0) return 0;
     if (!col || !count) return fail("ig_assembly_contacts_fetch: NULL output");
-    if (l.level == 1) {
+    if (l.level != 0) { /* reduced: the bins, a caller's units, a coarsening */
         HIPCK(hipMemcpy(col, l.rows.out_col + first, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
         HIPCK(hipMemcpy(count, l.rows.out_cnt + first, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost));
         return 0;

@@ -187,10 +187,12 @@ static int lift_sort_rows(ig_ctx* c, const char* who, LiftTimer& timer, int pass
 
 /* The runs of equal columns inside a row become one entry each: heads per chunk, their scan, the sums; the heads per row, their
  * scan.  d_heads: a zeroed word on the device; count: [U + 1] words, tot: the scan's totals (both
- * scratch).  Allocates the result (*out_col, *out_cnt: [*n_out]; *rowptr: [U + 1]); everything is enqueued, the caller waits. */
+ * scratch).  Allocates the result (*out_col, *out_cnt: [*n_out]; *rowptr: [U + 1]); everything is enqueued, the caller waits.
+ * gather (the coarsening, ig_host_zoom.inc): the low half of an entry is its index inside its row, and what its run sums is
+ * gather[rowstart + index], a 64-bit count (k_zoom_reduce); null: the low half is the count itself (k_lift_reduce). */
 static int lift_reduce_rows(ig_ctx* c, const char* who, LiftTimer& timer, int pass, const unsigned long long* rowstart, int Ui, const unsigned long long* ent,
                             long long K, unsigned long long* d_heads, unsigned long long* count, unsigned long long* tot, LiftWork& w, int** out_col,
-                            unsigned long long** out_cnt, unsigned long long** rowptr, long long* n_out)
+                            unsigned long long** out_cnt, unsigned long long** rowptr, long long* n_out, const unsigned long long* gather = nullptr)
 {
     const long long U = Ui;
     const long long chunks = scan_chunks(K);
@@ -211,8 +213,12 @@ static int lift_reduce_rows(ig_ctx* c, const char* who, LiftTimer& timer, int pa
     DALLOC(*rowptr, (size_t)U + 1);
     HIPCK(hipMemsetAsync(*out_cnt, 0, (size_t)*n_out * sizeof(unsigned long long), c->stream));
     HIPCK(hipMemsetAsync(count, 0, ((size_t)U + 1) * sizeof(unsigned long long), c->stream));
-    hipLaunchKernelGGL(k_lift_reduce, dim3((unsigned)chunks), dim3(SCAN_THREADS), 0, c->stream, ent, w.bits, K, w.rtot, rowstart, Ui, (unsigned long long)*n_out,
-                       *out_col, *out_cnt, count);
+    if (gather)
+        hipLaunchKernelGGL(k_zoom_reduce, dim3((unsigned)chunks), dim3(SCAN_THREADS), 0, c->stream, ent, w.bits, K, w.rtot, rowstart, Ui, gather,
+                           (unsigned long long)*n_out, *out_col, *out_cnt, count);
+    else
+        hipLaunchKernelGGL(k_lift_reduce, dim3((unsigned)chunks), dim3(SCAN_THREADS), 0, c->stream, ent, w.bits, K, w.rtot, rowstart, Ui, (unsigned long long)*n_out,
+                           *out_col, *out_cnt, count);
     HIPCK(hipMemsetAsync(*rowptr, 0, sizeof(unsigned long long), c->stream));
     scan64_enqueue(c, count, *rowptr + 1, 0, Ui, 1, tot);
     timer.end(pass);

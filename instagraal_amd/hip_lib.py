@@ -18,8 +18,8 @@ SRC = os.path.join(HERE, "csrc", "ig_hip.hip")
 SRC_HOST = os.path.join(HERE, "csrc", "ig_draw.cpp")  # host-only part: the candidate draw
 DEPS = [SRC, SRC_HOST] + [os.path.join(HERE, "csrc", f) for f in ("ig_ops.cuh", "ig_common.cuh", "ig_model.cuh", "ig_kernels_setup.cuh",
                                                           "ig_kernels_score.cuh", "ig_kernels_screen.cuh", "ig_kernels_commit.cuh",
-                                                          "ig_kernels_nuis.cuh", "ig_kernels_wave.cuh", "ig_kernels_genome.cuh", "ig_kernels_rows.cuh", "ig_kernels_map.cuh", "ig_kernels_law.cuh", "ig_kernels_junc.cuh", "ig_kernels_lift.cuh", "ig_kernels_join.cuh", "ig_kernels_emap.cuh", "ig_kernels_place.cuh", "ig_kernels_orient.cuh", "ig_kernels_bal.cuh", "ig_kernels_gap.cuh", "ig_host_core.inc", "ig_host_upload.inc", "ig_host_genome.inc", "ig_host_rows.inc",
-                                                          "ig_host_map.inc", "ig_host_law.inc", "ig_host_junc.inc", "ig_host_lift.inc", "ig_host_join.inc", "ig_host_emap.inc", "ig_host_place.inc", "ig_host_orient.inc", "ig_host_bal.inc", "ig_host_gap.inc",
+                                                          "ig_kernels_nuis.cuh", "ig_kernels_wave.cuh", "ig_kernels_genome.cuh", "ig_kernels_rows.cuh", "ig_kernels_map.cuh", "ig_kernels_law.cuh", "ig_kernels_junc.cuh", "ig_kernels_lift.cuh", "ig_kernels_join.cuh", "ig_kernels_emap.cuh", "ig_kernels_place.cuh", "ig_kernels_orient.cuh", "ig_kernels_bal.cuh", "ig_kernels_gap.cuh", "ig_kernels_zoom.cuh", "ig_host_core.inc", "ig_host_upload.inc", "ig_host_genome.inc", "ig_host_rows.inc",
+                                                          "ig_host_map.inc", "ig_host_law.inc", "ig_host_junc.inc", "ig_host_lift.inc", "ig_host_join.inc", "ig_host_emap.inc", "ig_host_place.inc", "ig_host_orient.inc", "ig_host_bal.inc", "ig_host_gap.inc", "ig_host_zoom.inc",
                                                           "ig_host_batch.inc", "ig_host_nuis.inc", "ig_host_debug.inc")] + \
        [os.path.join(ROOT, "include", f) for f in ("ig_detmath.h", "ig_detmath_tables.h", "instagraal_hip.h")]
 
@@ -33,6 +33,7 @@ ORIENTATION_SUPPORT_FORMS = {"observed": ("atomic", "combined"), "model": ("defa
 GAP_SUPPORT_WAVE_TERMS = 8192  # GAP_WAVE_TERMS (csrc/ig_kernels_gap.cuh): pairs * gaps beyond this take a workgroup in the model pass
 GAP_SUPPORT_PASSES = ("observed", "model", "model_wave", "model_workgroup")  # ig_debug_gap_support_time
 BALANCE_BUILD_PASSES = ("units", "count", "rows", "scatter", "sort_short", "sort_lds", "sort_long", "reduce")  # ig_debug_balance_build_time
+ZOOM_PASSES = ("rowstart", "words", "sort_short", "sort_lds", "sort_long", "reduce")  # the passes of ig_assembly_contacts_coarsen
 BALANCE_FORMS = ("default", "wave", "packed")  # ig_debug_balance_form
 MAX_CANDIDATES = 16
 
@@ -850,6 +851,86 @@ class Context:
         ms = np.zeros((int(n), len(ASSEMBLY_CONTACTS_PASSES)), np.float32)
         ck = C.c_int64()
         _ck(lib().ig_debug_assembly_contacts_time(self._h, C.c_int32(LEVELS.index(level)), C.c_int32(int(n)), _p(ms), C.byref(ck)))
+        return ms, int(ck.value)
+
+    # ---- fixed-resolution maps: a caller's unit per position, and a built level coarsened (the rule: zoom_levels.py)
+    @staticmethod
+    def _unit_table(unit, n_units, what):
+        from .zoom_levels import MAX_UNITS
+
+        src = np.asarray(unit)
+        if src.ndim != 1 or not (src.size == 0 or np.issubdtype(src.dtype, np.integer)):
+            raise HipError("%s: one vector of integers" % what)
+        if int(n_units) < 0 or int(n_units) > MAX_UNITS:
+            raise HipError("%s: n_units is 0 .. 2^31 - 1 (got %d)" % (what, int(n_units)))
+        if src.size and (int(src.min()) < -(1 << 31) or int(src.max()) >= 1 << 31):
+            raise HipError("%s: out of range (a unit is 32 bits)" % what)
+        return np.ascontiguousarray(src, np.int32)
+
+    def _lift_result(self, n_units, ne, sc):
+        from .assembly_contacts import SCALARS
+
+        rowptr = np.zeros(int(n_units) + 1, np.int64)
+        _ck(lib().ig_assembly_contacts_rows(self._h, _p(rowptr), C.c_int64(rowptr.size)))
+        out = dict(rowptr=rowptr, n_entries=int(ne.value))
+        out.update((k, int(v)) for k, v in zip(SCALARS, sc))
+        return out
+
+    def assembly_contacts_units(self, unit, n_units):
+        """``assembly_contacts("bin")`` with the caller's unit of every position of ``contact_map_order`` (non-decreasing, inside
+        0 .. n_units - 1, gaps allowed) -> dict: rowptr (int64 [n_units + 1]), n_entries and the scalars of
+        ``assembly_contacts.SCALARS``; a snapshot: the entries come through ``assembly_contacts_fetch``"""
+        t = self._unit_table(unit, n_units, "assembly_contacts_units: unit table")
+        ne, sc = C.c_int64(), np.zeros(8, np.int64)
+        _ck(lib().ig_assembly_contacts_build_units(self._h, _p(t), C.c_int64(t.size), C.c_int64(int(n_units)), C.byref(ne), _p(sc)))
+        return self._lift_result(n_units, ne, sc)
+
+    def assembly_contacts_coarsen(self, coarse_of_unit, n_coarse):
+        """replaces the built, summed snapshot by its coarsening under ``coarse_of_unit`` (one entry per unit of the snapshot,
+        non-decreasing, inside 0 .. n_coarse - 1) without reading the contacts again -> dict as ``assembly_contacts_units``; a
+        refusal leaves nothing built"""
+        t = self._unit_table(coarse_of_unit, n_coarse, "assembly_contacts_coarsen: coarse map")
+        ne, sc = C.c_int64(), np.zeros(8, np.int64)
+        _ck(lib().ig_assembly_contacts_coarsen(self._h, _p(t), C.c_int64(t.size), C.c_int64(int(n_coarse)), C.byref(ne), _p(sc)))
+        return self._lift_result(n_coarse, ne, sc)
+
+    def balance_build_units(self, unit, n_units, ignore_diags=2):
+        """``balance_build("bin")`` with the caller's unit of every position -> the dict ``balance_build`` returns (level: "units")"""
+        from .balance import SCALARS
+
+        t = self._unit_table(unit, n_units, "balance_build_units: unit table")
+        ne, sc = C.c_int64(), np.zeros(8, np.int64)
+        _ck(lib().ig_balance_build_units(self._h, _p(t), C.c_int64(t.size), C.c_int64(int(n_units)), C.c_int32(int(ignore_diags)), C.byref(ne), _p(sc)))
+        U = int(n_units)
+        rowptr, nnz, total = np.zeros(U + 1, np.int64), np.zeros(U, np.int64), np.zeros(U, np.int64)
+        _ck(lib().ig_balance_rows(self._h, _p(rowptr), _p(nnz), _p(total), C.c_int64(rowptr.size)))
+        out = dict(level="units", rowptr=rowptr, nnz=nnz, total=total, n_entries=int(ne.value))
+        out.update((k, int(v)) for k, v in zip(SCALARS, sc))
+        return out
+
+    def debug_zoom_coarsen(self, rowptr, col, count, coarse_of_unit, n_coarse):
+        """the coarsening over caller CSR data on a bare handle (tests/test_hip_zoom_levels.py) -> dict: rowptr (int64 [n_coarse + 1]),
+        col (int32), count (int64), n_out, forms (as ``debug_assembly_contacts_forms``, of the segments)"""
+        rowptr = np.ascontiguousarray(rowptr, np.int64)
+        col, count = np.ascontiguousarray(col, np.int32), np.ascontiguousarray(count, np.int64)
+        m = np.ascontiguousarray(coarse_of_unit, np.int32)
+        if rowptr.ndim != 1 or rowptr.size < 1 or col.shape != count.shape or col.ndim != 1 or m.shape != (rowptr.size - 1,) or col.size != int(rowptr[-1]):
+            raise HipError("debug_zoom_coarsen: rowptr [U + 1], col and count [rowptr[U]], coarse_of_unit [U]")
+        no, o = C.c_int64(), np.zeros(8, np.int64)
+        _ck(lib().ig_debug_zoom_coarsen(self._h, _p(rowptr), _p(col), _p(count), C.c_int64(rowptr.size - 1), _p(m), C.c_int64(int(n_coarse)), C.byref(no), _p(o)))
+        out = dict(n_out=int(no.value), rowptr=np.zeros(int(n_coarse) + 1, np.int64), col=np.zeros(no.value, np.int32), count=np.zeros(no.value, np.int64),
+                   forms=dict(short=(int(o[0]), int(o[1])), lds=(int(o[2]), int(o[3])), long=(int(o[4]), int(o[5])), runs=int(o[6]), longest=int(o[7])))
+        _ck(lib().ig_debug_zoom_fetch(self._h, _p(out["rowptr"]), C.c_int64(out["rowptr"].size), _p(out["col"]), _p(out["count"]), C.c_int64(out["n_out"])))
+        return out
+
+    def debug_zoom_time(self, n=1, coarse_of_unit=None, n_coarse=None):
+        """the coarsening of the built snapshot (``coarse_of_unit`` None: two units to one) n times with hipEvents around each pass;
+        the snapshot stays -> (ms [n, 6]: ``ZOOM_PASSES``, checksum of the last repeat's result)"""
+        ms = np.zeros((int(n), len(ZOOM_PASSES)), np.float32)
+        ck = C.c_int64()
+        t = None if coarse_of_unit is None else self._unit_table(coarse_of_unit, n_coarse, "debug_zoom_time: coarse map")
+        _ck(lib().ig_debug_zoom_time(self._h, _p(t), C.c_int64(0 if t is None else t.size), C.c_int64(0 if t is None else int(n_coarse)), C.c_int32(int(n)), _p(ms),
+                                     C.byref(ck)))
         return ms, int(ck.value)
 
     # ---- the layers the reports share, over caller data (tests/test_hip_rows_direct.py)

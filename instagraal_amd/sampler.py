@@ -23,6 +23,7 @@ import numpy as np
 
 from . import hip_lib
 from . import optim_rippe_curve_update as opti
+from . import zoom_levels as _zoom_levels
 
 LIST_SIZE = np.array([1, 3, 5, 10, 20, 50, 200, 200], dtype=np.int32)  # CL:417
 N_INSERT_BLOCKS = 6  # CL:192
@@ -1010,6 +1011,141 @@ class sampler:  # noqa: N801 - the reference's class name
             from . import balance as bal
 
             bal.write_weights(os.path.join(folder, "weights.tsv"), table, self.balance(level=level, **(balance if isinstance(balance, dict) else {})))
+        return out
+
+    # ------------------------------------------------------------ zoom levels
+    def _zoom_frame(self, diagonal):
+        """the order, the sub-fragment table of the current genome and the self-contacts by position (or None)"""
+        from . import assembly_contacts as ac
+
+        order = self.ctx.contact_map_order().astype(np.int64)
+        g = self.gpu_vect_frags.copy_from_gpu()
+        table = ac.bins_table(order, self.np_sub_frags_2_frags["x"].astype(np.int64), g.id_c, g.ori, self.S_o_A_sub_frags["len_bp"], "sub")
+        d = None
+        if diagonal and self.sparse_matrix is not None:
+            d = np.asarray(self.sparse_matrix.diagonal()).astype(np.int64)[order]
+        return order, table, d
+
+    @staticmethod
+    def _zoom_units(table_sub, binsize, units):
+        """-> (unit, U, the table of the units or None for a caller's own)"""
+        from . import assembly_contacts as ac, zoom_levels as zl
+
+        if (binsize is None) == (units is None):
+            raise ValueError("zoom levels: give binsize (bp) or units (\"scaffold\", or (unit, n_units)), not both")
+        if binsize is not None:
+            unit, U = zl.units_of_positions(table_sub, binsize)
+            return unit, U, zl.binnify(ac.chrom_sizes(table_sub), binsize)
+        if isinstance(units, str):
+            if units != "scaffold":
+                raise ValueError("zoom levels: units is \"scaffold\" or (unit, n_units) (got %r)" % (units,))
+            unit, U = zl.scaffold_units(table_sub)
+            return unit, U, zl.scaffold_table(table_sub)
+        unit, U = zl.check_units(units[0], units[1], table_sub.size)
+        return unit, U, None
+
+    @staticmethod
+    def _diag_of_units(d, unit, U):
+        if d is None:
+            return None
+        diag = np.zeros(U, np.int64)
+        np.add.at(diag, unit, d)
+        return diag
+
+    def _balance_units(self, unit, n_units, ignore_diags=2, min_nnz=10, min_count=0, mad_max=0, tol=1e-5, max_iters=200):
+        """``balance`` over a caller's units (``ig_balance_build_units``): the dict ``balance`` returns, level "units", without bins"""
+        from . import balance as bal
+
+        d = bal.check_ignore_diags(ignore_diags)
+        tol, max_iters = bal.check_run(tol, max_iters)
+        res = self.ctx.balance_build_units(unit, n_units, d)
+        try:
+            masked = bal.mask_units(res["nnz"], res["total"], min_nnz, min_count, mad_max)
+            res.update(self.ctx.balance_run(np.where(masked, 0.0, 1.0), tol, max_iters))
+        finally:
+            self.ctx.balance_release()
+        res["weight"], res["scale"] = bal.finish(res["b"], res["marg_final"], masked)
+        res.update(masked=masked, ignore_diags=d, min_nnz=int(min_nnz), min_count=int(min_count), mad_max=mad_max, tol=tol, max_iters=max_iters)
+        return res
+
+    def resolution_contacts(self, binsize=None, units=None, diagonal=True, balance=False):
+        """The contacts of the current genome at a fixed resolution (``ig_assembly_contacts_build_units``; the rule:
+        ``zoom_levels.py``): ``binsize`` in bp -- a unit is a fixed bin of that many bp of a scaffold, the last one cut at the
+        scaffold's end, and a sub-fragment counts for the bin that holds its midpoint --, or ``units="scaffold"`` (a unit is a
+        scaffold), or a caller's ``(unit, n_units)`` per position.  -> the dict ``assembly_contacts`` returns, with ``bins`` the table of
+        the fixed bins (contig, start, end; None for a caller's units), ``unit`` per position and ``units_without_position`` -- the
+        fixed bins no midpoint falls into: above 0 the resolution is below what the fragments carry.  ``diagonal`` and ``balance`` as
+        in ``assembly_contacts``.  No reference counterpart on the device (post.py bins the raw pairs on the host)."""
+        from . import assembly_contacts as ac, balance as bal, zoom_levels as zl
+
+        order, table_sub, d = self._zoom_frame(diagonal)
+        unit, U, bins = self._zoom_units(table_sub, binsize, units)
+        res = self.ctx.assembly_contacts_units(unit, U)
+        try:
+            col, count = self.ctx.assembly_contacts_fetch(0, res["n_entries"])
+        finally:
+            self.ctx.assembly_contacts_release()
+        rowptr = res.pop("rowptr")
+        res.pop("n_entries")
+        diag = self._diag_of_units(d, unit, U)
+        if diag is not None:
+            rowptr, col, count = ac.merge_diagonal(0, rowptr, col, count, diag)
+        res.update(rowptr=rowptr, col=col, count=count, order=order, bins=bins, unit=unit, chrom_sizes=ac.chrom_sizes(table_sub),
+                   contacts_diagonal=0 if diag is None else int(diag.sum()), units_without_position=zl.units_without_position(unit, U),
+                   binsize=None if binsize is None else int(binsize))
+        if balance:
+            res["weight"] = self._balance_units(unit, U, **(balance if isinstance(balance, dict) else {}))["weight"]
+            res["balanced"] = bal.balanced(count, ac.rows_of(rowptr), col, res["weight"])
+        return res
+
+    def scaffold_contacts(self, diagonal=True):
+        """the scaffold by scaffold matrix of the current genome: ``resolution_contacts(units="scaffold")``"""
+        return self.resolution_contacts(units="scaffold", diagonal=diagonal)
+
+    def write_zoom_levels(self, folder, resolutions=_zoom_levels.DEFAULT_RESOLUTIONS, scaffolds=True, diagonal=True, balance=False, block_rows=None):
+        """Writes the current genome's contacts at every bin size of ``resolutions`` (ascending, bp; the default:
+        ``zoom_levels.DEFAULT_RESOLUTIONS``) to ``<folder>/resolutions/<bp>/{bins.bed, pixels.tsv, chrom.sizes}`` and (``scaffolds``) the
+        scaffold matrix to ``<folder>/scaffolds/``, each what ``cooler load -f coo`` takes.  ``zoom_levels.plan`` decides how a level is
+        made: built from the contacts, or -- its bin size a multiple of the level before it -- coarsened on the device from that
+        level (``ig_assembly_contacts_coarsen``); the scaffold matrix is coarsened from the last level.  The bytes do not depend on the
+        plan.  ``balance=True`` (or a dict of ``balance()``'s parameters): ``weights.tsv`` per level.  -> a list, per level in order:
+        dict of ``level`` (bp, or "scaffolds"), ``made`` (``("direct",)`` / ``("coarsen", factor)``), ``folder``, the scalars,
+        ``n_units``, ``units_without_position``, ``contacts_diagonal`` and ``pixels_written``."""
+        from . import assembly_contacts as ac, zoom_levels as zl
+
+        import os
+
+        res_list = zl.check_resolutions(resolutions)
+        steps = list(zip(res_list, zl.plan(res_list)))
+        order, table_sub, d = self._zoom_frame(diagonal)
+        sizes = ac.chrom_sizes(table_sub)
+        rows = ac.DEFAULT_BLOCK_ROWS if block_rows is None else block_rows
+        out = []
+        try:
+            for i, (B, made) in enumerate(steps + ([("scaffolds", ("coarsen", "scaffolds"))] if scaffolds else [])):
+                if B == "scaffolds":
+                    (unit, U), bins, where = zl.scaffold_units(table_sub), zl.scaffold_table(table_sub), zl.scaffold_folder(folder)
+                    res = self.ctx.assembly_contacts_coarsen(*zl.scaffold_map(sizes, res_list[-1]))
+                else:
+                    (unit, U), bins, where = zl.units_of_positions(table_sub, B), zl.binnify(sizes, B), zl.level_folder(folder, B)
+                    if made[0] == "direct":
+                        res = self.ctx.assembly_contacts_units(unit, U)
+                    else:
+                        res = self.ctx.assembly_contacts_coarsen(*zl.coarse_map(sizes, res_list[i - 1], made[1]))
+                diag = self._diag_of_units(d, unit, U)
+                n = zl.write_level(where, bins, res["rowptr"], self.ctx.assembly_contacts_fetch, rows, diag)
+                one = {k: res[k] for k in ac.SCALARS}
+                one.update(level=B, made=made, folder=where, units_without_position=zl.units_without_position(unit, U),
+                           contacts_diagonal=0 if diag is None else int(diag.sum()), pixels_written=n)
+                if balance:
+                    from . import balance as bal
+
+                    w = self._balance_units(unit, U, **(balance if isinstance(balance, dict) else {}))
+                    w["level"] = "units"
+                    bal.write_weights(os.path.join(where, "weights.tsv"), bins, w)
+                out.append(one)
+        finally:
+            self.ctx.assembly_contacts_release()
         return out
 
     # ---------------------------------------------------------------- balance

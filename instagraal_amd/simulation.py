@@ -194,7 +194,8 @@ class instagraal_class:
         self.collect_id_fA_sampled.append(id_frag)
 
     def full_em(self, n_cycles, n_neighbours, bomb, id_start_sample_param, save_matrix=False, save_law=False, save_junctions=False,
-                save_contacts=False, save_joins=False, save_residuals=False, save_placements=False, save_orientations=False, save_weights=False, save_gaps=False):  # IG:196-291
+                save_contacts=False, save_joins=False, save_residuals=False, save_placements=False, save_orientations=False, save_weights=False, save_gaps=False,
+                save_resolutions=False):  # IG:196-291
         sampler = self.simulation.sampler
         if bomb:
             sampler.bomb_the_genome()
@@ -248,6 +249,11 @@ class instagraal_class:
                 emap.write_residuals(self._out("residuals_cycle_%d.txt" % j), sampler.strongest_residuals(residuals=res), res)
         if save_contacts:  # (once, behind the last cycle: the table is large)
             sampler.write_assembly_contacts(self._out("assembly_contacts"), level="sub")
+        if save_resolutions:  # (once, behind the last cycle, beside assembly_contacts/: the fixed-resolution maps and the scaffold matrix)
+            from . import zoom_levels as zl
+
+            sampler.write_zoom_levels(self._out("zoom_levels"), zl.DEFAULT_RESOLUTIONS if save_resolutions is True else tuple(save_resolutions),
+                                      balance=bool(save_weights))
         if save_joins:  # (once, behind the last cycle: behind a bomb the table has up to four lines per contact)
             from . import join_support as jsup
 
@@ -287,7 +293,7 @@ class instagraal_class:
 def run_instagraal(hic_folder, reference_fa, output_folder=None, level=4, cycles=100, coverage_std=1, neighborhood=5, device=0,
                    circular=False, bomb=False, pyramid_only=False, save_pickle=False, save_matrix=False, simple=False, save_law=False,
                    save_junctions=False, save_contacts=False, save_joins=False, save_residuals=False, save_placements=False,
-                   save_orientations=False, save_weights=False, save_gaps=False):
+                   save_orientations=False, save_weights=False, save_gaps=False, save_resolutions=False):
     """IG:502-581 (defaults of cli/main.py: level 4, 100 cycles, 5 neighbours, 1 std).  The three trailing switches of the
     reference's signature (IG:512-514) are accepted: ``save_pickle`` dumps the run object to ``graal.pkl`` as the reference
     tries to (IG:589-594: a warning when it cannot be pickled -- device handles here, h5py handles there); ``save_matrix``
@@ -319,7 +325,12 @@ def run_instagraal(hic_folder, reference_fa, output_folder=None, level=4, cycles
     once, behind the last cycle: one line per join -- those between two co-linear blocks of a scaffold first, those between two bins
     behind them -- with the contacts observed across it inside a window of 64 sub-fragments, the pairs, the gap in kb under which the
     model explains them best, its 95 % interval, the two log-likelihood ratios and the verdict "adjacent", "gap" or "apart"
-    (``sampler.gap_support``)."""
+    (``sampler.gap_support``); ``save_resolutions`` (an addition too; True: ``zoom_levels.DEFAULT_RESOLUTIONS``, or a tuple
+    of ascending bin sizes in bp) writes ``zoom_levels/`` once, behind the last cycle, beside ``assembly_contacts/``: per bin size
+    ``resolutions/<bp>/bins.bed``, ``pixels.tsv`` and ``chrom.sizes`` -- the contacts of the final genome in fixed bins of that many bp,
+    a level whose bin size is a multiple of the one before it made from that level alone -- and ``scaffolds/`` with the scaffold by
+    scaffold matrix; given together with ``save_weights``, ``weights.tsv`` of every level beside them (``sampler.write_zoom_levels``,
+    DESIGN 4.21)."""
     import warnings
 
     if simple and not pyramid_only:
@@ -340,7 +351,7 @@ def run_instagraal(hic_folder, reference_fa, output_folder=None, level=4, cycles
         p2.simulation.level.S_o_A_frags["circ"] += 1
     p2.full_em(n_cycles=cycles, n_neighbours=neighborhood, bomb=bomb, id_start_sample_param=4, save_matrix=save_matrix, save_law=save_law,
                save_junctions=save_junctions, save_contacts=save_contacts, save_joins=save_joins, save_residuals=save_residuals, save_placements=save_placements,
-               save_orientations=save_orientations, save_weights=save_weights, save_gaps=save_gaps)
+               save_orientations=save_orientations, save_weights=save_weights, save_gaps=save_gaps, save_resolutions=save_resolutions)
     if save_pickle:  # IG:589-594
         import pickle
 
