@@ -479,6 +479,10 @@ int ig_debug_zero_fallbacks(ig_ctx* ctx, int64_t* fallbacks);
  * lists did not fit the slice pool and were repeated with a larger one -- the counterpart of the batch path's re-run slots
  * (replaces nothing in the reference: its sort buffers are sized for the whole matrix, CL:1009-1069) */
 int ig_debug_pool_retries(ig_ctx* ctx, int64_t* n);
+/* tests: the bytes the per-window arrays of THIS handle's move buffers may take (default 64e9; bytes <= 0: the default again).  The
+ * arrays are released and sized again under the new budget at the strides the present contig lengths ask for; *slots (may be NULL): the
+ * move slots they hold now, 0 before any move buffers exist.  Every launch is capped by the slots held, so results do not depend on it. */
+int ig_debug_window_budget(ig_ctx* ctx, double bytes, int32_t* slots);
 int ig_debug_step_stats(ig_ctx* ctx, int64_t out2[2]); /* ig_step_draw: {calls that went through mapped memory, of them finished by the one-move tail} */
 int ig_debug_nuis_chain_stats(ig_ctx* ctx, int64_t out10[10]); /* chains: {calls, segments, pairs completed, ends by reason [7]} */
 int ig_debug_set_full_hist(int on); /* from-scratch pass: all-trans tiles from their count histograms (1, default) or contact by contact (0) */

@@ -56,6 +56,12 @@ static int exact_grid_floor(const ig_ctx* c, int max_c)
     return std::min(c->mb.work_cap, std::max(4096, 2 * std::max(max_c, 1) * NSLOT * std::max(c->mb.nseg, 8) + 2048));
 }
 
+/* the exact kernel's next grid from the work items the batch just decided needed (bo[6]); asked at the first commit of a scored piece */
+static void size_exact_grid(ig_ctx* c, const int bo[16])
+{
+    c->exact_grid = std::min(c->mb.work_cap, std::max(exact_grid_floor(c, c->up_max_c), (int)(1.25 * bo[6]) + 2048));
+}
+
 /* one-move calls: the bound on the longest contig comes back with the result (the window strides follow it) */
 static int queue_max_readback(ig_ctx* c)
 {
@@ -144,9 +150,11 @@ __global__ void __launch_bounds__(256) k_rescore_prepare(Glob* g, MoveBuf mb, Pz
  * done by this call (default: all of [w_begin, w_end)); par_only: nothing but that half, on slots gathered, mutated and
  * sliced by an earlier call (the runs of (move, nuisance step) pairs: the structural half of a batch survives an accepted
  * step, and is scored in pieces that follow the run lengths) */
-static void enqueue_score(ig_ctx* c, int move0, int W, int max_c, int force_slot, int phase, int w_begin = 0, int w_end = -1, int par_begin = -1,
-                          int par_end = -1, bool par_only = false)
+static int enqueue_score(ig_ctx* c, int move0, int W, int max_c, int force_slot, int phase, int w_begin = 0, int w_end = -1, int par_begin = -1,
+                         int par_end = -1, bool par_only = false)
 {
+    /* the chokepoint of the slot budget: a width that did not come from the call that ensured the buffers is a host error, before any kernel */
+    if (W > slots_held(c)) return fail("enqueue_score: a launch of %d slots, the window buffers hold %d (ensure_window_slots gives a launch its cap)", W, slots_held(c));
     /* slots [w_begin, w_end) are sliced and scored here (multi-GPU: the other ranks score the rest and the slot-major
      * records are all-gathered); the candidate genomes of EVERY slot are built on every rank, the commit step needs them */
     if (w_end < 0) w_end = W;
@@ -266,7 +274,7 @@ static void enqueue_score(ig_ctx* c, int move0, int W, int max_c, int force_slot
                 if (s_probe >= 0) {
                     const size_t C = (size_t)c->mb.capC * c->mb.capW;
                     if (!c->probe_scr) {
-                        if (dalloc(&c->probe_scr, C * NSLOT) || dalloc(&c->probe_void, 2 * C)) return;
+                        if (dalloc(&c->probe_scr, C * NSLOT) || dalloc(&c->probe_void, 2 * C)) return -1;
                     }
                     hipMemsetAsync(c->probe_scr, 0, C * NSLOT * sizeof(ScreenSum), c->stream);
                     hipMemsetAsync(c->probe_void, 0, 2 * C * sizeof(unsigned), c->stream);
@@ -361,6 +369,7 @@ static void enqueue_score(ig_ctx* c, int move0, int W, int max_c, int force_slot
             }
         }
     }
+    return 0;
 }
 
 /* scores + argmax of slot w (or the forced choice of ig_apply) */
@@ -408,10 +417,11 @@ static void enqueue_apply(ig_ctx* c, int move, int w, int forced, bool log_dirty
     }
 }
 
-static void enqueue_move(ig_ctx* c, int move, int max_c, int force_slot, int phase)
+static int enqueue_move(ig_ctx* c, int move, int max_c, int force_slot, int phase)
 {
-    enqueue_score(c, move, 1, max_c, force_slot, phase);
+    if (enqueue_score(c, move, 1, max_c, force_slot, phase)) return -1;
     if (phase == 1 || phase == 2) enqueue_choose(c, 0, force_slot);
+    return 0;
 }
 
 static int validate_move(ig_ctx* c, int frag_a, const int32_t* cands, int C)
@@ -428,25 +438,33 @@ static int validate_move(ig_ctx* c, int frag_a, const int32_t* cands, int C)
 
 static int g_zero_inject = 0; /* ig_debug_set_zero_inject: the decide step treats every n-th move of a two-tier batch as one with a score of exactly 0.0 */
 
+/* contender-only records (two-tier scoring): the decide step checks for scores of exactly 0.0 (decide_body, stop code 3) */
+static int decide_zcheck(const ig_ctx* c) { return (c->own_screened == 1 ? 1 : 0) | (std::max(g_zero_inject, 0) << 8); }
+
+/* decide and apply in ONE launch (k_decide_commit: seven waves work behind the decide wave)?  0: no, 1: where that pays, 2: IG_FUSED_COMMIT=2
+ * says always (and keeps decide_body's one wave: the tests compare all three; =0: never).  It pays for plain batches of moves on windows that
+ * 448 threads apply as fast as k_commit_batch's 1 024 -- not for a run's one-move launches (their host waits for the record, which the
+ * fused kernel writes behind a longer prologue: 10.2 k instead of 10.7 k; ig_step_draw publishes from the fused kernel: one launch less on
+ * the call's critical path), not for the late shapes (bigctg: 5.7 k instead of 5.9 k).  launch_commit and the chains' driver ask here. */
+static int fuse_commit(const ig_ctx* c, bool publish)
+{
+    static const int s_fused = getenv("IG_FUSED_COMMIT") ? atoi(getenv("IG_FUSED_COMMIT")) : 1;
+    return s_fused >= 2 ? 2 : ((s_fused == 1 && (!publish || c->pub_step) && c->max_SL <= 4096) ? 1 : 0);
+}
+
 /* commit the scored batch [move0, move0 + w_now): k_commit_batch, the one-move tail for a windowed winner, resume */
-/* the decide + apply launches of the slots [next, w_now) of the batch at move `done` */
+/* the decide + apply launches of the slots [next, w_now) of the batch at move `done`; fused (fuse_commit) unless this is a rank's share of a
+ * batch (the winners of the other ranks are mutated in between) */
 static void launch_commit(ig_ctx* c, int done, int w_now, int next, int resumed_plain, bool publish = false)
 {
     nh_untracked_move(c);
     flush_pending_sums(c);
     TimedLaunch t(c, T_COMMIT);
-    static const int s_fused = getenv("IG_FUSED_COMMIT") ? atoi(getenv("IG_FUSED_COMMIT")) : 1;
-    /* one launch where that pays (k_decide_commit: seven waves work behind the decide wave): plain batches of moves on windows that
-     * 448 threads apply as fast as k_commit_batch's 1 024 -- not a run's one-move launches (their host waits for the record, which the
-     * fused kernel writes behind a longer prologue: 10.2 k instead of 10.7 k), not the late shapes (bigctg: 5.7 k instead of 5.9 k),
-     * not a rank's share of a batch (the winners of the other ranks are mutated in between).  IG_FUSED_COMMIT=0 / 2: never / always. */
-    const bool fuse = s_fused >= 2 || (s_fused == 1 && (!publish || c->pub_step) && c->max_SL <= 4096); /* (ig_step_draw publishes from the fused kernel: one launch less on the call's critical path) */
-    /* contender-only records (two-tier scoring): the decide step checks for scores of exactly 0.0 (decide_body, stop code 3) */
-    const int zcheck = (c->own_screened == 1 ? 1 : 0) | (std::max(g_zero_inject, 0) << 8);
+    const int fuse = fuse_commit(c, publish), zcheck = decide_zcheck(c);
     /* the decisions in rounds of DPAR moves side by side (decide_rounds, round 6) where the launch is a plain chain: moves of at most five
      * candidates (two score records per lane), nothing published to the host from inside the kernel (ig_step_draw's scores and record), at
      * least a round's worth of decisions.  IG_FUSED_COMMIT=2 keeps decide_body's one wave (the tests compare all three) */
-    if (fuse && s_fused == 1 && !publish && !c->pub_scores && c->up_max_c <= 5 && w_now - next >= DPAR && !(c->own_begin > 0 || c->own_end < w_now)) {
+    if (fuse == 1 && !publish && !c->pub_scores && c->up_max_c <= 5 && w_now - next >= DPAR && !(c->own_begin > 0 || c->own_end < w_now)) {
         const int seq = ++c->bo_seq;
         hipLaunchKernelGGL(k_decide_commit_par, dim3(1), dim3(DPAR * 64 + DPAR_CW * 64), 0, c->stream, c->glob, c->mb, c->d_results, done, w_now, next,
                            c->dirty_buf, c->batch_out, (volatile int*)c->host_bo_dev, seq, resumed_plain, c->st, c->tab, c->tab_prev, c->init_prev,
@@ -527,7 +545,7 @@ static int commit_loop(ig_ctx* c, int done, int w_now, int* next_out, bool publi
             return 0;
         }
         if (c->own_screened == 1 && next == 0) /* first commit of this batch: size the exact kernel's next grid */
-            c->exact_grid = std::min(c->mb.work_cap, std::max(exact_grid_floor(c, c->up_max_c), (int)(1.25 * bo[6]) + 2048));
+            size_exact_grid(c, bo);
         next = bo[0];
         if (bo[1] >= 0) { /* slot bo[1] chose a windowed winner: delta + apply with the one-move kernels, then go on */
             enqueue_apply(c, done + bo[1], bo[1], 0);
@@ -549,13 +567,20 @@ static int commit_loop(ig_ctx* c, int done, int w_now, int* next_out, bool publi
 
 static int g_batch_w = -1; /* moves scored per launch in ig_step_batch: env IG_BATCH_W, default 24; 1 = one move at a time */
 
-/* the per-slot window buffers (strides: three times the longest contig, at most the genome): keep them under ~64 GB */
+/* the widest batch of moves of max_c candidates: what the slot budget holds at the strides the present contig lengths ask for (three times
+ * the longest contig, at most the genome: what ensure_window_buffers allocates when it has to) */
 static int max_batch_width(ig_ctx* c, int max_c)
 {
     const double sN = std::min<double>(c->N, std::max(256.0, 3.0 * c->max_L)), sM = std::min<double>(c->M, std::max(768.0, 3.0 * c->max_SL));
-    const double per_slot = window_bytes_per_slot(max_c, sN, sM);
-    const int fit = (int)std::max(1.0, 64e9 / std::max(per_slot, 1.0));
-    return std::min(fit, IG_MAX_BATCH);
+    return std::min(slots_in_budget(c, std::max(max_c, c->mb.capC), sN, sM), IG_MAX_BATCH);
+}
+/* ... as ig_batch_max_width / ig_batch_upload promise it to a caller that sizes its own launches: no more than the buffers in place hold
+ * where they hold fewer slots than they were asked for (strides never shrink; ig_debug_window_budget) -- the next ensure_window_slots gives
+ * these or the ones above, so ig_batch_score does not refuse a width promised here */
+static int promised_width(ig_ctx* c, int max_c)
+{
+    const int fit = max_batch_width(c, max_c), held = slots_held(c);
+    return (held > 0 && held < c->mb.capW) ? std::min(fit, held) : fit;
 }
 
 static int batch_width(ig_ctx* c, int max_c)
@@ -568,7 +593,7 @@ static int batch_width(ig_ctx* c, int max_c)
     return std::min(g_batch_w, max_batch_width(c, max_c));
 }
 
-extern "C" int ig_batch_max_width(ig_ctx* c, int32_t max_c) { IG_JOIN(c); return max_batch_width(c, max_c); }
+extern "C" int ig_batch_max_width(ig_ctx* c, int32_t max_c) { IG_JOIN(c); return promised_width(c, max_c); }
 
 /* validate and upload the pre-drawn (fragment, candidates) lists of a run of moves */
 static int upload_moves(ig_ctx* c, int n_moves, const int32_t* frags, const int32_t* cands, int max_c)
@@ -628,6 +653,48 @@ static int retry_with_larger_pool(ig_ctx* c)
     return 0;
 }
 
+/* one move per launch sequence until its lists fit the slice pool: attempt() enqueues the move and what reads its outcome back, waits for
+ * it and answers 1: it fitted, 0: it did not (a larger pool, again), -1: an error */
+template <class Attempt>
+static int until_it_fits(ig_ctx* c, Attempt attempt)
+{
+    for (;;) {
+        const int fit = attempt();
+        if (fit) return fit < 0 ? -1 : 0;
+        if (retry_with_larger_pool(c)) return -1;
+    }
+}
+
+/* ---- the driver's shared pieces (DESIGN 4.1): what the loops below, ig_batch_commit, ig_step_draw and the runs of ig_host_nuis.inc say once */
+/* a launch's FIRST slot was refused (commit_loop: *next_out = -code; the runs: bo[2]) and nothing was committed -- room for it, then the
+ * caller scores the same launch again: 1 the slice pool is grown, 2 the exact kernel's grid is made four times larger, 3 a score of exactly
+ * 0.0: nothing to do, wait_commit has set exact_next and the next scoring leaves the screening tier out.  `who`: what did not fit. */
+static int make_room(ig_ctx* c, int code, const char* who)
+{
+    if (code == 1) return grow_slice_pool(c);
+    if (code == 3) return 0;
+    if (c->exact_grid >= c->mb.work_cap) return fail("the exact kernel's work list cannot hold %s", who);
+    c->exact_grid = std::min(c->mb.work_cap, c->exact_grid * 4);
+    return 0;
+}
+/* a launch that committed `next` of its w_now slots was cut short by the slice pool, not by a conflict: twice the room for the launches to
+ * come (the pool starts at 2 Z entries; small problems with long contigs need more than that for 24 slots).  1: so it was, 0: no, -1: error */
+static int pool_cut_short(ig_ctx* c, int next, int w_now)
+{
+    if (!(next < w_now && c->last_stop == 1 && (size_t)c->mb.pool_cap < slice_pool_max(c))) return 0;
+    HIPCK(hipStreamSynchronize(c->stream));
+    return alloc_slice_pool(c, std::min(slice_pool_max(c), (size_t)c->mb.pool_cap * 2)) ? -1 : 1;
+}
+/* The width follows the conflict rate: where few contigs are left (late in an assembly) nearly every move touches a contig an earlier
+ * move of the batch modified, and slots scored behind the first conflict are wasted work.  w_ema: moving average of the moves a launch
+ * got through (one that got through all of them counts double: the run was at least that long); the next launch is 1.5 x that, at
+ * most Wmax.  Results do not depend on the widths. */
+static int next_width(const ig_ctx* c, int Wmax) { return std::max(Wmax > 1 ? 2 : 1, std::min(Wmax, (int)(1.5 * c->w_ema + 1.5))); }
+static void feed_width(ig_ctx* c, int next, int w_now, int Wmax)
+{
+    c->w_ema = 0.6 * c->w_ema + 0.4 * (next >= w_now ? std::min(2.0 * w_now, (double)Wmax) : (double)next);
+}
+
 /* the moves [0, n_moves) of the uploaded lists: speculative batches of up to Wmax moves (Wmax == 1: one move per launch
  * sequence).  `ready(first, count)` is called before moves [first, first + count) are enqueued: the fused draw + step entry
  * point waits there for its drawing thread and uploads the candidate lists drawn so far. */
@@ -637,54 +704,39 @@ static int run_moves(ig_ctx* c, int n_moves, int max_c, int Wmax, Ready ready)
     if (Wmax == 1) {
         for (int i = 0; i < n_moves; i++) {
             if (ready(i, 1)) return -1;
-            for (;;) { /* (one move per launch sequence is the slow way on purpose: the outcome is read per move -- a move whose lists
-                        * did not fit the slice pool is repeated with a larger one before the next move builds on it) */
+            /* (one move per launch sequence is the slow way on purpose: the outcome is read per move -- a move whose lists
+             * did not fit the slice pool is repeated with a larger one before the next move builds on it) */
+            const int rc = until_it_fits(c, [&]() -> int {
                 ig_move_result r;
-                enqueue_move(c, i, max_c, -1, 2);
+                if (enqueue_move(c, i, max_c, -1, 2)) return -1;
                 enqueue_apply(c, i, 0, 0);
                 HIPCK(hipMemcpyAsync(&r, c->d_results + i, sizeof r, hipMemcpyDeviceToHost, c->stream));
                 HIPCK(hipStreamSynchronize(c->stream));
-                if (r.pad != 1) break;
-                if (retry_with_larger_pool(c)) return -1;
-            }
+                return r.pad != 1;
+            });
+            if (rc) return -1;
         }
         return 0;
     }
     /* speculative batches: score W moves against the same state, commit the conflict-free prefix on the device,
      * finish a winner that needs the exact delta pass with the one-move tail, continue after it */
-    /* The width follows the conflict rate: where few contigs are left (late in an assembly) nearly every move touches a
-     * contig an earlier move of the batch modified, and slots scored behind the first conflict are wasted work.  Moving
-     * average of the moves a batch got through (a batch that got through all of them counts double: the run was at
-     * least that long); the next batch is 1.5 x that, at most Wmax.  Results do not depend on the widths. */
     if (c->w_ema <= 0.0 || c->w_ema > Wmax) c->w_ema = Wmax;
     int done = 0;
     while (done < n_moves) {
-        if (ensure_window_buffers(c)) return -1; /* the longest contig may have grown (fewer slots may fit behind that: window_slots) */
-        Wmax = std::min(Wmax, window_slots(c));
-        const int w_want = std::max(Wmax > 1 ? 2 : 1, std::min(Wmax, (int)(1.5 * c->w_ema + 1.5)));
-        const int w_now = std::min(w_want, n_moves - done);
-        if (ready(done, w_now)) return -1;
-        enqueue_score(c, done, w_now, max_c, -1, 2);
+        const int held = ensure_window_slots(c); /* the longest contig may have grown, and fewer slots may fit behind that */
+        if (held < 0) return -1;
+        Wmax = std::min(Wmax, held);
+        const int w_want = next_width(c, Wmax), w_now = std::min(w_want, n_moves - done);
+        if (ready(done, w_now) || enqueue_score(c, done, w_now, max_c, -1, 2)) return -1;
         int next = 0;
         if (commit_loop(c, done, w_now, &next)) return -1;
         if (next < 0) { /* the first slot did not fit: more room, the same batch again (nothing was committed) */
-            if (next == -1) {
-                if (grow_slice_pool(c)) return -1;
-            } else if (next == -3) { /* (wait_commit has set exact_next: the same batch again without the screening tier) */
-            } else {
-                if (c->exact_grid >= c->mb.work_cap) return fail("the exact kernel's work list cannot hold the first move of a batch");
-                c->exact_grid = std::min(c->mb.work_cap, c->exact_grid * 4);
-            }
+            if (make_room(c, -next, "the first move of a batch")) return -1;
             continue;
         }
-        if (next < w_now && c->last_stop == 1 && (size_t)c->mb.pool_cap < slice_pool_max(c)) {
-            /* cut short by the slice pool, not by a conflict: twice the room for the batches to come (the pool starts at 2 Z
-             * entries; small problems with long contigs need more than that for 24 slots) */
-            HIPCK(hipStreamSynchronize(c->stream));
-            if (alloc_slice_pool(c, std::min(slice_pool_max(c), (size_t)c->mb.pool_cap * 2))) return -1;
-        } else if (w_now == w_want) { /* a batch cut short by the end of the run says nothing */
-            c->w_ema = 0.6 * c->w_ema + 0.4 * (next >= w_now ? std::min(2.0 * w_now, (double)Wmax) : (double)next);
-        }
+        const int cut = pool_cut_short(c, next, w_now);
+        if (cut < 0) return -1;
+        if (!cut && w_now == w_want) feed_width(c, next, w_now, Wmax); /* (a batch cut short by the end of the run says nothing) */
         done += next;
     }
     return 0;
@@ -730,8 +782,10 @@ static int window_ring(ig_ctx* c, int max_c)
 template <class Ready>
 static int run_moves_window(ig_ctx* c, int n_moves, int max_c, int Wmax, Ready ready)
 {
-    int ring = 1; /* physical slots in use: a power of two, as many as the buffers hold (ensure_move_buffers: window_ring at the call's start) */
-    while (2 * ring <= std::min(IG_MAX_BATCH, window_slots(c))) ring *= 2;
+    int held = ensure_window_slots(c);
+    if (held < 0) return -1;
+    int ring = 1; /* physical slots in use: a power of two, as many as the buffers hold (plan_call: window_ring at the call's start) */
+    while (2 * ring <= std::min(IG_MAX_BATCH, held)) ring *= 2;
     Wmax = std::min(Wmax, ring);
     struct Restore { /* the other entry points index the slots directly */
         ig_ctx* c;
@@ -749,16 +803,15 @@ static int run_moves_window(ig_ctx* c, int n_moves, int max_c, int Wmax, Ready r
     unsigned long long stale = 0ull; /* bit p: the slot of move done + p has to be scored again */
     while (done < n_moves) {
         const int sN_before = c->mb.sN, sM_before = c->mb.sM;
-        if (ensure_window_buffers(c)) return -1; /* the longest contig may have grown: new strides, nothing in the buffers survives */
+        if ((held = ensure_window_slots(c)) < 0) return -1; /* the longest contig may have grown: new strides, nothing in the buffers survives */
         /* (the strides, not the pointers: the allocator may hand the freed block out again) */
         const bool regrown = c->mb.sN != sN_before || c->mb.sM != sM_before;
         if (regrown) { /* ... and fewer slots may fit at the new strides: a smaller ring (everything is dropped anyway) */
-            while (ring > 1 && ring > window_slots(c)) ring /= 2;
+            while (ring > 1 && ring > held) ring /= 2;
             Wmax = std::min(Wmax, ring);
             if (c->w_ema > Wmax) c->w_ema = Wmax;
         }
-        const int w_want = std::max(Wmax > 1 ? 2 : 1, std::min(Wmax, (int)(1.5 * c->w_ema + 1.5)));
-        const int w_now = std::min(w_want, n_moves - done);
+        const int w_want = next_width(c, Wmax), w_now = std::min(w_want, n_moves - done);
         if (ready(done, w_now)) return -1;
         if (regrown || c->exact_next) scored_upto = done;
         const int n_have = std::min(std::max(scored_upto - done, 0), w_now);
@@ -778,28 +831,19 @@ static int run_moves_window(ig_ctx* c, int n_moves, int max_c, int Wmax, Ready r
             c->mb.ring = 1 | (s_chk ? 4 : 0);
         }
         c->n_window_slots += w_now - __builtin_popcountll(keep);
-        enqueue_score(c, done, w_now, max_c, -1, 2);
+        if (enqueue_score(c, done, w_now, max_c, -1, 2)) return -1;
         scored_upto = std::max(scored_upto, done + w_now);
         int next = 0;
         if (commit_loop(c, done, w_now, &next)) return -1;
         if (next < 0) { /* the first slot did not fit: more room, the same window again, every slot of it (nothing was committed) */
-            if (next == -1) {
-                if (grow_slice_pool(c)) return -1;
-            } else if (next == -3) { /* (wait_commit has set exact_next: the window again without the screening tier) */
-            } else {
-                if (c->exact_grid >= c->mb.work_cap) return fail("the exact kernel's work list cannot hold the first move of a batch");
-                c->exact_grid = std::min(c->mb.work_cap, c->exact_grid * 4);
-            }
+            if (make_room(c, -next, "the first move of a batch")) return -1;
             scored_upto = done;
             stale = 0ull;
             continue;
         }
-        if (next < w_now && c->last_stop == 1 && (size_t)c->mb.pool_cap < slice_pool_max(c)) {
-            HIPCK(hipStreamSynchronize(c->stream)); /* cut short by the slice pool: twice the room for the launches to come */
-            if (alloc_slice_pool(c, std::min(slice_pool_max(c), (size_t)c->mb.pool_cap * 2))) return -1;
-        } else if (w_now == w_want) {
-            c->w_ema = 0.6 * c->w_ema + 0.4 * (next >= w_now ? std::min(2.0 * w_now, (double)Wmax) : (double)next);
-        }
+        const int cut = pool_cut_short(c, next, w_now);
+        if (cut < 0) return -1;
+        if (!cut && w_now == w_want) feed_width(c, next, w_now, Wmax);
         /* what the decide step found stale among the positions it did not commit (c->last_stale: position p of THIS window), seen from
          * the next window's front */
         stale = next >= 64 ? 0ull : (c->last_stale >> next);
@@ -808,6 +852,17 @@ static int run_moves_window(ig_ctx* c, int n_moves, int max_c, int Wmax, Ready r
         done += next;
     }
     return 0;
+}
+
+/* how a call of n_moves is run: *Wmax moves per batch (1: the initial links are not mutually inverse), *Wwin > 1: under the window rule, with
+ * a window of that many slots; the move buffers for it */
+static int plan_call(ig_ctx* c, int n_moves, int max_c, int* Wmax, int* Wwin)
+{
+    *Wmax = c->init_links_inverse ? batch_width(c, max_c) : 1;
+    const int ring = window_ring(c, max_c);
+    *Wwin = (*Wmax > 1 && window_width() > 1) ? std::min(window_width(), ring) : 0;
+    c->full_windows = (*Wmax == 1 && n_moves > 1); /* moves enqueued one behind the other: no host round trip to follow the contig lengths */
+    return ensure_move_buffers(c, std::max(8, max_c), *Wwin > 1 ? ring : *Wmax);
 }
 
 extern "C" int ig_step_batch(ig_ctx* c, int32_t n_moves, const int32_t* frags, const int32_t* cands, int32_t max_c,
@@ -819,14 +874,10 @@ extern "C" int ig_step_batch(ig_ctx* c, int32_t n_moves, const int32_t* frags, c
     if (n_moves <= 0) return 0;
     if (max_c < 1 || max_c > IG_MAX_CANDIDATES) return fail("ig_step_batch: max_c out of range");
     if (c->world > 1) return fail("ig_step_batch: this handle scores a contact shard (ig_set_shard %d/%d): use ig_step_begin / all-reduce / ig_step_finish", c->rank, c->world);
-    int Wmax = c->init_links_inverse ? batch_width(c, max_c) : 1;
-    const int Wwin = (Wmax > 1 && window_width() > 1) ? std::min(window_width(), window_ring(c, max_c)) : 0;
-    c->full_windows = (Wmax == 1 && n_moves > 1); /* moves enqueued one behind the other: no host round trip to follow the contig lengths */
-    if (ensure_move_buffers(c, std::max(8, (int)max_c), Wwin > 1 ? window_ring(c, max_c) : Wmax)) return -1;
-    if (upload_moves(c, n_moves, frags, cands, max_c)) return -1;
-    if (Wwin > 1) {
-        if (run_moves_window(c, n_moves, max_c, Wwin, [](int, int) { return 0; })) return -1;
-    } else if (run_moves(c, n_moves, max_c, Wmax, [](int, int) { return 0; })) return -1;
+    int Wmax, Wwin;
+    if (plan_call(c, n_moves, max_c, &Wmax, &Wwin) || upload_moves(c, n_moves, frags, cands, max_c)) return -1;
+    auto ready_fn = [](int, int) { return 0; };
+    if (Wwin > 1 ? run_moves_window(c, n_moves, max_c, Wwin, ready_fn) : run_moves(c, n_moves, max_c, Wmax, ready_fn)) return -1;
     return download_results(c, n_moves, results);
 }
 
@@ -848,11 +899,8 @@ extern "C" int ig_step_batch_draw(ig_ctx* c, ig_neighbours* nb, uint32_t* mt_key
     if (c->world > 1) return fail("ig_step_batch_draw: this handle scores a contact shard (ig_set_shard %d/%d)", c->rank, c->world);
     for (int i = 0; i < n_moves; i++)
         if (frags[i] < 0 || frags[i] >= c->N) return fail("fragment %d out of range", frags[i]);
-    const int Wmax = c->init_links_inverse ? batch_width(c, max_c) : 1;
-    const int Wwin = (Wmax > 1 && window_width() > 1) ? std::min(window_width(), window_ring(c, max_c)) : 0;
-    c->full_windows = (Wmax == 1 && n_moves > 1);
-    if (ensure_move_buffers(c, std::max(8, (int)max_c), Wwin > 1 ? window_ring(c, max_c) : Wmax)) return -1;
-    if (ensure_io(c, n_moves, max_c)) return -1;
+    int Wmax, Wwin;
+    if (plan_call(c, n_moves, max_c, &Wmax, &Wwin) || ensure_io(c, n_moves, max_c)) return -1;
     /* the lists go to the device from pinned staging (layout of h_stage: result records, fragments, candidates) */
     int* st_frags = nullptr;
     int* st_cands = nullptr;
@@ -906,8 +954,7 @@ extern "C" int ig_step_batch_draw(ig_ctx* c, ig_neighbours* nb, uint32_t* mt_key
         return 0;
     };
     const int rc = Wwin > 1 ? run_moves_window(c, n_moves, max_c, Wwin, ready_fn) : run_moves(c, n_moves, max_c, Wmax, ready_fn);
-    if (drawer.joinable())
-    drawer.join(); /* the generator state the caller puts back is the one after ALL draws, also on an error */
+    if (drawer.joinable()) drawer.join(); /* the generator state the caller puts back is the one after ALL draws, also on an error */
     if (rc) return -1;
     if (draw_rc.load()) return fail("candidate draw failed");
     return download_results(c, n_moves, results);
@@ -921,8 +968,8 @@ extern "C" int ig_batch_upload(ig_ctx* c, int32_t n_moves, const int32_t* frags,
     HIPCK(hipSetDevice(c->device));
     if (check_ready(c)) return -1;
     if (n_moves <= 0) return fail("ig_batch_upload: no moves");
-    if (max_w < 1 || max_w > max_batch_width(c, max_c))
-        return fail("ig_batch_upload: batch width %d out of 1..%d (ig_batch_max_width)", max_w, max_batch_width(c, max_c));
+    if (max_w < 1 || max_w > promised_width(c, max_c))
+        return fail("ig_batch_upload: batch width %d out of 1..%d (ig_batch_max_width)", max_w, promised_width(c, max_c));
     if (c->world > 1) return fail("ig_batch_upload: contact shards (ig_set_shard) and slot splitting are exclusive");
     /* k_commit_batch counts every genome-distance credit exactly once by a rule on mutually inverse initial links -- also for a
      * batch of one move */
@@ -938,9 +985,10 @@ extern "C" int ig_batch_score(ig_ctx* c, int32_t move0, int32_t W, int32_t slot_
     HIPCK(hipSetDevice(c->device));
     if (W < 1 || W > c->mb.capW || move0 < 0 || move0 + W > c->up_moves) return fail("ig_batch_score: batch out of range");
     if (slot_begin < 0 || slot_end > W || slot_begin > slot_end) return fail("ig_batch_score: slot range out of range");
-    if (ensure_window_buffers(c)) return -1; /* the longest contig may have grown */
-    if (W > window_slots(c)) return fail("ig_batch_score: the window buffers hold %d slots at the present contig lengths (ig_batch_max_width)", window_slots(c));
-    enqueue_score(c, move0, W, c->up_max_c, -1, 2, slot_begin, slot_end);
+    const int held = ensure_window_slots(c); /* the longest contig may have grown */
+    if (held < 0) return -1;
+    if (W > held) return fail("ig_batch_score: the window buffers hold %d slots at the present contig lengths (ig_batch_max_width)", held);
+    if (enqueue_score(c, move0, W, c->up_max_c, -1, 2, slot_begin, slot_end)) return -1;
     HIPCK(hipGetLastError());
     return 0;
 }
@@ -961,18 +1009,11 @@ extern "C" int ig_batch_commit(ig_ctx* c, int32_t move0, int32_t W, int32_t* n_c
     if (W < 1 || W > c->mb.capW || move0 < 0 || move0 + W > c->up_moves) return fail("ig_batch_commit: batch out of range");
     int next = 0;
     if (commit_loop(c, move0, W, &next)) return -1;
-    if (next < 0) { /* the first slot did not fit the slice pool / the exact kernel's grid: more room, the caller scores the batch again */
-        if (next == -1) {
-            if (grow_slice_pool(c)) return -1;
-        } else if (next == -3) { /* (the next ig_batch_score is exact in every column: exact_next) */
-        } else {
-            if (c->exact_grid >= c->mb.work_cap) return fail("the exact kernel's work list cannot hold the first move of a batch");
-            c->exact_grid = std::min(c->mb.work_cap, c->exact_grid * 4);
-        }
+    if (next < 0) { /* the first slot did not fit: more room, the caller scores the batch again */
+        if (make_room(c, -next, "the first move of a batch")) return -1;
         next = 0;
-    } else if (next < W && c->last_stop == 1 && (size_t)c->mb.pool_cap < slice_pool_max(c)) { /* cut short by the slice pool: more room for the batches to come */
-        HIPCK(hipStreamSynchronize(c->stream));
-        if (alloc_slice_pool(c, std::min(slice_pool_max(c), (size_t)c->mb.pool_cap * 2))) return -1;
+    } else if (pool_cut_short(c, next, W) < 0) {
+        return -1;
     }
     *n_committed = next;
     return 0;
@@ -998,7 +1039,7 @@ extern "C" int ig_scratch_bytes(ig_ctx* c, int64_t out3[3])
     IG_JOIN(c);
     const MoveBuf& m = c->mb;
     const int64_t C = (int64_t)m.capC * m.capW;
-    out3[0] = C * ((int64_t)m.sN * 4 * 3 + (int64_t)m.sM * 4 * 2 + (int64_t)m.sM * NSLOT * 8 + (int64_t)NSLOT * NDYN * m.sN * 4);
+    out3[0] = (int64_t)m.capC * slots_held(c) * ((int64_t)m.sN * 4 * 3 + (int64_t)m.sM * 4 * 2 + (int64_t)m.sM * NSLOT * 8 + (int64_t)NSLOT * NDYN * m.sN * 4);
     out3[1] = m.pool_cap * (m.packed ? 8 : 12);
     out3[2] = C * (int64_t)(SLICE_SEG * 16 + sizeof(CandMeta) + NSLOT * NCODE * sizeof(ColMeta) + (P_STRIDE + Q_STRIDE) * 8 + IG_N_TMP_STRUCT * 8 +
                             NSLOT * 8 + NSLOT * 16 + 16) +
@@ -1029,6 +1070,23 @@ extern "C" int ig_slice_walk_stats(ig_ctx* c, int64_t out2[2])
     return 0;
 }
 
+/* the one-move entry points: the move's lists -> d_frags[0], d_cands[0 .. C) ... */
+static int upload_one_move(ig_ctx* c, const int* frag, const int* cands, int C)
+{
+    HIPCK(hipMemcpyAsync(c->d_frags, frag, sizeof(int), hipMemcpyHostToDevice, c->stream));
+    HIPCK(hipMemcpyAsync(c->d_cands, cands, (size_t)C * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    return 0;
+}
+/* ... and the end of a call that applied its move and has synchronised: launch errors, timers, the bound on the longest contig, the record's verdict */
+static int finish_one_move(ig_ctx* c, int error)
+{
+    HIPCK(hipGetLastError());
+    drain_timers(c);
+    take_max_readback(c);
+    if (error) return fail("device-side consistency failure %d", error);
+    return 0;
+}
+
 extern "C" int ig_step(ig_ctx* c, int32_t frag_a, const int32_t* cands, int32_t C, ig_move_result* out, double* scores)
 {
     IG_JOIN(c);
@@ -1048,28 +1106,23 @@ extern "C" int ig_step(ig_ctx* c, int32_t frag_a, const int32_t* cands, int32_t 
         s_in[0] = frag_a;
         for (int i = 0; i < C; i++) s_in[1 + i] = cands[i];
     }
-    HIPCK(hipMemcpyAsync(c->d_frags, s_in ? (const void*)s_in : (const void*)&frag_a, sizeof(int), hipMemcpyHostToDevice, c->stream));
-    HIPCK(hipMemcpyAsync(c->d_cands, s_in ? (const void*)(s_in + 1) : (const void*)cands, (size_t)C * sizeof(int), hipMemcpyHostToDevice, c->stream));
-    for (;;) {
-        enqueue_move(c, 0, C, -1, 2);
+    if (upload_one_move(c, s_in ? s_in : &frag_a, s_in ? s_in + 1 : cands, C)) return -1;
+    const int rc = until_it_fits(c, [&]() -> int {
+        if (enqueue_move(c, 0, C, -1, 2)) return -1;
         if (scores) HIPCK(hipMemcpyAsync(s_sc, c->mb.scores, (size_t)C * IG_N_TMP_STRUCT * sizeof(double), hipMemcpyDeviceToHost, c->stream));
         enqueue_apply(c, 0, 0, 0);
         HIPCK(hipMemcpyAsync(s_res, c->d_results, sizeof(ig_move_result), hipMemcpyDeviceToHost, c->stream));
         if (queue_max_readback(c)) return -1;
         HIPCK(hipStreamSynchronize(c->stream));
-        if (s_res->pad != 1) break;
-        take_max_readback(c);
-        if (retry_with_larger_pool(c)) return -1;
-    }
+        if (s_res->pad == 1) take_max_readback(c);
+        return s_res->pad != 1;
+    });
+    if (rc) return -1;
     if (stg) {
         *out = *s_res;
         if (scores) memcpy(scores, s_sc, (size_t)C * IG_N_TMP_STRUCT * sizeof(double));
     }
-    HIPCK(hipGetLastError());
-    drain_timers(c);
-    take_max_readback(c);
-    if (out->error) return fail("device-side consistency failure %d", out->error);
-    return 0;
+    return finish_one_move(c, out->error);
 }
 
 /* ---- one reference-shaped step_sampler call (CL:1401-1465) with less around the move -------------------------------------------------
@@ -1086,22 +1139,6 @@ extern "C" int ig_step(ig_ctx* c, int32_t frag_a, const int32_t* cands, int32_t 
  * mutually inverse take ig_step's way.  nb == NULL: the candidates are the caller's (cands[0 .. *n_cands)). */
 static bool wait_host_flag(volatile int* flag, int seq, hipStream_t stream);
 static int ensure_host_nuis(ig_ctx* c);
-static int ensure_host_step(ig_ctx* c)
-{
-    if (c->host_step) return 0;
-    StepHost* hp = nullptr;
-    if (hipHostMalloc((void**)&hp, sizeof(StepHost), hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) {
-        (void)hipGetLastError();
-        return 0; /* (no mapped memory: ig_step's way) */
-    }
-    memset(hp, 0, sizeof(StepHost));
-    c->host_step = hp;
-    void* dp = nullptr;
-    if (!(getenv("IG_NO_HOST_FLAG") && atoi(getenv("IG_NO_HOST_FLAG"))) && hipHostGetDevicePointer(&dp, hp, 0) == hipSuccess)
-        c->host_step_dev = (StepHost*)dp;
-    (void)hipGetLastError();
-    return 0;
-}
 
 extern "C" int ig_step_draw(ig_ctx* c, ig_neighbours* nb, uint32_t* mt_key624, int32_t* mt_pos, int32_t frag_a, int32_t n_neighbours,
                             int32_t* cands, int32_t* n_cands, ig_move_result* out, double* scores)
@@ -1122,7 +1159,8 @@ extern "C" int ig_step_draw(ig_ctx* c, ig_neighbours* nb, uint32_t* mt_key624, i
         if (C < 1 || C > IG_MAX_CANDIDATES) return fail("a move needs 1..%d candidates (got %d)", IG_MAX_CANDIDATES, C);
         for (int i = 0; i < C; i++) list[i] = cands[i];
     }
-    if (ensure_host_step(c) || ensure_host_nuis(c)) return -1;
+    if (!c->host_step) c->host_step = (StepHost*)mapped_block(sizeof(StepHost), (void**)&c->host_step_dev, false); /* (none: ig_step's way) */
+    if (ensure_host_nuis(c)) return -1;
     const int s_fast = getenv("IG_STEP_DRAW_FAST") ? atoi(getenv("IG_STEP_DRAW_FAST")) : 1; /* 0: ig_step's way (copies, synchronise; read per call: a test toggles it) */
     const bool fast = c->host_step_dev && c->host_nuis_dev && c->host_bo && !c->timing && s_fast && c->init_links_inverse;
     if (fast && c->nuis_in_flight) return fail("ig_step_draw: a nuisance step is in flight (ig_nuis_end): its record travels through the same mapped block");
@@ -1160,15 +1198,10 @@ extern "C" int ig_step_draw(ig_ctx* c, ig_neighbours* nb, uint32_t* mt_key624, i
         for (int i = 0; i < n_neighbours; i++) cands[i] = i < C ? list[i] : -1;
         *n_cands = C;
     }
-    if (!fast) {
-        if (ensure_move_buffers(c, std::max(8, (int)C)) || ensure_io(c, 1, C)) return -1;
-        undo.armed = false; /* (behind its own checks, all passed above, ig_step enqueues the move) */
-        return ig_step(c, frag_a, list, C, out, scores);
-    }
-    c->full_windows = false;
-    if (ensure_move_buffers(c, std::max(8, (int)C))) return -1;
-    if (ensure_io(c, 1, C)) return -1;
-    undo.armed = false; /* the move is on its way */
+    if (fast) c->full_windows = false;
+    if (ensure_move_buffers(c, std::max(8, (int)C)) || ensure_io(c, 1, C)) return -1;
+    undo.armed = false; /* the move is on its way (ig_step: behind its own checks, all passed above, it enqueues the move) */
+    if (!fast) return ig_step(c, frag_a, list, C, out, scores);
     StepHost* hs = c->host_step;
     hs->in[0] = frag_a;
     for (int i = 0; i < C; i++) hs->in[1 + i] = list[i];
@@ -1187,7 +1220,7 @@ extern "C" int ig_step_draw(ig_ctx* c, ig_neighbours* nb, uint32_t* mt_key624, i
         }
     } restore{c, c->d_frags, c->d_cands};
     for (;;) {
-        if (ensure_window_buffers(c)) return -1;
+        if (ensure_window_slots(c) < 0) return -1;
         const int seq = ++c->step_seq;
         c->d_frags = c->host_step_dev->in; /* (k_gather reads the lists from the mapped block: no upload) */
         c->d_cands = c->host_step_dev->in + 1;
@@ -1197,45 +1230,30 @@ extern "C" int ig_step_draw(ig_ctx* c, ig_neighbours* nb, uint32_t* mt_key624, i
          * the exact kernel for the columns that can still win, a score of exactly 0.0 among them the long way (stop code 3) */
         c->pub_scores = scores ? c->host_step_dev->scores : nullptr;
         c->screen_w1 = scores == nullptr;
-        enqueue_score(c, 0, 1, C, -1, 2);
+        const int rc_score = enqueue_score(c, 0, 1, C, -1, 2);
         c->screen_w1 = false;
         c->d_frags = restore.f;
         c->d_cands = restore.cd;
         const long long pend0 = c->n_batch_pending;
         int next = 0;
-        const int rc = commit_loop(c, 0, 1, &next, true);
+        const int rc = rc_score ? -1 : commit_loop(c, 0, 1, &next, true);
         c->pub_step = nullptr;
         c->pub_scores = nullptr;
         if (rc) return -1;
         if (next < 0) { /* the move did not fit: more room, again (nothing was committed: run_moves) */
-            if (next == -1) {
-                if (grow_slice_pool(c)) return -1;
-                c->n_pool_retries++;
-            } else if (next == -3) { /* (wait_commit has set exact_next: again, every column exact) */
-            } else {
-                if (c->exact_grid >= c->mb.work_cap) return fail("the exact kernel's work list cannot hold the move");
-                c->exact_grid = std::min(c->mb.work_cap, c->exact_grid * 4);
-            }
+            if (make_room(c, -next, "the move")) return -1;
+            if (next == -1) c->n_pool_retries++;
             continue;
         }
-        if (c->n_batch_pending != pend0) { /* finished by the one-move tail (k_delta .. k_commit) */
-            c->n_step_tail++;
-            if (!wait_host_flag(&hs->fin_seq, seq, c->stream)) {
-                HIPCK(hipStreamSynchronize(c->stream));
-                return fail("ig_step_draw: the move's kernels ended without its record");
-            }
-            *out = hs->fin;
-            c->max_L = std::max(c->max_L, hs->max_L);
-            c->max_SL = std::max(c->max_SL, hs->max_SL);
-        } else {
-            if (!wait_host_flag(&c->host_nuis->res_seq, c->res_seq, c->stream)) {
-                HIPCK(hipStreamSynchronize(c->stream));
-                return fail("ig_step_draw: the move's kernels ended without its record");
-            }
-            *out = c->host_nuis->res;
-            c->max_L = std::max(c->max_L, c->host_nuis->max_L);
-            c->max_SL = std::max(c->max_SL, c->host_nuis->max_SL);
+        const bool tail = c->n_batch_pending != pend0; /* finished by the one-move tail (k_delta .. k_commit): its record is StepHost.fin */
+        if (tail) c->n_step_tail++;
+        if (!(tail ? wait_host_flag(&hs->fin_seq, seq, c->stream) : wait_host_flag(&c->host_nuis->res_seq, c->res_seq, c->stream))) {
+            HIPCK(hipStreamSynchronize(c->stream));
+            return fail("ig_step_draw: the move's kernels ended without its record");
         }
+        *out = tail ? hs->fin : c->host_nuis->res;
+        c->max_L = std::max(c->max_L, tail ? hs->max_L : c->host_nuis->max_L);
+        c->max_SL = std::max(c->max_SL, tail ? hs->max_SL : c->host_nuis->max_SL);
         break;
     }
     HIPCK(hipGetLastError());
@@ -1253,17 +1271,16 @@ extern "C" int ig_score_move(ig_ctx* c, int32_t frag_a, const int32_t* cands, in
     if (validate_move(c, frag_a, cands, C)) return -1;
     if (ensure_move_buffers(c, std::max(8, (int)C))) return -1;
     if (ensure_io(c, 1, C)) return -1;
-    HIPCK(hipMemcpyAsync(c->d_frags, &frag_a, sizeof(int), hipMemcpyHostToDevice, c->stream));
-    HIPCK(hipMemcpyAsync(c->d_cands, cands, (size_t)C * sizeof(int), hipMemcpyHostToDevice, c->stream));
-    for (;;) {
+    if (upload_one_move(c, &frag_a, cands, C)) return -1;
+    const int rc = until_it_fits(c, [&]() -> int {
         int retry = 0;
-        enqueue_move(c, 0, C, -1, 2);
+        if (enqueue_move(c, 0, C, -1, 2)) return -1;
         HIPCK(hipMemcpyAsync(scores, c->mb.scores, (size_t)C * IG_N_TMP_STRUCT * sizeof(double), hipMemcpyDeviceToHost, c->stream));
         HIPCK(hipMemcpyAsync(&retry, &c->glob->retry_pool, sizeof(int), hipMemcpyDeviceToHost, c->stream));
         HIPCK(hipStreamSynchronize(c->stream));
-        if (!retry) break;
-        if (retry_with_larger_pool(c)) return -1;
-    }
+        return !retry;
+    });
+    if (rc) return -1;
     HIPCK(hipGetLastError());
     drain_timers(c);
     return 0;
@@ -1279,24 +1296,18 @@ extern "C" int ig_apply(ig_ctx* c, int32_t frag_a, int32_t frag_b, int32_t op)
     if (validate_move(c, frag_a, &frag_b, 1)) return -1;
     if (ensure_move_buffers(c, 8)) return -1;
     if (ensure_io(c, 1, 1)) return -1;
-    HIPCK(hipMemcpyAsync(c->d_frags, &frag_a, sizeof(int), hipMemcpyHostToDevice, c->stream));
-    HIPCK(hipMemcpyAsync(c->d_cands, &frag_b, sizeof(int), hipMemcpyHostToDevice, c->stream));
+    if (upload_one_move(c, &frag_a, &frag_b, 1)) return -1;
     ig_move_result r;
-    for (;;) {
-        enqueue_move(c, 0, 1, op, 2);
+    const int rc = until_it_fits(c, [&]() -> int {
+        if (enqueue_move(c, 0, 1, op, 2)) return -1;
         enqueue_apply(c, 0, 0, 1);
         HIPCK(hipMemcpyAsync(&r, c->d_results, sizeof r, hipMemcpyDeviceToHost, c->stream));
         if (queue_max_readback(c)) return -1;
         HIPCK(hipStreamSynchronize(c->stream));
-        if (r.pad != 1) break;
-        take_max_readback(c);
-        if (retry_with_larger_pool(c)) return -1;
-    }
-    HIPCK(hipGetLastError());
-    drain_timers(c);
-    take_max_readback(c);
-    if (r.error) return fail("device-side consistency failure %d", r.error);
-    return 0;
+        if (r.pad == 1) take_max_readback(c);
+        return r.pad != 1;
+    });
+    return rc ? -1 : finish_one_move(c, r.error);
 }
 
 extern "C" int ig_set_shard(ig_ctx* c, int32_t rank, int32_t world)
@@ -1320,16 +1331,16 @@ extern "C" int ig_step_begin(ig_ctx* c, int32_t frag_a, const int32_t* cands, in
     if (validate_move(c, frag_a, cands, C)) return -1;
     if (ensure_move_buffers(c, std::max(8, (int)C))) return -1;
     if (ensure_io(c, 1, C)) return -1;
-    HIPCK(hipMemcpyAsync(c->d_frags, &frag_a, sizeof(int), hipMemcpyHostToDevice, c->stream));
-    HIPCK(hipMemcpyAsync(c->d_cands, cands, (size_t)C * sizeof(int), hipMemcpyHostToDevice, c->stream));
-    for (;;) { /* (the partial sums go into a collective next: a rank whose lists did not fit its pool finds out here, on its own) */
+    if (upload_one_move(c, &frag_a, cands, C)) return -1;
+    /* (the partial sums go into a collective next: a rank whose lists did not fit its pool finds out here, on its own) */
+    const int rc = until_it_fits(c, [&]() -> int {
         int overflow = 0;
-        enqueue_move(c, 0, C, -1, 0);
+        if (enqueue_move(c, 0, C, -1, 0)) return -1;
         HIPCK(hipMemcpyAsync(&overflow, &c->mb.ctl[0].overflow, sizeof(int), hipMemcpyDeviceToHost, c->stream));
         HIPCK(hipStreamSynchronize(c->stream));
-        if (!overflow) break;
-        if (retry_with_larger_pool(c)) return -1;
-    }
+        return !overflow;
+    });
+    if (rc) return -1;
     HIPCK(hipGetLastError());
     return 0;
 }
@@ -1338,9 +1349,7 @@ extern "C" int ig_step_finish(ig_ctx* c, ig_move_result* out, double* scores)
 {
     IG_JOIN(c);
     HIPCK(hipSetDevice(c->device));
-    int C = 0;
-    enqueue_move(c, 0, IG_MAX_CANDIDATES, -1, 1);
-    (void)C;
+    if (enqueue_move(c, 0, IG_MAX_CANDIDATES, -1, 1)) return -1;
     if (scores) {
         MoveCtl mc;
         HIPCK(hipMemcpyAsync(&mc, c->mb.ctl, sizeof mc, hipMemcpyDeviceToHost, c->stream));
@@ -1351,10 +1360,7 @@ extern "C" int ig_step_finish(ig_ctx* c, ig_move_result* out, double* scores)
     HIPCK(hipMemcpyAsync(out, c->d_results, sizeof(ig_move_result), hipMemcpyDeviceToHost, c->stream));
     if (queue_max_readback(c)) return -1;
     HIPCK(hipStreamSynchronize(c->stream));
-    HIPCK(hipGetLastError());
-    drain_timers(c);
-    take_max_readback(c);
-    if (out->error) return fail("device-side consistency failure %d", out->error);
+    if (finish_one_move(c, out->error)) return -1;
     if (out->pad == 1) { /* (ig_step_begin repeats a move whose lists did not fit: not reachable unless the lists changed in between) */
         HIPCK(hipMemsetAsync(&c->glob->retry_pool, 0, sizeof(int), c->stream));
         return fail("ig_step_finish: the move's lists did not fit the slice pool");

@@ -46,9 +46,7 @@ static int nuis_join(ig_ctx* c)
             if ((spin & 0x3ff) == 0x3ff) std::this_thread::yield();
     }
     if (w->rc) {
-        const int rc = w->rc;
         w->rc = 0;
-        (void)rc;
         return fail("%s", w->err.c_str());
     }
     return 0;
@@ -206,6 +204,27 @@ static void drain_timers(ig_ctx* c)
     }
 }
 
+/* a zeroed block of pinned host memory the kernels write themselves (mapped, coherent: no copy, no stream synchronisation) and its
+ * device address -- *dev stays null where the block cannot be mapped or IG_NO_HOST_FLAG=1 says not to (tests: the copying paths);
+ * need_dev: without a device address the block is of no use.  nullptr: no such memory. */
+static void* mapped_block(size_t bytes, void** dev, bool need_dev)
+{
+    const bool s_no_flag = getenv("IG_NO_HOST_FLAG") && atoi(getenv("IG_NO_HOST_FLAG")); /* (read per block: a test toggles it between handles) */
+    void *hp = nullptr, *dp = nullptr;
+    *dev = nullptr;
+    if ((need_dev && s_no_flag) || hipHostMalloc(&hp, bytes, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) hp = nullptr;
+    if (hp && !s_no_flag && hipHostGetDevicePointer(&dp, hp, 0) == hipSuccess) *dev = dp;
+    if (hp && need_dev && !*dev) {
+        hipHostFree(hp);
+        hp = nullptr;
+    }
+    if (hp) memset(hp, 0, bytes);
+    (void)hipGetLastError();
+    return hp;
+}
+
+static const double kWindowBudget = 64e9; /* ig_ctx.window_budget unless ig_debug_window_budget says otherwise (slots_in_budget) */
+
 extern "C" const char* ig_last_error(void) { return g_err.c_str(); }
 
 extern "C" int ig_create(int device_id, ig_ctx** out)
@@ -215,111 +234,32 @@ extern "C" int ig_create(int device_id, ig_ctx** out)
     if (hipGetDeviceCount(&n) != hipSuccess || n == 0) return fail("ig_create: no HIP device (the MI355X path has no CPU fallback)");
     if (device_id < 0 || device_id >= n) return fail("ig_create: device %d out of range (%d devices)", device_id, n);
     HIPCK(hipSetDevice(device_id));
-    ig_ctx* c = new ig_ctx();
-    memset((void*)&c->st, 0, sizeof c->st);
-    memset((void*)&c->tab, 0, sizeof c->tab);
-    memset((void*)&c->tab_prev, 0, sizeof c->tab_prev);
-    memset((void*)&c->mb, 0, sizeof c->mb);
+    ig_ctx* c = new ig_ctx(); /* value-initialised: every field starts as zero / null / false; what follows is what does not */
     c->device = device_id;
     c->own_stream = true;
-    c->host_bo = nullptr;
-    c->host_bo_dev = nullptr;
-    c->bo_seq = 0;
-    c->w_ema = 0.0;
-    c->n_contigs_seen = 0;
-    c->rank = 0;
     c->world = 1;
-    c->N = c->M = 0;
-    c->Z = 0;
-    c->max_count = 0;
-    c->st_block = nullptr;
-    c->sub_tab = nullptr;
-    c->rowptr = nullptr;
-    c->cc = nullptr;
-    c->crow = nullptr;
-    c->tabrec = nullptr;
-    c->tiled_cc = nullptr;
-    c->tile_work = nullptr;
-    c->n_tile_work = 0;
-    c->tile_trace = c->diff_trace = nullptr;
-    c->init_prev = c->init_next = c->orientable = nullptr;
-    c->black = nullptr;
-    c->batch_out = nullptr;
-    c->own_tag = c->own_idx = nullptr;
-    c->dirty_buf = nullptr;
-    c->d_results = nullptr;
-    c->results_cap = 0;
-    c->d_frags = c->d_cands = nullptr;
-    c->cands_cap = 0;
-    c->prev_touched = nullptr;
-    c->pz_tab = c->pz_tab1 = nullptr;
-    c->score_const = nullptr;
-    c->full_const = nullptr;
-    c->screen_const = nullptr;
-    c->screen_worst = nullptr;
-    c->n_screen_cols = c->n_screen_cont = 0;
-    c->pz_n = c->pz_n1 = 0;
     c->timing_mask = 0xffff;
     c->side_busy = true;
     c->timing_every = 1;
-    c->timing = false;
-    c->n_batches = c->n_batch_committed = c->n_batch_pending = c->n_batch_predicted = 0;
-    c->up_moves = c->up_max_c = 0;
-    c->own_begin = c->own_end = 0;
-    c->own_screened = 0;
-    c->last_stale = 0ull;
-    c->n_window_slots = 0;
-    c->exact_grid = 0;
-    c->max_L = c->max_SL = 0;
-    c->full_windows = false;
-    c->host_max = nullptr;
-    c->host_step = c->host_step_dev = nullptr;
-    c->pub_step = nullptr;
-    c->pub_scores = nullptr;
-    c->screen_w1 = false;
-    c->step_seq = 0;
-    c->n_step_tail = 0;
+    c->window_budget = kWindowBudget;
     for (int i = 0; i < T_COUNT; i++) {
         c->timers[i].name = kTimerNames[i];
         c->timers[i].total_ms = 0;
         c->timers[i].n = 0;
     }
-    c->have_contacts = c->have_sub = c->have_state = c->have_init = c->have_params = false;
     c->init_links_inverse = true;
     HIPCK(hipStreamCreate(&c->stream));
     HIPCK(hipStreamCreate(&c->stream2));
     HIPCK(hipStreamCreate(&c->stream3));
     HIPCK(hipEventCreateWithFlags(&c->ev_gathered, hipEventDisableTiming));
     HIPCK(hipEventCreateWithFlags(&c->ev_main, hipEventDisableTiming));
-    c->host_nuis = nullptr;
-    c->host_nuis_dev = nullptr;
-    c->nuis_in_flight = false;
-    c->diff_const = nullptr;
-    c->scratch_diff = nullptr;
-    c->tile_partial0 = nullptr;
-    c->diff_seq = 0;
-    c->nuis_diff = c->nuis_exact_queued = c->nuis_screen_rejected = false;
-    c->scratch_exact = nullptr;
-    c->nuis_sums_pending = c->nuis_accept_certain = false;
-    c->exact_seq = 0;
     HIPCK(hipEventCreateWithFlags(&c->ev_exact, hipEventDisableTiming));
     HIPCK(hipEventCreateWithFlags(&c->ev_walk, hipEventDisableTiming));
-    c->worker = nullptr;
-    c->probe_scr = nullptr;
-    c->probe_void = nullptr;
     c->last_moved = true;
-    c->n_accepts = 0;
-    c->nh = NuisHist{nullptr, nullptr, nullptr, 0};
-    c->scratch_hist = nullptr;
-    c->nh_valid = false;
     c->nh_pending_slot = -1;
-    c->nh_tracking = false;
     c->nh_policy_on = true;
     c->nh_p_changed = 0.1;
     c->nuis_tier = 1;
-    c->nuis_tiles_listed = false;
-    for (double& v : c->nhs) v = 0.0;
-    for (double& v : c->nscr) v = 0.0;
     HIPCK(hipEventCreateWithFlags(&c->ev_slice, hipEventDisableTiming));
     HIPCK(hipEventCreateWithFlags(&c->ev_tail, hipEventDisableTiming));
     DALLOC(c->glob, 1);
@@ -610,10 +550,17 @@ static double window_bytes_per_slot(int capC, double sN, double sM)
 {
     return (double)std::max(8, capC) * ((double)NSLOT * NDYN * sN * 4.0 + sM * NSLOT * 8.0 + 3.0 * sN * 4.0 + 2.0 * sM * 4.0);
 }
-/* slots the per-window arrays hold (<= MoveBuf.capW: fewer once long contigs have made a slot gigabytes) */
-static int window_slots(const ig_ctx* c) { return c->win_slots > 0 ? std::min(c->win_slots, c->mb.capW) : c->mb.capW; }
-static int ensure_window_buffers(ig_ctx* c, MoveBuf& m)
+/* THE slot budget: the slots whose per-window arrays fit ig_ctx.window_budget at these strides (at least one: a genome whose one slot
+ * is over the budget is tried, and fails in hipMalloc if it must).  max_batch_width, window_ring and ensure_window_buffers size by it. */
+static int slots_in_budget(const ig_ctx* c, int capC, double sN, double sM)
 {
+    return (int)std::max(1.0, std::min(c->window_budget / window_bytes_per_slot(capC, sN, sM), 1e6));
+}
+/* slots the per-window arrays hold now (<= MoveBuf.capW: fewer once long contigs have made a slot gigabytes; 0: none allocated) */
+static int slots_held(const ig_ctx* c) { return c->mb.Lloc ? c->win_slots : 0; }
+static int ensure_window_buffers(ig_ctx* c)
+{
+    MoveBuf& m = c->mb;
     if (!m.capC || !m.capW) return 0;
     const int need_n = std::min(c->N, std::max(2 * c->max_L, 1)), need_m = std::min(c->M, std::max(2 * c->max_SL, 1));
     const bool s_full = c->full_windows; /* strides = the whole genome */
@@ -622,11 +569,10 @@ static int ensure_window_buffers(ig_ctx* c, MoveBuf& m)
     const int sM = s_full ? c->M : std::min(c->M, std::max(768, need_m + need_m / 2));
     HIPCK(hipStreamSynchronize(c->stream));
     free_window_buffers(m);
-    /* as many physical slots as the budget of max_batch_width holds at the NEW strides (ADVICE r5: the window rule sizes the set to its ring
-     * of up to 64 slots once per call, and contigs that merge during the call regrow the strides -- a late, long-contig state that fitted
-     * at 24 slots must shrink its ring instead of failing in hipMalloc in the middle of a call); the callers cap their widths by
-     * window_slots() behind every call of this function */
-    c->win_slots = std::max(1, std::min(m.capW, (int)std::min<double>(64e9 / window_bytes_per_slot(m.capC, sN, sM), 1e6)));
+    /* as many physical slots as the budget holds at the NEW strides (ADVICE r5: the window rule sizes the set to its ring of up to 64
+     * slots once per call, and contigs that merge during the call regrow the strides -- a late, long-contig state that fitted at 24
+     * slots must shrink its ring instead of failing in hipMalloc in the middle of a call) */
+    c->win_slots = std::min(m.capW, slots_in_budget(c, m.capC, sN, sM));
     const size_t C = (size_t)m.capC * c->win_slots;
     DALLOC(m.Lloc, C * sN);
     DALLOC(m.lbloc, C * sN);
@@ -640,7 +586,23 @@ static int ensure_window_buffers(ig_ctx* c, MoveBuf& m)
     m.sM = sM;
     return 0;
 }
-static int ensure_window_buffers(ig_ctx* c) { return ensure_window_buffers(c, c->mb); }
+/* the window buffers at the strides the genome needs NOW -> the slots they hold, or -1.  Whoever sizes a launch takes its cap from this
+ * call's answer, so that no width can be older than the buffers it is launched on; enqueue_score refuses anything wider (slots_held). */
+static int ensure_window_slots(ig_ctx* c) { return ensure_window_buffers(c) ? -1 : slots_held(c); }
+/* tests: this handle's budget (bytes <= 0: the default again); the window buffers are sized anew under it at once -> *slots: what they
+ * hold now (0: no move buffers yet).  Whatever was scored ahead in them is gone. */
+extern "C" int ig_debug_window_budget(ig_ctx* c, double bytes, int32_t* slots)
+{
+    IG_JOIN(c);
+    HIPCK(hipSetDevice(c->device));
+    HIPCK(hipStreamSynchronize(c->stream));
+    c->window_budget = bytes > 0 ? bytes : kWindowBudget;
+    free_window_buffers(c->mb);
+    c->spec_valid = false;
+    const int held = ensure_window_slots(c);
+    if (slots) *slots = std::max(held, 0);
+    return held < 0 ? -1 : 0;
+}
 
 /* the slice pool: room for the lists of a batch.  A slot whose lists do not fit behind the earlier ones is re-run; when
  * the FIRST slot of a batch does not fit, the host grows the pool (grow_slice_pool) and repeats the batch.  The worst case
@@ -714,21 +676,8 @@ static int ensure_move_buffers(ig_ctx* c, int capC, int capW = 1)
     DALLOC(c->own_idx, N);
     HIPCK(memset_now(c->own_tag, 0xff, N * sizeof(int)));
     DALLOC(c->batch_out, 16);
-    if (!c->host_bo && !(getenv("IG_NO_HOST_FLAG") && atoi(getenv("IG_NO_HOST_FLAG")))) {
-        /* the batch outcome is also written to mapped host memory (commit_loop polls it); without it: copy + synchronise */
-        int* hp = nullptr;
-        if (hipHostMalloc((void**)&hp, 16 * sizeof(int), hipHostMallocMapped | hipHostMallocCoherent) == hipSuccess) {
-            void* dp = nullptr;
-            if (hipHostGetDevicePointer(&dp, hp, 0) == hipSuccess) {
-                memset(hp, 0, 16 * sizeof(int));
-                c->host_bo = hp;
-                c->host_bo_dev = (int*)dp;
-            } else {
-                hipHostFree(hp);
-            }
-        }
-        (void)hipGetLastError();
-    }
+    /* the batch outcome is also written to mapped host memory (commit_loop polls it); without it: copy + synchronise */
+    if (!c->host_bo) c->host_bo = (int*)mapped_block(16 * sizeof(int), (void**)&c->host_bo_dev, true);
     DALLOC(c->dirty_buf, 2 * IG_MAX_BATCH + 4);
     return ensure_window_buffers(c);
 }

@@ -23,17 +23,8 @@ __global__ void k_catch_up(Tables tab, Tables tab_prev, const int* __restrict__ 
 static int ensure_host_nuis(ig_ctx* c)
 {
     if (c->host_nuis) return 0;
-    NuisHost* hp = nullptr;
-    if (hipHostMalloc((void**)&hp, sizeof(NuisHost), hipHostMallocMapped | hipHostMallocCoherent) == hipSuccess) {
-        void* dp = nullptr;
-        memset(hp, 0, sizeof(NuisHost));
-        c->host_nuis = hp;
-        if (!(getenv("IG_NO_HOST_FLAG") && atoi(getenv("IG_NO_HOST_FLAG"))) && hipHostGetDevicePointer(&dp, hp, 0) == hipSuccess)
-            c->host_nuis_dev = (NuisHost*)dp;
-        (void)hipGetLastError();
-        return 0;
-    }
-    (void)hipGetLastError();
+    c->host_nuis = (NuisHost*)mapped_block(sizeof(NuisHost), (void**)&c->host_nuis_dev, false);
+    if (c->host_nuis) return 0;
     HIPCK(hipHostMalloc((void**)&c->host_nuis, sizeof(NuisHost), hipHostMallocDefault));
     memset(c->host_nuis, 0, sizeof(NuisHost));
     return 0;
@@ -333,8 +324,7 @@ extern "C" int ig_nuis_begin(ig_ctx* c, int32_t frag_a, const int32_t* cands, in
     if (ensure_host_nuis(c)) return -1;
     c->host_nuis->frag = frag_a;
     for (int i = 0; i < C; i++) c->host_nuis->cands[i] = cands[i];
-    HIPCK(hipMemcpyAsync(c->d_frags, &c->host_nuis->frag, sizeof(int), hipMemcpyHostToDevice, c->stream));
-    HIPCK(hipMemcpyAsync(c->d_cands, c->host_nuis->cands, (size_t)C * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    if (upload_one_move(c, &c->host_nuis->frag, c->host_nuis->cands, C)) return -1;
     c->nuis_in_flight = true;
     c->nuis_spec = false;
     c->spec_valid = false;
@@ -342,7 +332,7 @@ extern "C" int ig_nuis_begin(ig_ctx* c, int32_t frag_a, const int32_t* cands, in
     c->nuis_one_C = C;
     if (enqueue_nuis_pass(c, p_test, mean_subfrag_kb)) return -1;
     /* the move */
-    enqueue_move(c, 0, C, -1, 2);
+    if (enqueue_move(c, 0, C, -1, 2)) return -1;
     enqueue_apply(c, 0, 0, 0);
     HIPCK(hipMemcpyAsync(&c->host_nuis->res, c->d_results, sizeof(ig_move_result), hipMemcpyDeviceToHost, c->stream));
     if (queue_max_readback(c)) return -1;
@@ -356,11 +346,11 @@ extern "C" int ig_nuis_begin(ig_ctx* c, int32_t frag_a, const int32_t* cands, in
  * moves starting at i if move i has no valid scores yet (first step, after an accepted step, after a conflict, batch used
  * up), and decides + applies move i ALONE from its records (k_decide_batch over one slot); ig_nuis_end / ig_nuis_accept as
  * above.  An accepted step invalidates the slots scored ahead.  Same results as one move and one step at a time. */
-static int nuis_spec_width(ig_ctx* c)
+static int nuis_spec_width(ig_ctx* c, int slots)
 {
     if (g_nuis_w < 0) g_nuis_w = 0; /* (IG_NUIS_W: nuis_latch_env) */
     const int s_w = g_nuis_w;
-    const int cap = std::min(window_slots(c), IG_MAX_BATCH);
+    const int cap = std::min(slots, IG_MAX_BATCH);
     if (s_w > 0) return std::min(s_w, cap);
     if (c->spec_ema <= 0.0) c->spec_ema = 3.0;
     return std::max(1, std::min(cap, (int)(1.5 * c->spec_ema + 1.5)));
@@ -407,15 +397,16 @@ extern "C" int ig_nuis_run_begin(ig_ctx* c, int32_t n_moves, const int32_t* frag
 
 /* Widths.  The PARAMETER width (slots screened / scored per launch) follows the number of moves decided between two accepted
  * steps; the STRUCTURAL width (slots gathered, mutated and sliced per launch) the number of moves a batch gets through before
- * a conflict -- an accepted step voids only the former.  IG_NUIS_W / ig_set_nuis_width fixes both (tests). */
-static int nuis_struct_width(ig_ctx* c)
+ * a conflict -- an accepted step voids only the former.  IG_NUIS_W / ig_set_nuis_width fixes both (tests).  `slots`: what the window
+ * buffers hold, from the call that ensured them (nuis_spec_score) */
+static int nuis_struct_width(ig_ctx* c, int slots)
 {
-    const int cap = std::min(window_slots(c), IG_MAX_BATCH);
+    const int cap = std::min(slots, IG_MAX_BATCH);
     if (g_nuis_w > 0) return std::min(g_nuis_w, cap);
     if (c->spec_struct_ema <= 0.0) c->spec_struct_ema = cap;
     /* (not "at least the parameter width": that one follows the runs between accepted steps now, and where a batch ends in a conflict
      * after two moves -- few long contigs -- slots gathered, mutated and sliced behind it are wasted) */
-    return std::max(2, std::min(cap, (int)(1.5 * c->spec_struct_ema + 1.5)));
+    return std::min(cap, std::max(2, (int)(1.5 * c->spec_struct_ema + 1.5))); /* (at least two where two fit) */
 }
 
 /* the parameter-dependent scores ahead are of no use any more (accepted step) */
@@ -461,12 +452,14 @@ static int nuis_spec_score(ig_ctx* c, int move)
 {
     if (nh_flush_pending(c)) return -1; /* (the buffers of the last move's slot are about to be overwritten) */
     nuis_spec_invalidate(c);
-    const int W = std::min(nuis_struct_width(c), c->up_moves - move);
-    const int r = std::min(nuis_spec_width(c), W);
-    if (ensure_window_buffers(c)) return -1; /* the longest contig may have grown */
+    const int held = ensure_window_slots(c); /* the longest contig may have grown: the buffers first, the widths from what they hold */
+    if (held < 0) return -1;
+    const int W = std::min(nuis_struct_width(c, held), c->up_moves - move);
+    const int r = std::min(nuis_spec_width(c, held), W);
     c->no_predict = !(nuis_chain_on() && nuis_hist_usable(c)); /* (decided one move per step: a pause for a windowed winner costs nothing the step would not wait for anyway; a chain would end at it) */
-    enqueue_score(c, move, W, c->up_max_c, -1, 2, 0, W, 0, r, false);
+    const int rc = enqueue_score(c, move, W, c->up_max_c, -1, 2, 0, W, 0, r, false);
     c->no_predict = false;
+    if (rc) return -1;
     c->spec_base = move;
     c->spec_W = W;
     c->spec_next = 0;
@@ -486,10 +479,12 @@ static bool nuis_spec_can_rescore(const ig_ctx* c, int move)
 static int nuis_spec_rescore(ig_ctx* c)
 {
     nuis_par_invalidate(c);
-    const int pb = c->spec_next, pe = std::min(c->spec_W, pb + nuis_spec_width(c));
+    /* (NOT ensure_window_slots: the structural half of the batch lives in the buffers as they are -- what they hold is the cap) */
+    const int pb = c->spec_next, pe = std::min(c->spec_W, pb + nuis_spec_width(c, slots_held(c)));
     c->no_predict = !(nuis_chain_on() && nuis_hist_usable(c));
-    enqueue_score(c, c->spec_base, c->spec_W, c->up_max_c, -1, 2, 0, c->spec_W, pb, pe, true);
+    const int rc = enqueue_score(c, c->spec_base, c->spec_W, c->up_max_c, -1, 2, 0, c->spec_W, pb, pe, true);
     c->no_predict = false;
+    if (rc) return -1;
     c->spec_par_begin = pb;
     c->spec_par_end = pe;
     return 0;
@@ -540,8 +535,7 @@ static int nuis_spec_finish(ig_ctx* c)
         int bo[16];
         const int w = c->spec_next;
         if (wait_commit(c, bo, w == c->spec_par_begin, w)) return -1;
-        if (c->own_screened == 1 && w == c->spec_par_begin && !(bo[2] && bo[0] == 0 && bo[1] < 0))
-            c->exact_grid = std::min(c->mb.work_cap, std::max(exact_grid_floor(c, c->up_max_c), (int)(1.25 * bo[6]) + 2048));
+        if (c->own_screened == 1 && w == c->spec_par_begin && !(bo[2] && bo[0] == 0 && bo[1] < 0)) size_exact_grid(c, bo);
         if (bo[0] == w + 1) {
             c->spec_prev_pending = false;
             break;
@@ -556,17 +550,12 @@ static int nuis_spec_finish(ig_ctx* c)
         /* not decided: a contig of the move was modified by an earlier move of the batch (w > 0), or the first slot did not
          * fit the slice pool / the exact kernel's grid: score a batch from this move */
         if (w == 0) {
-            if (bo[2] == 1) {
-                if (grow_slice_pool(c)) return -1;
-            } else if (bo[2] == 2) {
-                if (c->exact_grid >= c->mb.work_cap) return fail("the exact kernel's work list cannot hold the first move of a batch");
-                c->exact_grid = std::min(c->mb.work_cap, c->exact_grid * 4);
-            } else if (bo[2] == 3) { /* (a score of exactly 0.0: exact_next is set, the scoring below leaves the screening tier out) */
-            } else {
+            if (bo[2] < 1 || bo[2] > 3) {
                 Glob hg;
                 HIPCK(hipMemcpy(&hg, c->glob, sizeof hg, hipMemcpyDeviceToHost));
                 return fail("device-side consistency failure %d at move %d of a run", hg.error, c->spec_move);
             }
+            if (make_room(c, bo[2], "the first move of a batch")) return -1;
             c->spec_valid = false; /* says nothing about run lengths */
         }
         if (attempt > 8) return fail("move %d of a run could not be decided", c->spec_move);
@@ -649,7 +638,7 @@ static int nuis_end_body(ig_ctx* c, ig_move_result* out, double* nz_test, double
                                                                 * slice pool and nothing was applied -- the move again with a larger pool (the
                                                                 * step's pass read the state before the move: it stands) */
             if (retry_with_larger_pool(c)) return -1;
-            enqueue_move(c, 0, c->nuis_one_C, -1, 2);
+            if (enqueue_move(c, 0, c->nuis_one_C, -1, 2)) return -1;
             enqueue_apply(c, 0, 0, 0);
             HIPCK(hipMemcpyAsync(&c->host_nuis->res, c->d_results, sizeof(ig_move_result), hipMemcpyDeviceToHost, c->stream));
             if (queue_max_readback(c)) return -1;
@@ -1145,10 +1134,9 @@ static int nuis_chain_impl(ig_ctx* c, int32_t move, int32_t n_sets, float mean_k
         hipLaunchKernelGGL(k_chain_hist_eval, dim3(n_zero + NH_NB / 256 + NH_DH_BLOCKS, avail), dim3(256), 0, st, c->nh, c->glob, c->chain_sets + done,
                            c->score_const, c->chain_out16, c->tab, c->M, c->chain_zs, n_zero, pz0, c->chain_tests);
         flush_pending_sums(c);
-        const int zcheck = (c->own_screened == 1 ? 1 : 0) | (std::max(g_zero_inject, 0) << 8);
+        const int zcheck = decide_zcheck(c);
         const ChainArgs ca{c->chain_tests, c->chain_in, done, 1.0};
-        static const int s_fused = getenv("IG_FUSED_COMMIT") ? atoi(getenv("IG_FUSED_COMMIT")) : 1;
-        if (s_fused >= 2 || (s_fused == 1 && c->max_SL <= 4096)) { /* decisions and apply step in one launch (as launch_commit chooses) */
+        if (fuse_commit(c, false)) { /* decisions and apply step in one launch */
             hipLaunchKernelGGL(k_chain_decide_commit, dim3(1), dim3(64 + FUSED_CW * 64), 0, st, c->glob, c->mb, c->d_results, c->spec_base, w0 + avail, w0,
                                c->dirty_buf, c->batch_out, (volatile int*)c->host_bo_dev, ++c->bo_seq, c->spec_prev_pending ? 0 : 1, c->st, c->tab,
                                c->tab_prev, c->init_prev, c->init_next, c->orientable, c->black, c->own_tag, c->own_idx, c->prev_touched, zcheck, ca);
@@ -1161,8 +1149,7 @@ static int nuis_chain_impl(ig_ctx* c, int32_t move, int32_t n_sets, float mean_k
         }
         int bo[16];
         if (wait_commit(c, bo, w0 == c->spec_par_begin, w0)) return -1;
-        if (c->own_screened == 1 && w0 == c->spec_par_begin && !(bo[2] && bo[0] == w0 && bo[1] < 0))
-            c->exact_grid = std::min(c->mb.work_cap, std::max(exact_grid_floor(c, c->up_max_c), (int)(1.25 * bo[6]) + 2048));
+        if (c->own_screened == 1 && w0 == c->spec_par_begin && !(bo[2] && bo[0] == w0 && bo[1] < 0)) size_exact_grid(c, bo);
         const int j = bo[0] - w0;
         if (j < 0 || j > avail) return fail("ig_nuis_chain: the decide step reported %d of %d pairs", j, avail);
         c->n_chain_segments++;

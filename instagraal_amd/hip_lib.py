@@ -648,6 +648,13 @@ class Context:
         _ck(lib().ig_debug_pool_retries(self._h, C.byref(n)))
         return int(n.value)
 
+    def debug_window_budget(self, nbytes=0.0):
+        """set the bytes the per-window arrays of this handle's move buffers may take (<= 0: the default, 64e9) and size them again ->
+        the move slots they hold now (0: no move buffers yet)"""
+        n = C.c_int32()
+        _ck(lib().ig_debug_window_budget(self._h, C.c_double(float(nbytes)), C.byref(n)))
+        return int(n.value)
+
     def debug_nuis_hist_check(self):
         """words of the maintained histogram that differ from one built from scratch (-1: no histogram kept)"""
         n = C.c_int64()

@@ -177,8 +177,10 @@ class BatchRunner:
             self._buffers(cap_slots)
         done = 0
         while done < n:
-            # the width follows the conflict rate (identical on every rank: it only depends on the committed counts)
-            w_want = max(world, min(self.width, int(1.5 * self._ema + 1.5)))
+            # the width follows the conflict rate (identical on every rank: it only depends on the committed counts) and, batch by
+            # batch, what the library promises to score: contigs that merge during the run make a slot larger, and fewer may fit
+            fit = self.ctx.batch_max_width(cands.shape[1]) if hasattr(self.ctx, "batch_max_width") else self.width
+            w_want = max(world, min(self.width, fit, int(1.5 * self._ema + 1.5)))
             w_now = min(w_want, n - done)
             per = -(-w_now // world)
             b, e = min(rank * per, w_now), min((rank + 1) * per, w_now)

@@ -5,7 +5,8 @@
 // grid), the speculative-batch driver (widths, conflicts, pending one-move tails, first-slot overflows of both kinds), the
 // fused draw + step entry point with its drawing thread, the runs of (move, nuisance step) pairs -- scored-ahead batches
 // whose structural half survives accepted steps, the screened pass's three outcomes (decisive, undecided, void), the exact
-// fallback, promotion -- the mapped-memory flag protocol, every argument check.  The models script the few device outputs
+// fallback, promotion -- the mapped-memory flag protocol, every argument check, and every caller that sizes a launch once more under a
+// slot budget that binds (budget_block).  The models script the few device outputs
 // that steer the host (the decide step's outcome block, result records, pass sums) with pseudo-random but protocol-conforming
 // values; sums and scores are meaningless here, memory safety and the state machines are the subject.
 // Built and run by tests/test_cpu_abi_and_host.py::test_host_logic_under_address_and_ub_sanitizers.
@@ -324,6 +325,148 @@ static void model_commit_one(void** a, dim3, dim3)
     }
 }
 
+// jump distributions over the bins of `pr` for draws of nn neighbours (ig_neighbours_create), nullptr: refused
+static ig_neighbours* make_neighbours(const Problem& pr, int nn)
+{
+    std::vector<int64_t> indptr(pr.N + 1, 0);
+    std::vector<int32_t> xk;
+    std::vector<float> pk;
+    for (int f = 0; f < pr.N; f++) {
+        /* bins without a hetero contact draw uniformly (CL:3124) -- possibly the focal bin itself, which is dropped: with one
+         * neighbour asked for that can leave an empty list, a refused move (quirk Q13); not what this block is after */
+        const int deg = (f % 7 == 0 && nn > 2) ? 0 : 1 + (int)(rnd() % 12);
+        float tot = 0;
+        const size_t at = pk.size();
+        for (int q = 0; q < deg; q++) {
+            int32_t b = (int32_t)(rnd() % (uint32_t)pr.N);
+            if (b == f) b = (b + 1) % pr.N;
+            bool dup = false;
+            for (size_t e = at; e < xk.size(); e++) dup |= xk[e] == b;
+            if (dup) continue;
+            xk.push_back(b);
+            pk.push_back(1.0f + (float)(rnd() % 9));
+            tot += pk.back();
+        }
+        for (size_t e = at; e < pk.size(); e++) pk[e] /= tot;
+        indptr[f + 1] = (int64_t)xk.size();
+    }
+    ig_neighbours* nb = nullptr;
+    return ig_neighbours_create(indptr.data(), xk.data(), pk.data(), pr.N, nullptr, 0, &nb) == 0 ? nb : nullptr;
+}
+
+// ---- the slot budget (ig_ctx.window_budget): every caller that sizes a launch once more, under a budget that holds fewer slots than the
+// move buffers were made for and while the decide model reports longer contigs -- the window buffers are regrown in the middle of the
+// runs, fewer slots fit behind each regrowth, and a launch wider than the slots held is refused by enqueue_score (a failed call here)
+static int budget_block(ig_ctx* c, const Problem& pr, const float p8[8])
+{
+    const int max_c = 5, n_moves = 120, nn = std::min(max_c, std::max(1, pr.N - 1));
+    if (pr.N < 3) return 0;
+    std::vector<int32_t> frags(n_moves), cands((size_t)n_moves * max_c, -1);
+    for (int i = 0; i < n_moves; i++) {
+        frags[i] = (int32_t)(rnd() % (uint32_t)pr.N);
+        const int C = 1 + (int)(rnd() % (uint32_t)std::min(max_c, pr.N - 1));
+        for (int q = 0; q < C; q++) cands[(size_t)i * max_c + q] = (frags[i] + 1 + (int32_t)(rnd() % (uint32_t)(pr.N - 1))) % pr.N;
+    }
+    std::vector<ig_move_result> res(n_moves);
+    ig_move_result one;
+    CHECK(ig_set_window(48) == 0 && ig_set_batch_width(24) == 0);
+    CHECK(ig_step_batch(c, 8, frags.data(), cands.data(), max_c, res.data()) == 0); /* (the move buffers, a ring of 64 slots) */
+    const int capW = c->mb.capW, capC = c->mb.capC;
+    CHECK(capW >= 48);
+    /* five slots at the strides of a genome of short contigs; the regrown strides are up to three times as long */
+    const double per_cand = (double)NSLOT * NDYN * std::min(pr.N, 256) * 4.0 + (double)std::min(pr.M, 768) * NSLOT * 8.0 + 3.0 * std::min(pr.N, 256) * 4.0 + 2.0 * std::min(pr.M, 768) * 4.0;
+    const double budget = 5.5 * capC * per_cand;
+    int min_held = capW, shrunk = 0;
+    /* before each caller: the contig lengths recounted (short again), the budget written, the buffers sized anew under it */
+    auto arm = [&](int32_t& held) -> int {
+        CHECK(ig_upload_state(c, pr.soa.data(), pr.N) == 0);
+        c->window_budget = budget;
+        CHECK(ig_debug_window_budget(c, c->window_budget, &held) == 0 && held == c->win_slots && held >= 1 && held <= 5);
+        g_grow_windows = 1;
+        return 0;
+    };
+    /* behind each: what the buffers hold now, and ig_scratch_bytes saying so */
+    auto seen = [&](int held_before) -> int {
+        g_grow_windows = 0;
+        const MoveBuf& m = c->mb;
+        int64_t sb[3];
+        CHECK(ig_scratch_bytes(c, sb) == 0);
+        CHECK(sb[0] == (int64_t)m.capC * c->win_slots * ((int64_t)m.sN * 4 * 3 + (int64_t)m.sM * 4 * 2 + (int64_t)m.sM * NSLOT * 8 + (int64_t)NSLOT * NDYN * m.sN * 4));
+        CHECK(c->win_slots >= 1 && c->win_slots <= held_before);
+        min_held = std::min(min_held, c->win_slots);
+        shrunk += c->win_slots < held_before;
+        return 0;
+    };
+    int32_t h = 0;
+    CHECK(arm(h) == 0 && ig_step_batch(c, n_moves, frags.data(), cands.data(), max_c, res.data()) == 0 && seen(h) == 0); /* the window rule */
+    CHECK(ig_set_window(0) == 0);
+    CHECK(arm(h) == 0 && ig_step_batch(c, n_moves, frags.data(), cands.data(), max_c, res.data()) == 0 && seen(h) == 0); /* plain batches */
+    CHECK(ig_set_window(48) == 0);
+    if (pr.N > nn + 1) {
+        ig_neighbours* nb = make_neighbours(pr, nn);
+        CHECK(nb);
+        std::vector<uint32_t> key(624);
+        for (auto& k : key) k = rnd();
+        int32_t pos = 624;
+        std::vector<int32_t> cout_((size_t)n_moves * nn, -1);
+        CHECK(arm(h) == 0 && ig_step_batch_draw(c, nb, key.data(), &pos, n_moves, frags.data(), nn, cout_.data(), res.data()) == 0 && seen(h) == 0);
+        CHECK(arm(h) == 0);
+        for (int rep = 0; rep < 40; rep++) {
+            int32_t nc = 0;
+            std::vector<int32_t> cl(nn, -7);
+            CHECK(ig_step_draw(c, nb, key.data(), &pos, frags[rep], nn, cl.data(), &nc, &one, nullptr) == 0);
+        }
+        CHECK(seen(h) == 0);
+        ig_neighbours_destroy(nb);
+    }
+    { /* the slot-split loop: every batch as wide as ig_batch_max_width promises at that moment -- ig_batch_score keeps the promise */
+        CHECK(arm(h) == 0);
+        const int w0 = ig_batch_max_width(c, max_c);
+        CHECK(w0 >= 1 && w0 <= h);
+        CHECK(ig_batch_upload(c, n_moves, frags.data(), cands.data(), max_c, w0) == 0);
+        CHECK(ig_batch_upload(c, n_moves, frags.data(), cands.data(), max_c, h + 1) != 0); /* more than the buffers hold: not promised */
+        g_grow_windows = 1; /* (the upload has recounted nothing, but armed the lists) */
+        int done = 0;
+        while (done < n_moves) {
+            const int w_now = std::min(std::min(ig_batch_max_width(c, max_c), w0), n_moves - done);
+            CHECK(w_now >= 1 && ig_batch_score(c, done, w_now, 0, w_now) == 0);
+            int32_t got = 0;
+            CHECK(ig_batch_commit(c, done, w_now, &got) == 0);
+            done += got;
+        }
+        CHECK(ig_batch_results(c, n_moves, res.data()) == 0 && seen(h) == 0);
+    }
+    for (int chains = 0; chains < 2; chains++) { /* a nuisance run: the plain way, and with chains where the decide model lets them through */
+        CHECK(ig_set_nuis_hist(2) == 0);
+        CHECK(arm(h) == 0 && ig_nuis_run_begin(c, n_moves, frags.data(), cands.data(), max_c) == 0);
+        for (int i = 0; i < n_moves;) {
+            if (chains && i > 0 && (i & 3) == 0) {
+                const int K = std::min(n_moves - i, 6);
+                std::vector<float> pt_(8 * (size_t)K);
+                std::vector<double> uu(K, 0.5), tt(K, 1.0);
+                for (int k = 0; k < K; k++) memcpy(&pt_[8 * (size_t)k], p8, 8 * sizeof(float));
+                int32_t nd = -1, why = -1;
+                CHECK(ig_nuis_chain_begin(c, i, K, pt_.data(), uu.data(), tt.data(), 1.8f) == 0 && ig_nuis_chain_end(c, &nd, &why) == 0);
+                i += nd;
+                if (i >= n_moves) break;
+            }
+            int32_t acc = -1;
+            double nzt, zt;
+            CHECK(ig_nuis_step_begin(c, i, p8, 1.8f) == 0);
+            CHECK(ig_nuis_step_next(c, 1.0, (rnd() % 1000 + 1) / 1001.0, nullptr, nullptr, 1.8f, i + 1 < n_moves, &one, &nzt, &zt, &acc) == 0);
+            if (acc == 2 && (rnd() & 1)) CHECK(ig_nuis_accept(c) == 0);
+            i++;
+        }
+        CHECK(ig_batch_results(c, n_moves, res.data()) == 0 && seen(h) == 0);
+    }
+    std::fprintf(stderr, "[harness]   slot budget: %d slots made, at least %d held, fewer behind a regrowth in %d of 7 callers\n", capW, min_held, shrunk);
+    CHECK(min_held < capW);             /* the budget bound */
+    CHECK(shrunk > 0 || pr.N <= 256);   /* ... and (genomes longer than the floor of the strides) bound harder behind a regrowth */
+    int32_t held = 0;
+    CHECK(ig_debug_window_budget(c, 0.0, &held) == 0 && c->window_budget == 64e9 && held == capW);
+    return 0;
+}
+
 int main()
 {
     setenv("IG_NUIS_SCREEN_NOCHECK", "1", 1); /* the models' screened and exact sums are unrelated numbers */
@@ -500,31 +643,9 @@ int main()
 
             // ---- the draw inside the call: jump distributions in the library, numpy's MT19937 state in and out, a drawing thread
             {
-                std::vector<int64_t> indptr(pr.N + 1, 0);
-                std::vector<int32_t> xk;
-                std::vector<float> pk;
                 const int nn = std::min(max_c, std::max(1, pr.N - 1));
-                for (int f = 0; f < pr.N; f++) {
-                    /* bins without a hetero contact draw uniformly (CL:3124) -- possibly the focal bin itself, which is dropped: with one
-                     * neighbour asked for that can leave an empty list, a refused move (quirk Q13); not what this block is after */
-                    const int deg = (f % 7 == 0 && nn > 2) ? 0 : 1 + (int)(rnd() % 12);
-                    float tot = 0;
-                    const size_t at = pk.size();
-                    for (int q = 0; q < deg; q++) {
-                        int32_t b = (int32_t)(rnd() % (uint32_t)pr.N);
-                        if (b == f) b = (b + 1) % pr.N;
-                        bool dup = false;
-                        for (size_t e = at; e < xk.size(); e++) dup |= xk[e] == b;
-                        if (dup) continue;
-                        xk.push_back(b);
-                        pk.push_back(1.0f + (float)(rnd() % 9));
-                        tot += pk.back();
-                    }
-                    for (size_t e = at; e < pk.size(); e++) pk[e] /= tot;
-                    indptr[f + 1] = (int64_t)xk.size();
-                }
-                ig_neighbours* nb = nullptr;
-                CHECK(ig_neighbours_create(indptr.data(), xk.data(), pk.data(), pr.N, nullptr, 0, &nb) == 0 && nb);
+                ig_neighbours* nb = make_neighbours(pr, nn);
+                CHECK(nb);
                 std::vector<uint32_t> key(624);
                 for (auto& k : key) k = rnd();
                 int32_t pos = 624;
@@ -676,6 +797,7 @@ int main()
             }
             g_diff_mode = 0;
         }
+        if (budget_block(c, pr, p8)) return 1;
         CHECK(ig_bomb(c, nullptr) == 0);
         double d;
         CHECK(ig_genome_distance(c, &d) == 0);

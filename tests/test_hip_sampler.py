@@ -408,6 +408,89 @@ def test_slice_pool_overflow_on_the_one_move_path(monkeypatch):
     assert b["retries_step"] > 0 and b["retries_w1"] > 0 and b["retries_sharded"] > 0 and b["retries_nuis"] > 0
 
 
+@pytest.mark.parametrize("way_name,window", [("plain", 48), ("plain", 0), ("nuisance", 48), ("runner", 48)])
+def test_a_small_window_budget_changes_widths_not_results(way_name, window):
+    """ig_debug_window_budget: the bytes the per-window arrays may take.  `small` from a bombed start -- the smallest config whose
+    window strides regrow during a run (at `tiny` their 256 / 768 floors are the genome already) -- in calls of 250 moves until, under
+    the default budget, the strides have regrown twice on their own (contigs of one bin merge into a few dozen; at most 8 000 moves).
+    Under the default budget the buffers hold every slot they were made for; under one that holds 12 slots at the first strides (fewer
+    than the default width of 24) fewer fit behind every regrowth, and still at least 2 at the end.  Every launch takes its cap from
+    the slots held, so the same moves give the same records and the same genome, byte for byte, four ways (the cases): the window rule,
+    plain batches (ig_set_window(0)), a run of (move, nuisance step) pairs, and multi_gpu.BatchRunner on one device sized from
+    batch_max_width; the maintained sums equal a from-scratch pass."""
+    from instagraal_amd import hip_lib, synth
+    from instagraal_amd.multi_gpu import BatchRunner
+    from instagraal_amd.sampler import sampler as hip_sampler
+
+    prob = synth.make_problem(*synth.CONFIGS["small"])
+    np.random.seed(6)
+    per_call, most_calls = 250, 32
+    frags = np.resize(np.random.permutation(prob.n_frags), per_call * most_calls).astype(np.int32)
+
+    def fresh():
+        s = hip_sampler(**prob.sampler_kwargs(), device_id=0)
+        s.set_param_simu(prob.params)
+        s.bins = np.arange(1.0, 60.0, 1.0)
+        s.eval_likelihood_init()
+        np.random.seed(5)
+        s.bomb_the_genome()
+        return s
+
+    def plain(s, fr):
+        return s.ctx.step_batch(fr, s.draw_candidates(fr, 5)).tobytes()
+
+    def nuisance(s, fr):
+        res, tuples = s.step_sampler_nuisance_batch(fr, 5, s.dt, 0, per_call * most_calls)
+        return res.tobytes() + repr(tuples).encode()
+
+    def runner(s, fr):
+        return BatchRunner(s.ctx, 0, 1, width=24).run(fr, s.draw_candidates(fr, 5)).tobytes()
+
+    s = fresh()  # the bytes of a slot at the first strides
+    plain(s, frags[:2])
+    held0 = s.ctx.debug_window_budget(0)
+    per_slot = int(s.ctx.scratch_bytes()[0]) // held0
+    s.free_gpu()
+    small_budget = 12.5 * per_slot
+
+    def run(way, window, budget, n_calls):
+        """n_calls = 0: until the strides have regrown twice -> (records per call, final state, slots reported behind the first call and
+        behind the last, bytes of the per-window arrays behind every call)"""
+        hip_lib.set_window(window)
+        s = fresh()
+        s.ctx.debug_window_budget(budget)  # (no move buffers yet: the budget is set, the first call sizes them under it)
+        out, window_bytes, first = [], [], 0
+        while len(out) < (n_calls or most_calls):
+            out.append(way(s, frags[len(out) * per_call:(len(out) + 1) * per_call]))
+            if len(out) == 1:
+                first = s.ctx.debug_window_budget(budget)
+            window_bytes.append(int(s.ctx.scratch_bytes()[0]))  # (default budget: slots made x bytes of a slot -- it follows the strides)
+            if budget:  # ig_scratch_bytes counts the slots held, not the slots asked for
+                assert per_slot <= window_bytes[-1] <= budget, (window_bytes, budget)
+            if not n_calls and len(set(window_bytes)) >= 3:
+                break
+        last = s.ctx.debug_window_budget(budget)
+        sums, _ = s.ctx.debug_globals()
+        _, _, limbs = s.ctx.full_likelihood(0)
+        assert [int(x) for x in sums[:5]] == [int(x) for x in limbs[:5]], (way.__name__, window, budget)
+        state = s.gpu_vect_frags.copy_from_gpu().soa17().tobytes()
+        s.free_gpu()
+        return out, state, (first, last), window_bytes
+
+    way = {"plain": plain, "nuisance": nuisance, "runner": runner}[way_name]
+    try:
+        want, want_state, slots_d, bytes_d = run(way, window, 0, 0)
+        got, got_state, slots_s, bytes_s = run(way, window, small_budget, len(want))
+        print(way_name, window, "calls", len(want), "slots held (first, last): default budget", slots_d, "small budget", slots_s,
+              "bytes of the per-window arrays: default", sorted(set(bytes_d)), "small", bytes_s)
+        assert got == want and got_state == want_state
+        assert len(set(bytes_d)) >= 3 and sorted(bytes_d) == bytes_d, bytes_d  # the strides regrew at least twice, on their own
+        assert min(slots_d) >= 24, slots_d  # the default budget holds what the buffers were made for
+        assert 2 <= slots_s[1] < slots_s[0] < 24, slots_s  # the small one fewer than the default width, fewer still at the end, never one
+    finally:
+        hip_lib.set_window(48)
+
+
 def test_wide_slice_entries_equal_packed(monkeypatch):
     """slice entries are packed in 8 bytes when M < 2^20 and the counts are below 2^24, else kept as three ints: same results"""
     from instagraal_amd import synth
