@@ -475,6 +475,13 @@ int ig_debug_nuis_hist_check(ig_ctx* ctx, int64_t* mismatches);
  * move of a two-tier batch takes that path (0 = off) -- and how often a handle has taken it */
 int ig_debug_set_zero_inject(int every);
 int ig_debug_zero_fallbacks(ig_ctx* ctx, int64_t* fallbacks);
+/* tests: the census of the decide rounds (k_decide_commit_par).  With the switch on (process-wide, default off) every round
+ * adds one to the counter of the way it ended; out16 = {launches, rounds, moves kept, all four kept, end of the batch behind four
+ * moves / behind fewer, cut behind a state-changing move, cut in front of a move decided under other flags, conflict / pool / grid
+ * stop at position 0 / later, zero-score stop at 0 / later, pending windowed winner at 0 / later, launches that resumed a batch,
+ * rounds none of these describes (always 0)}; clear = 1 zeroes the handle's counters behind the read.  Results do not depend on it. */
+int ig_debug_set_round_census(int on);
+int ig_debug_round_census(ig_ctx* ctx, int32_t out16[16], int32_t clear);
 /* tests: moves of the one-move path (ig_step, ig_score_move, ig_apply, ig_step_begin, ig_step_batch at width 1, ig_nuis_begin) whose
  * lists did not fit the slice pool and were repeated with a larger one -- the counterpart of the batch path's re-run slots
  * (replaces nothing in the reference: its sort buffers are sized for the whole matrix, CL:1009-1069) */

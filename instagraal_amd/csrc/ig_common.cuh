@@ -106,6 +106,27 @@ struct Glob {
      * its own per candidate in the focal contig and per candidate of another contig would have walked (k_offsets) */
     long long slice_walked, slice_walked_per_cand;
     int dbg[8]; /* what raised Glob.error (diagnostics: printed with a consistency failure) */
+    int census[16]; /* decide_rounds: how its rounds ended (IG_RC_*; counted only under ig_debug_set_round_census, read by ig_debug_round_census) */
+};
+
+/* Glob.census: one class per round of decide_rounds, in the order of precedence of its scan */
+enum {
+    IG_RC_LAUNCHES = 0, /* launches of k_decide_commit_par */
+    IG_RC_ROUNDS,       /* rounds: the sum of the twelve classes below */
+    IG_RC_COMMITTED,    /* moves the rounds kept (the sum of np) */
+    IG_RC_FULL,         /* all DPAR moves kept, the chain goes on */
+    IG_RC_TAIL_FULL,    /* the end of the batch, behind a round of DPAR moves */
+    IG_RC_TAIL_SHORT,   /* ... behind a round of fewer */
+    IG_RC_CHANGED,      /* behind a state-changing move, moves left undecided */
+    IG_RC_FLAGS,        /* in front of a move decided under flags that differ where it looks */
+    IG_RC_STOP1_FIRST,  /* a conflict, a pool, the grid: at position 0 */
+    IG_RC_STOP1_MID,    /* ... behind kept moves */
+    IG_RC_STOP3_FIRST,  /* a score of exactly 0.0 */
+    IG_RC_STOP3_MID,
+    IG_RC_PEND_FIRST,   /* a pending windowed winner */
+    IG_RC_PEND_MID,
+    IG_RC_RESUMED,      /* launches with w_start > 0 */
+    IG_RC_UNCLASSED     /* a round none of the above describes: there is none (the tests hold it to 0) */
 };
 
 /* one move slot of a batch (W = 1: the move in flight) */

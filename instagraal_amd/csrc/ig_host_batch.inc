@@ -437,9 +437,11 @@ static int validate_move(ig_ctx* c, int frag_a, const int32_t* cands, int C)
 }
 
 static int g_zero_inject = 0; /* ig_debug_set_zero_inject: the decide step treats every n-th move of a two-tier batch as one with a score of exactly 0.0 */
+static int g_round_census = 0; /* ig_debug_set_round_census: decide_rounds counts how each of its rounds ended (Glob.census) */
 
-/* contender-only records (two-tier scoring): the decide step checks for scores of exactly 0.0 (decide_body, stop code 3) */
-static int decide_zcheck(const ig_ctx* c) { return (c->own_screened == 1 ? 1 : 0) | (std::max(g_zero_inject, 0) << 8); }
+/* bit 0: contender-only records (two-tier scoring): the decide step checks for scores of exactly 0.0 (decide_body, stop code 3); bit 1: the
+ * census of decide_rounds; bits 8 and up: the injection period */
+static int decide_zcheck(const ig_ctx* c) { return (c->own_screened == 1 ? 1 : 0) | (g_round_census ? 2 : 0) | (std::max(g_zero_inject, 0) << 8); }
 
 /* decide and apply in ONE launch (k_decide_commit: seven waves work behind the decide wave)?  0: no, 1: where that pays, 2: IG_FUSED_COMMIT=2
  * says always (and keeps decide_body's one wave: the tests compare all three; =0: never).  It pays for plain batches of moves on windows that

@@ -306,6 +306,24 @@ extern "C" int ig_debug_zero_fallbacks(ig_ctx* c, int64_t* fallbacks)
     return 0;
 }
 
+/* the census of decide_rounds (k_decide_commit_par): with the switch on, every round adds one to the counter of the way it ended
+ * (Glob.census, IG_RC_*: ig_common.cuh); off (default) the kernel tests one bit per round and counts nothing.  clear = 1 zeroes the
+ * handle's counters behind the read. */
+extern "C" int ig_debug_set_round_census(int on)
+{
+    g_round_census = on ? 1 : 0;
+    return 0;
+}
+extern "C" int ig_debug_round_census(ig_ctx* c, int32_t* out16, int32_t clear)
+{
+    IG_JOIN(c);
+    HIPCK(hipSetDevice(c->device));
+    HIPCK(hipStreamSynchronize(c->stream));
+    HIPCK(hipMemcpy(out16, c->glob->census, 16 * sizeof(int), hipMemcpyDeviceToHost));
+    if (clear) HIPCK(memset_now(c->glob->census, 0, 16 * sizeof(int)));
+    return 0;
+}
+
 extern "C" int ig_debug_set_tail_quirk(int on)
 {
     g_tail_quirk = on;

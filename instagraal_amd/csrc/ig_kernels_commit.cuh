@@ -1498,6 +1498,10 @@ __device__ __forceinline__ void decide_rounds(Glob* g, MoveBuf mb, ig_move_resul
             ps->stop_overflow = 0;
             ps->n_cand = 0;
             ps->n_predicted = 0;
+            if (zcheck & 2) { /* the census of round endings (ig_debug_set_round_census) */
+                atomicAdd(&g->census[IG_RC_LAUNCHES], 1);
+                if (w_start > 0) atomicAdd(&g->census[IG_RC_RESUMED], 1);
+            }
         }
     }
     struct MoveData {
@@ -1757,6 +1761,19 @@ __device__ __forceinline__ void decide_rounds(Glob* g, MoveBuf mb, ig_move_resul
                     if (ps->changes[wl]) break;
                 }
                 if (!f && base + np >= W) f = true;
+            }
+            /* the census (ig_debug_set_round_census; off: this one test): how the round ended, in the scan's order of precedence, from
+             * what the scan left -- a prefix that ends early without a stop ends behind its last move where that one changes the
+             * state, else in front of a move decided under other flags (no wave writes `changes` between the two barriers) */
+            if ((zcheck & 2) && dwv == 0 && lane == 0) {
+                int cls = IG_RC_UNCLASSED;
+                if (stop_at >= 0) cls = (f_pend >= 0 ? IG_RC_PEND_FIRST : f_code == 3 ? IG_RC_STOP3_FIRST : IG_RC_STOP1_FIRST) + (stop_at > base ? 1 : 0);
+                else if (f) cls = cnt == DPAR ? IG_RC_TAIL_FULL : IG_RC_TAIL_SHORT;
+                else if (np == cnt) cls = IG_RC_FULL;
+                else if (np > 0) cls = ps->changes[base + np - 1] ? IG_RC_CHANGED : IG_RC_FLAGS;
+                atomicAdd(&g->census[IG_RC_ROUNDS], 1);
+                atomicAdd(&g->census[IG_RC_COMMITTED], np);
+                atomicAdd(&g->census[cls], 1);
             }
             const bool mine_committed = active && w < base + np;
             if (mine_committed) { /* this wave's NEXT move enters the window: the flags it leaves by default -- unless a block insert of another

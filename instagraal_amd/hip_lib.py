@@ -325,6 +325,16 @@ def debug_set_zero_inject(every):
     _ck(lib().ig_debug_set_zero_inject(C.c_int(int(every))))
 
 
+ROUND_CENSUS = ("launches", "rounds", "committed", "full", "tail_full", "tail_short", "changed", "flags", "stop1_first", "stop1_mid",
+                "stop3_first", "stop3_mid", "pend_first", "pend_mid", "resumed", "unclassed")  # IG_RC_* (csrc/ig_common.cuh)
+ROUND_CLASSES = ROUND_CENSUS[3:14] + ROUND_CENSUS[15:]  # one of them per round
+
+
+def debug_set_round_census(on):
+    """tests: the decide rounds (k_decide_commit_par) count how each round ended (``Context.debug_round_census``); off by default"""
+    _ck(lib().ig_debug_set_round_census(C.c_int(int(bool(on)))))
+
+
 def debug_set_full_hist(on):
     """from-scratch pass over all contacts: tiles of trans pairs only from their count histograms (default) or contact by
     contact -- same exact sums (tests)"""
@@ -641,6 +651,13 @@ class Context:
         n = C.c_int64()
         _ck(lib().ig_debug_zero_fallbacks(self._h, C.byref(n)))
         return int(n.value)
+
+    def debug_round_census(self, clear=False):
+        """how the decide rounds of this handle ended since the census was switched on (``debug_set_round_census``) -> dict over
+        ROUND_CENSUS; counts depend on timing, the identities between them do not"""
+        o = np.zeros(16, np.int32)
+        _ck(lib().ig_debug_round_census(self._h, _p(o), C.c_int32(int(bool(clear)))))
+        return dict(zip(ROUND_CENSUS, (int(x) for x in o)))
 
     def debug_pool_retries(self):
         """moves of the one-move path repeated with a larger slice pool (their lists did not fit)"""

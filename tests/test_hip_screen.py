@@ -85,10 +85,11 @@ def test_screening_with_large_counts_and_other_parameters(monkeypatch):
     np.random.seed(5)
     frags = np.resize(np.random.permutation(prob.n_frags), 300).astype(np.int32)
     for params in (prob.params, dict(prob.params, slope=0.0), dict(prob.params, slope=-0.7, v_inter=2e-4)):
-        prob.params = params
-        exact, _, _ = _run(prob, frags, 9, {"IG_SCREEN": "0"}, monkeypatch)
-        verified, stats, _ = _run(prob, frags, 9, {"IG_SCREEN_VERIFY": "1"}, monkeypatch)
-        screened, _, _ = _run(prob, frags, 9, {}, monkeypatch)
+        run = copy.copy(prob)  # (a problem object of its own per parameter set: nothing another test holds is written)
+        run.params = dict(params)
+        exact, _, _ = _run(run, frags, 9, {"IG_SCREEN": "0"}, monkeypatch)
+        verified, stats, _ = _run(run, frags, 9, {"IG_SCREEN_VERIFY": "1"}, monkeypatch)
+        screened, _, _ = _run(run, frags, 9, {}, monkeypatch)
         assert verified == exact and screened == exact
         assert stats[0] < 0.5
 
@@ -99,9 +100,11 @@ def test_screening_with_a_table_longer_than_its_staged_copy(cfg, n_moves, monkey
     Staged windows hold no rank distance beyond the copy (the two-columns-per-pass loop serves them as before); unstaged ones
     (bigctg: windows of thousands of sub-fragments) read their far pairs' entries from the table itself -- neither voids a
     column's bound any more: the exact kernel keeps to the contenders"""
+    import copy
+
     from instagraal_amd import synth
 
-    prob = synth.make_problem(*synth.CONFIGS[cfg])
+    prob = copy.copy(synth.make_problem(*synth.CONFIGS[cfg]))  # (the session may cache the problem object: its parameters stay what they were)
     prob.params = dict(prob.params, slope=-0.6, d_max=2.5e6)
     np.random.seed(12)
     frags = np.resize(np.random.permutation(prob.n_frags), n_moves).astype(np.int32)
@@ -134,10 +137,12 @@ def test_screening_at_the_settled_parameters(monkeypatch):
     where a default run spends 95 of its 100 cycles): the P_z table longer than its staged copy, and a ring pair's term at the
     contract's clamp (-2^20: 3e6 contacts expected per pair) -- the ring columns are ruled out by their clamped upper bound instead
     of going through the exact kernel's general loop (they were half of the exact tier's columns and nine tenths of its time)"""
+    import copy
+
     from instagraal_amd import synth
 
-    prob = synth.make_problem(*synth.CONFIGS["cfg3"])
-    prob.params = synth.settled_params(prob.params)
+    prob = copy.copy(synth.make_problem(*synth.CONFIGS["cfg3"]))  # (cached per session by tests/conftest.py: the later cfg3 tests read its own parameters)
+    prob.params = dict(synth.settled_params(prob.params))
     np.random.seed(2)
     frags = np.resize(np.random.permutation(prob.n_frags), 400).astype(np.int32)
     exact, _, _ = _run(prob, frags, 3, {"IG_SCREEN": "0"}, monkeypatch, coo=True)
