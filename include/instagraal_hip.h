@@ -682,6 +682,27 @@ int ig_debug_zoom_fetch(ig_ctx* ctx, int64_t* rowptr, int64_t n_rowptr, int32_t*
  * around each pass: ms_n[n][6] = {segment starts, words, sort short, sort lds, sort long, reduce}.  The snapshot is read only and stays
  * as it is; *checksum (may be NULL): the rows, columns and counts of the last repeat, each word weighted by its place */
 int ig_debug_zoom_time(ig_ctx* ctx, const int32_t* coarse_of_unit, int64_t n_units, int64_t n_coarse, int32_t n, float* ms_n, int64_t* checksum);
+
+/* ---- segment placement support: where the contacts say a run of bins belongs, and which way round (the rule:
+ * instagraal_amd/segment_placement.py).  The guests are the n_seg segments [seg_first[i], seg_last[i]] of positions of
+ * the genome order (ascending, disjoint, each inside one placed contig; they need not cover the order); each gets what
+ * ig_placement_support gives a bin -- home, the best site, the runner-up, the segment itself taken out of the order -- and at each of
+ * the three sites the four sums HL, HR, TL, TR of its contacts by the arm of the segment they touch (head, tail: its outermost
+ * min(n / 2, window) positions) and the part of the site's window the other end lies in (left, right).  The device reproduces the
+ * rule's arrays byte for byte, whatever the form of the scan (ig_debug_placement_support_form holds here too: it is the same kernel).
+ * ints: 12 arrays of n_seg int32 -- status (0 guest, 2 on a ring), contig, offset, n_positions, home_hosts, best_contig, best_offset,
+ * best_hosts, second_contig, second_offset, second_hosts, arm --; longs: 6 arrays of n_seg int64 -- home_left, home_right, best_left,
+ * best_right, second_left, second_right --; quadrants: [n_seg][3][4], the sites home, best, second; scalars: unplaced_observed,
+ * ring_observed, within_segment_observed, counted_observed, uncounted_observed, entries, n_contigs, n_guests, n_placed.  The arrays may
+ * be NULL with n_seg == 0.  A call that fails leaves the outputs untouched and the handle usable; nothing stays on the device.  Needs the
+ * sub-fragment table, the contacts and a state, all contacts on one handle, and no nuisance step or chain in flight. */
+int ig_segment_placement(ig_ctx* ctx, int32_t window, int32_t min_hosts, int32_t n_seg, const int32_t* seg_first, const int32_t* seg_last, int32_t* ints,
+                         int64_t* longs, int64_t* quadrants, int64_t scalars[9]);
+/* the call n times with hipEvents around each pass: ms_n[n][11] = {records, count, rows, scatter, sort short, sort lds, sort long, reduce,
+ * prefix, scan, quadrants}; *checksum (may be NULL): every output word of the last call -- ints, longs, quadrants, scalars -- weighted by
+ * its place */
+int ig_debug_segment_placement_time(ig_ctx* ctx, int32_t window, int32_t min_hosts, int32_t n_seg, const int32_t* seg_first, const int32_t* seg_last, int32_t n,
+                                    float* ms_n, int64_t* checksum);
 #ifdef __cplusplus
 }
 #endif

@@ -559,6 +559,30 @@ struct GapBuf {
     size_t cap_words = 0;
 };
 
+/* segment placement support (ig_kernels_segplace.cuh): every buffer of the feature, freed by free_segplace_buffers
+ * (ig_host_segplace.inc) first thing and at the end of every call -- no snapshot stays on the device.  The form of the scan is the
+ * placement support's setting (PlaceBuf.form): it is the same kernel */
+struct SegPlaceBuf {
+    unsigned long long* head = nullptr;   /* [T + 1] the join support's heads ... */
+    unsigned long long* incl = nullptr;   /* [T + 1] ... their running sum */
+    unsigned long long* htot = nullptr;   /* that scan's chunk totals */
+    int4* rec = nullptr;                  /* [M] ... and records: (depth, depth, run index, position) per sub-fragment */
+    struct JoinEnd* ends = nullptr;       /* [K] first position and positions per linear contig */
+    int *first = nullptr, *last = nullptr; /* [n_seg] the caller's list */
+    int* seg_of = nullptr;                /* [T] the segment of every position, -1: none */
+    int4* recs = nullptr;                 /* [n_seg] (first position, positions, run index or JOIN_RING, 0) per segment */
+    int* err = nullptr;                   /* 1 word: k_segplace_records found the list malformed */
+    unsigned long long* sc = nullptr;     /* SEGPLACE_NS scalars of the passes over the contacts */
+    RowBuf rows;                          /* n_seg rows of summed entries: rowptr, out_col (positions), out_cnt (counts) */
+    unsigned long long* pre = nullptr;    /* [n_summed + 1] the exclusive prefix sums of the counts */
+    unsigned long long* ptot = nullptr;   /* that scan's chunk totals */
+    int* out_i = nullptr;                 /* [SEGPLACE_NI][n_seg] */
+    long long* out_l = nullptr;           /* [SEGPLACE_NL][n_seg] */
+    int4* win = nullptr;                  /* [n_seg][3] (lo, mid, hi, 0): the sites as bounds in the original positions */
+    unsigned long long* quad = nullptr;   /* [n_seg][3][4] HL, HR, TL, TR at home, best, second */
+    long long forms[8] = {0, 0, 0, 0, 0, 0, 0, 0}; /* the last call's LIFT_C_* words */
+};
+
 struct ig_ctx {
     int device;
     hipStream_t stream;
@@ -672,6 +696,7 @@ struct ig_ctx {
     BalBuf bal;
     OrientBuf orient;
     GapBuf gap;
+    SegPlaceBuf segplace;
     DebugRows debug_rows;
     DebugRows debug_zoom; /* the last ig_debug_zoom_coarsen's result (ig_debug_zoom_fetch) */
     int* batch_out; /* committed moves, pending slot, (unused), candidates, predicted deltas used, contigs */

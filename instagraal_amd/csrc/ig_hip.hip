@@ -69,6 +69,7 @@
 #include "ig_kernels_bal.cuh"
 #include "ig_kernels_gap.cuh"
 #include "ig_kernels_zoom.cuh"
+#include "ig_kernels_segplace.cuh"
 
 /* ================================================================== host side (one translation unit, eighteen parts) */
 #include "ig_host_core.inc"
@@ -86,6 +87,7 @@
 #include "ig_host_bal.inc"
 #include "ig_host_gap.inc"
 #include "ig_host_zoom.inc"
+#include "ig_host_segplace.inc"
 #include "ig_host_batch.inc"
 #include "ig_host_nuis.inc"
 #include "ig_host_debug.inc"

@@ -18,8 +18,8 @@ SRC = os.path.join(HERE, "csrc", "ig_hip.hip")
 SRC_HOST = os.path.join(HERE, "csrc", "ig_draw.cpp")  # host-only part: the candidate draw
 DEPS = [SRC, SRC_HOST] + [os.path.join(HERE, "csrc", f) for f in ("ig_ops.cuh", "ig_common.cuh", "ig_model.cuh", "ig_kernels_setup.cuh",
                                                           "ig_kernels_score.cuh", "ig_kernels_screen.cuh", "ig_kernels_commit.cuh",
-                                                          "ig_kernels_nuis.cuh", "ig_kernels_wave.cuh", "ig_kernels_genome.cuh", "ig_kernels_rows.cuh", "ig_kernels_map.cuh", "ig_kernels_law.cuh", "ig_kernels_junc.cuh", "ig_kernels_lift.cuh", "ig_kernels_join.cuh", "ig_kernels_emap.cuh", "ig_kernels_place.cuh", "ig_kernels_orient.cuh", "ig_kernels_bal.cuh", "ig_kernels_gap.cuh", "ig_kernels_zoom.cuh", "ig_host_core.inc", "ig_host_upload.inc", "ig_host_genome.inc", "ig_host_rows.inc",
-                                                          "ig_host_map.inc", "ig_host_law.inc", "ig_host_junc.inc", "ig_host_lift.inc", "ig_host_join.inc", "ig_host_emap.inc", "ig_host_place.inc", "ig_host_orient.inc", "ig_host_bal.inc", "ig_host_gap.inc", "ig_host_zoom.inc",
+                                                          "ig_kernels_nuis.cuh", "ig_kernels_wave.cuh", "ig_kernels_genome.cuh", "ig_kernels_rows.cuh", "ig_kernels_map.cuh", "ig_kernels_law.cuh", "ig_kernels_junc.cuh", "ig_kernels_lift.cuh", "ig_kernels_join.cuh", "ig_kernels_emap.cuh", "ig_kernels_place.cuh", "ig_kernels_orient.cuh", "ig_kernels_bal.cuh", "ig_kernels_gap.cuh", "ig_kernels_zoom.cuh", "ig_kernels_segplace.cuh", "ig_host_core.inc", "ig_host_upload.inc", "ig_host_genome.inc", "ig_host_rows.inc",
+                                                          "ig_host_map.inc", "ig_host_law.inc", "ig_host_junc.inc", "ig_host_lift.inc", "ig_host_join.inc", "ig_host_emap.inc", "ig_host_place.inc", "ig_host_orient.inc", "ig_host_bal.inc", "ig_host_gap.inc", "ig_host_zoom.inc", "ig_host_segplace.inc",
                                                           "ig_host_batch.inc", "ig_host_nuis.inc", "ig_host_debug.inc")] + \
        [os.path.join(ROOT, "include", f) for f in ("ig_detmath.h", "ig_detmath_tables.h", "instagraal_hip.h")]
 
@@ -28,6 +28,7 @@ ASSEMBLY_CONTACTS_PASSES = ("count", "scan", "scatter", "sort_short", "sort_lds"
 JOIN_SUPPORT_PASSES = ("ends", "count", "scan", "scatter", "sort_short", "sort_lds", "sort_long", "reduce", "model")  # ig_debug_join_support_time
 PLACEMENT_SUPPORT_PASSES = ("records", "count", "rows", "scatter", "sort_short", "sort_lds", "sort_long", "reduce", "prefix", "scan")  # ig_debug_placement_support_time
 PLACEMENT_SUPPORT_FORMS = ("default", "thread", "wave")  # ig_debug_placement_support_form
+SEGMENT_PLACEMENT_PASSES = PLACEMENT_SUPPORT_PASSES + ("quadrants",)  # ig_debug_segment_placement_time
 ORIENTATION_SUPPORT_WAVE_PAIRS = 4096  # ORIENT_WAVE_PAIRS (csrc/ig_kernels_orient.cuh): 2 * pairs beyond this take a workgroup in the model pass
 ORIENTATION_SUPPORT_FORMS = {"observed": ("atomic", "combined"), "model": ("default", "wave", "workgroup")}  # ig_debug_orientation_support_time: pass -> forms
 GAP_SUPPORT_WAVE_TERMS = 8192  # GAP_WAVE_TERMS (csrc/ig_kernels_gap.cuh): pairs * gaps beyond this take a workgroup in the model pass
@@ -1181,6 +1182,49 @@ class Context:
         ck = C.c_int64()
         _ck(lib().ig_debug_placement_support_time(self._h, C.c_int32(int(window)), C.c_int32(int(window) if min_hosts is None else int(min_hosts)), C.c_int32(int(n)),
                                                   _p(ms), C.byref(ck)))
+        return ms, int(ck.value)
+
+    # ---- segment placement support: where the contacts say a run of bins belongs, and which way round (the rule: segment_placement.py)
+    @staticmethod
+    def _placement_segments(first, last):
+        f, l = np.asarray(first), np.asarray(last)
+        if f.ndim != 1 or f.shape != l.shape or not (np.issubdtype(f.dtype, np.integer) and np.issubdtype(l.dtype, np.integer)):
+            raise HipError("segment_placement: segment list: first and last are integer vectors of one length")
+        if f.size and (min(f.min(), l.min()) < -2 ** 31 or max(f.max(), l.max()) >= 2 ** 31):
+            raise HipError("segment_placement: segment list out of range")
+        return np.ascontiguousarray(f, np.int32), np.ascontiguousarray(l, np.int32)
+
+    def segment_placement(self, window, first, last, min_hosts=None):
+        """every segment [first[i], last[i]] of positions of a linear contig against every other site of the genome inside ``window``
+        positions, the segment itself taken out of the order, and the four sums by arm and part of the window at its home, its best
+        site and the runner-up -> dict: window, min_hosts, n_seg, first, last, the per-segment arrays of ``segment_placement.ARRAYS``
+        (int32 / int64 [n_seg]), ``quadrants`` (int64 [n_seg, 3, 4]) and the int64 scalars of ``segment_placement.SCALARS``.
+        Nothing stays on the device."""
+        from .segment_placement import INT_ARRAYS, LONG_ARRAYS, SCALARS
+
+        window = int(window)
+        min_hosts = window if min_hosts is None else int(min_hosts)
+        f, l = self._placement_segments(first, last)
+        n_seg = int(f.size)
+        ints = np.zeros((len(INT_ARRAYS), n_seg), np.int32)
+        longs = np.zeros((len(LONG_ARRAYS), n_seg), np.int64)
+        quad = np.zeros((n_seg, 3, 4), np.int64)
+        sc = np.zeros(len(SCALARS), np.int64)
+        _ck(lib().ig_segment_placement(self._h, C.c_int32(window), C.c_int32(min_hosts), C.c_int32(n_seg), _p(f), _p(l), _p(ints), _p(longs), _p(quad), _p(sc)))
+        out = dict(window=window, min_hosts=min_hosts, n_seg=n_seg, first=f.astype(np.int64), last=l.astype(np.int64), quadrants=quad)
+        out.update((k, ints[i].copy()) for i, k in enumerate(INT_ARRAYS))
+        out.update((k, longs[i].copy()) for i, k in enumerate(LONG_ARRAYS))
+        out.update((k, int(v)) for k, v in zip(SCALARS, sc))
+        return out
+
+    def debug_segment_placement_time(self, window, first, last, min_hosts=None, n=1):
+        """the call n times with hipEvents around each pass -> (ms [n, 11]: ``SEGMENT_PLACEMENT_PASSES``, checksum of every output word
+        of the last call)"""
+        f, l = self._placement_segments(first, last)
+        ms = np.zeros((int(n), len(SEGMENT_PLACEMENT_PASSES)), np.float32)
+        ck = C.c_int64()
+        _ck(lib().ig_debug_segment_placement_time(self._h, C.c_int32(int(window)), C.c_int32(int(window) if min_hosts is None else int(min_hosts)), C.c_int32(int(f.size)),
+                                                  _p(f), _p(l), C.c_int32(int(n)), _p(ms), C.byref(ck)))
         return ms, int(ck.value)
 
     # ---- balancing the contact map of the current genome (the rule: balance.py)

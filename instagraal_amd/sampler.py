@@ -1280,6 +1280,67 @@ class sampler:  # noqa: N801 - the reference's class name
         res = self.placement_support(window, window_kb, min_hosts) if result is None else result
         return ps.misplaced_bins(res, n, min_ratio)
 
+    # ------------------------------------------------------ segment placement
+    def segment_placement(self, level="block", segments=None, window=None, window_kb=None, min_hosts=None):
+        """Where the contacts say a run of bins belongs, and which way round (``ig_segment_placement``; the rule:
+        ``segment_placement.py``): placement support with a segment of the genome order for its guest -- a block carried along by
+        an early wrong insertion is invisible bin by bin, its interior finds the rest of the block at home.  ``level``: "block", the
+        maximal co-linear runs of bins of one initial contig (``orientation_support.block_segments``), "scaffold", one segment per
+        linear placed scaffold, or "bin", one per placed bin (placement support's own answer); ``segments=(first, last)``: the
+        caller's own intervals of positions, which override ``level``.  ``window``: in positions (default: placement support's,
+        64), or ``window_kb``; ``min_hosts``: the fewest positions a site's window must hold (default: the window).  -> the rule's
+        dict (the per-segment arrays of ``segment_placement.ARRAYS``, ``quadrants``, the scalars) plus ``level``, the densities
+        (``home_density``, ``best_density``, ``ratio``, ``second_ratio``), the orientation at each site (``keep``, ``flip``,
+        ``verdict``: [n_seg, 3] over home, best, second), the segments and sites for people (``first_bin``, ``last_bin``,
+        ``scaffold``, ``best_scaffold``, ``best_before``, ``best_after`` and the same of ``second``), ``first_position`` and
+        ``contig_positions`` per linear contig, and ``order``.  No reference counterpart."""
+        from . import join_support as js, orientation_support as osup, segment_placement as sp
+
+        if window is not None and window_kb is not None:
+            raise ValueError("segment_placement: window or window_kb, not both")
+        if window_kb is not None:
+            window = sp.window_from_kb(window_kb, self.mean_kb())
+        w = sp.check_window(sp.DEFAULT_WINDOW if window is None else window)
+        try:
+            mh = sp.check_min_hosts(min_hosts, w)
+        except ValueError as e:
+            raise ValueError(str(e).replace("placement support", sp.NAME)) from None
+        order = self.ctx.contact_map_order().astype(np.int64)
+        parent = self.np_sub_frags_2_frags["x"].astype(np.int64)
+        g = self.gpu_vect_frags.copy_from_gpu()
+        _, contig, stot, _, _ = self.ctx.debug_tables()
+        position = np.full(parent.size, -1, np.int64)
+        position[order] = np.arange(order.size)
+        _, start, length, run = js.linear_runs(stot, contig, position)
+        if segments is not None:
+            first, last = (np.asarray(a) for a in segments)
+            level = "custom"
+        elif level == "bin":
+            seg = osup.bin_segments(order, parent)
+            first, last = seg["first"], seg["last"]
+        elif level == "block":
+            seg = osup.block_segments(order, parent, g.id_c, g.ori, g.id_d, self.np_init_id_c, self.np_init_pos)
+            first, last = seg["first"], seg["last"]
+        elif level == "scaffold":
+            first, last = start.astype(np.int64), (start + length - 1).astype(np.int64)
+        else:
+            raise ValueError("segment_placement: level is 'block', 'scaffold' or 'bin' (got %r)" % (level,))
+        res = self.ctx.segment_placement(w, first, last, mh)
+        res["level"], res["order"] = level, order
+        res["first_position"], res["contig_positions"] = start.astype(np.int32), length.astype(np.int32)
+        res.update(sp.densities(res))
+        res.update(sp.orientation_at(res))
+        res.update(sp.sites_for_people(res, order, parent, g.id_c))
+        return res
+
+    def misplaced_segments(self, n=20, min_ratio=1.0, result=None, level="block", segments=None, window=None, window_kb=None, min_hosts=None):
+        """The ``n`` segments of ``segment_placement()`` whose contacts are denser somewhere else than at home by more than
+        ``min_ratio``, best first (``segment_placement.misplaced_segments``: inf first, ties by segment index)."""
+        from . import segment_placement as sp
+
+        res = self.segment_placement(level, segments, window, window_kb, min_hosts) if result is None else result
+        return sp.misplaced_segments(res, n, min_ratio)
+
     # ---------------------------------------------------- orientation support
     def orientation_support(self, level="bin", segments=None, window=None, window_kb=None, model=True):
         """Which segments of the current genome the contacts would reverse (``ig_orientation_support``; the rule:

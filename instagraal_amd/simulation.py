@@ -195,7 +195,7 @@ class instagraal_class:
 
     def full_em(self, n_cycles, n_neighbours, bomb, id_start_sample_param, save_matrix=False, save_law=False, save_junctions=False,
                 save_contacts=False, save_joins=False, save_residuals=False, save_placements=False, save_orientations=False, save_weights=False, save_gaps=False,
-                save_resolutions=False):  # IG:196-291
+                save_resolutions=False, save_segment_placements=False):  # IG:196-291
         sampler = self.simulation.sampler
         if bomb:
             sampler.bomb_the_genome()
@@ -262,6 +262,11 @@ class instagraal_class:
             from . import placement_support as psup
 
             psup.write_placements(self._out("placements.txt"), sampler.placement_support())
+        if save_segment_placements:  # (once, behind the last cycle, next to placements.txt: the blocks, then the scaffolds, the contacts would rather see elsewhere)
+            from . import segment_placement as spl
+
+            spl.write_segment_placements(self._out("segment_placements.txt"), sampler.segment_placement(level="block"), title="level=block")
+            spl.write_segment_placements(self._out("segment_placements.txt"), sampler.segment_placement(level="scaffold"), mode="a", title="level=scaffold")
         if save_weights:  # (once, behind the last cycle, beside placements.txt: the balancing weight of every bin of the final genome)
             from . import balance as bal
 
@@ -293,7 +298,7 @@ class instagraal_class:
 def run_instagraal(hic_folder, reference_fa, output_folder=None, level=4, cycles=100, coverage_std=1, neighborhood=5, device=0,
                    circular=False, bomb=False, pyramid_only=False, save_pickle=False, save_matrix=False, simple=False, save_law=False,
                    save_junctions=False, save_contacts=False, save_joins=False, save_residuals=False, save_placements=False,
-                   save_orientations=False, save_weights=False, save_gaps=False, save_resolutions=False):
+                   save_orientations=False, save_weights=False, save_gaps=False, save_resolutions=False, save_segment_placements=False):
     """IG:502-581 (defaults of cli/main.py: level 4, 100 cycles, 5 neighbours, 1 std).  The three trailing switches of the
     reference's signature (IG:512-514) are accepted: ``save_pickle`` dumps the run object to ``graal.pkl`` as the reference
     tries to (IG:589-594: a warning when it cannot be pickled -- device handles here, h5py handles there); ``save_matrix``
@@ -330,7 +335,10 @@ def run_instagraal(hic_folder, reference_fa, output_folder=None, level=4, cycles
     ``resolutions/<bp>/bins.bed``, ``pixels.tsv`` and ``chrom.sizes`` -- the contacts of the final genome in fixed bins of that many bp,
     a level whose bin size is a multiple of the one before it made from that level alone -- and ``scaffolds/`` with the scaffold by
     scaffold matrix; given together with ``save_weights``, ``weights.tsv`` of every level beside them (``sampler.write_zoom_levels``,
-    DESIGN 4.21)."""
+    DESIGN 4.21); ``save_segment_placements`` (an addition too) writes ``segment_placements.txt`` once, behind the last cycle, next to
+    ``placements.txt``: one line per segment -- the co-linear blocks first, the whole scaffolds behind them -- whose contacts are denser
+    around another site of the genome than around where it lies, with that site, the two densities, their ratio and the way round the
+    contacts would put it in there (``sampler.segment_placement``)."""
     import warnings
 
     if simple and not pyramid_only:
@@ -351,7 +359,8 @@ def run_instagraal(hic_folder, reference_fa, output_folder=None, level=4, cycles
         p2.simulation.level.S_o_A_frags["circ"] += 1
     p2.full_em(n_cycles=cycles, n_neighbours=neighborhood, bomb=bomb, id_start_sample_param=4, save_matrix=save_matrix, save_law=save_law,
                save_junctions=save_junctions, save_contacts=save_contacts, save_joins=save_joins, save_residuals=save_residuals, save_placements=save_placements,
-               save_orientations=save_orientations, save_weights=save_weights, save_gaps=save_gaps, save_resolutions=save_resolutions)
+               save_orientations=save_orientations, save_weights=save_weights, save_gaps=save_gaps, save_resolutions=save_resolutions,
+               save_segment_placements=save_segment_placements)
     if save_pickle:  # IG:589-594
         import pickle
 
