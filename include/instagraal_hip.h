@@ -446,6 +446,8 @@ int ig_debug_candidate_state(ig_ctx* ctx, int32_t c, int32_t slot, int32_t* soa1
 int ig_debug_last_sums(ig_ctx* ctx, int64_t* nz_hi, int64_t* nz_lo, int64_t* z_hi, int64_t* z_lo, int64_t* n_intra,
                        int64_t* ext_hi, int64_t* ext_lo, int64_t* n_slice, int32_t* n_uniq, int32_t* uniq);
 int ig_debug_tables(ig_ctx* ctx, float* dist, int32_t* id_c, float* s_tot, int32_t* pos, int32_t* len);
+/* the P_z table ig_set_params built for set `which` (0 or 1): *n its length, out[0 .. min(*n, cap)) its entries */
+int ig_debug_pz_table(ig_ctx* ctx, int32_t which, float* out, int32_t cap, int32_t* n);
 /* maintained exact sums {nz_hi, nz_lo, z_hi, z_lo, n_intra}; {n_contigs, next_cid, chosen c, k, slot, windowed} */
 int ig_debug_globals(ig_ctx* ctx, int64_t* sums5, int32_t* ints6);
 int ig_debug_dbg(ig_ctx* ctx, int32_t* out8, int32_t clear); /* Glob.dbg: the eight words a device-side consistency failure leaves (tuning builds: tick counters) */

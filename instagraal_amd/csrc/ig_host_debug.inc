@@ -182,6 +182,23 @@ extern "C" int ig_debug_tables(ig_ctx* c, float* dist, int32_t* id_c, float* s_t
     return 0;
 }
 
+/* the P_z table of parameter set `which` as ig_set_params left it (k_build_pz): *n its length, out[0 .. min(*n, cap)) its entries */
+extern "C" int ig_debug_pz_table(ig_ctx* c, int32_t which, float* out, int32_t cap, int32_t* n)
+{
+    IG_JOIN(c);
+    HIPCK(hipSetDevice(c->device));
+    if (which != 0 && which != 1) return fail("ig_debug_pz_table: which must be 0 or 1");
+    if (!n || cap < 0 || (cap > 0 && !out)) return fail("ig_debug_pz_table: NULL argument");
+    const float* tab = which == 0 ? c->pz_tab : c->pz_tab1;
+    const int len = which == 0 ? c->pz_n : c->pz_n1;
+    if (!tab) return fail("ig_debug_pz_table: no parameters were set for set %d", which);
+    HIPCK(hipStreamSynchronize(c->stream));
+    *n = len;
+    const int m = std::min(len, (int)cap);
+    if (m > 0) HIPCK(hipMemcpy(out, tab, (size_t)m * sizeof(float), hipMemcpyDeviceToHost));
+    return 0;
+}
+
 /* v_log_f32 / v_exp_f32 over their whole domain against the contract's double functions (the screening bound assumes
  * both below SCR_KL = SCR_KE = 4 in these units): out[0], out[1] as k_transcendental_error defines them */
 extern "C" int ig_debug_transcendental_error(ig_ctx* c, double out2[2])

@@ -1412,6 +1412,14 @@ class Context:
         _ck(lib().ig_debug_dbg(self._h, _p(o), C.c_int32(int(bool(clear)))))
         return o
 
+    def debug_pz_table(self, which=0):
+        """the P_z table set_params built for parameter set ``which``: pz[d] for every rank distance d below its length"""
+        out = np.zeros(4096, np.float32)
+        n = C.c_int32()
+        _ck(lib().ig_debug_pz_table(self._h, C.c_int32(int(which)), _p(out), C.c_int32(out.size), C.byref(n)))
+        assert 0 <= n.value <= out.size, n.value
+        return out[: n.value].copy()
+
     def debug_tables(self):
         M = self.M
         d = np.zeros(M, np.float32)

@@ -136,6 +136,7 @@ void igo_last_limbs(int64_t* hi, int64_t* lo, int n); /* n <= 24: limbs of the l
 void igo_eval_terms(const float* s, const float* s_tot, const int32_t* ob, int64_t n, const ig_params* P, float* ex,
                     float* ex_circ, double* term, int64_t* q);
 void igo_lgf_table(double* out15);
+void igo_detmath_probe(int fn, const double* x, int64_t n, double* out); /* 0 ig_log2_pos, 1 ig_exp2, 2 ig_log10 */
 
 #ifdef __cplusplus
 }

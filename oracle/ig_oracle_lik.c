@@ -72,6 +72,13 @@ void igo_lgf_table(double* out15)
 {
     for (int k = 0; k < 15; k++) out15[k] = ig_log10((double)factorial_det((float)k), ig_tab());
 }
+/* the contract's double functions on their own (tests/test_contract_precision_host.py): 0 ig_log2_pos (positive, finite, normal x),
+ * 1 ig_exp2, 2 ig_log10 */
+void igo_detmath_probe(int fn, const double* x, int64_t n, double* out)
+{
+    for (int64_t i = 0; i < n; i++)
+        out[i] = fn == 0 ? ig_log2_pos(x[i], ig_tab()) : fn == 1 ? ig_exp2(x[i], ig_tab()) : ig_log10(x[i], ig_tab());
+}
 static void lgf_init(void)
 {
     if (!g_lgf_ready) {

@@ -140,3 +140,11 @@ def lgf_table():
     out = np.zeros(15, np.float64)
     lib().igo_lgf_table(ptr(out))
     return out
+
+
+def detmath_probe(fn, x):
+    """the contract's double functions on their own: fn 0 ig_log2_pos (positive, finite, normal x), 1 ig_exp2, 2 ig_log10"""
+    x = np.ascontiguousarray(x, np.float64)
+    out = np.zeros(x.size, np.float64)
+    lib().igo_detmath_probe(C.c_int(int(fn)), ptr(x), C.c_int64(x.size), ptr(out))
+    return out
