@@ -705,6 +705,36 @@ int ig_segment_placement(ig_ctx* ctx, int32_t window, int32_t min_hosts, int32_t
  * its place */
 int ig_debug_segment_placement_time(ig_ctx* ctx, int32_t window, int32_t min_hosts, int32_t n_seg, const int32_t* seg_first, const int32_t* seg_last, int32_t n,
                                     float* ms_n, int64_t* checksum);
+
+/* ---- segment edits: the moves the block-level reports propose, scored exactly and applied (the rule: instagraal_amd/rearrange.py;
+ * DESIGN.md 4.23).  An edit is five int32: first_bin, last_bin, anchor, side, flip -- the bins of one linear contig from first_bin to
+ * last_bin (in the current order) are taken out, reversed with their ori negated if flip, and put back where they were (anchor -2),
+ * made a contig of their own (anchor -1) or inserted directly behind (side 0) or in front of (side 1) the bin anchor, a bin outside
+ * the segment in a linear contig.  status: 0 ok, 1 a bin out of range, 2 the two bins not in one contig or in the wrong order, 3 a
+ * ring, 4 the anchor inside the segment, 5 anchor, side or flip out of range.  The device reproduces the rule's states byte for byte.
+ * All three calls need the sub-fragment table, the contacts, a state and the parameters, all contacts on one handle, and no nuisance
+ * step or chain in flight. */
+/* The five exact sums of the genome every edit of edits[n_edits][5] would leave, limbs[n_edits][5] in the order of
+ * ig_full_likelihood's limbs5, with nz[n_edits] and z[n_edits] formed as that call forms them; an edit that is refused (status != 0)
+ * gets the sums of the current genome.  form 0 (the delta form): the maintained sums plus one pass over the contacts and one over the
+ * sub-fragments per chunk of up to 64 edits, terms evaluated only where a contig an edit touches is involved; form 1 (the whole form,
+ * the definition): the from-scratch passes on the tables of every edited genome.  Both give the same limbs.  Any n_edits: the list is
+ * worked off in chunks of 64 or fewer, as many as the free device memory holds (per edit: 44 N + 20 M bytes); when one edit does not
+ * fit the call fails before it allocates and names the bytes it needs.  Reads the current state and changes nothing a move reads.  The
+ * buffers are kept from call to call and freed by ig_destroy. */
+int ig_edit_score(ig_ctx* ctx, int32_t n_edits, const int32_t* edits, int32_t form, int32_t* status, int64_t* limbs, double* nz, double* z);
+/* tests: the state one edit would leave, soa17 in the order of ig_upload_state with the INTERNAL contig ids (a new contig: the next
+ * free id); nothing is committed.  A refused edit returns the current state. */
+int ig_edit_state(ig_ctx* ctx, const int32_t edit[5], int32_t* soa17, int32_t* status);
+/* Commits one edit: its dynamic arrays become the live state, a new contig uses up the next free id, the stale insert flags are
+ * cleared as ig_upload_state clears them, the moves scored ahead are dropped, and everything a move reads is rebuilt from the state
+ * (tables, maintained sums, genome distance).  The initial genome, the blacklist and the parameters stay.  limbs5 (may be NULL): the
+ * maintained sums behind the call.  A status other than 0 leaves everything as it was. */
+int ig_edit_apply(ig_ctx* ctx, const int32_t edit[5], int32_t* status, int64_t* limbs5);
+/* ig_edit_score n times with hipEvents around each pass, summed over the chunks: ms_n[n][6] = {plan, state, tables, delta, zero,
+ * whole} (the passes of the other form stay 0); *checksum (may be NULL): the statuses, then the limbs of the last call, each word
+ * weighted by its place: the two forms agree on it */
+int ig_debug_edit_time(ig_ctx* ctx, int32_t n_edits, const int32_t* edits, int32_t form, int32_t n, float* ms_n, int64_t* checksum);
 #ifdef __cplusplus
 }
 #endif

@@ -583,6 +583,21 @@ struct SegPlaceBuf {
     long long forms[8] = {0, 0, 0, 0, 0, 0, 0, 0}; /* the last call's LIFT_C_* words */
 };
 
+/* segment edits (ig_kernels_edit.cuh): the scratch states and tables of a chunk of edits, kept from call to call and grown to the
+ * largest chunk asked for (cap edits; the arrays sized for N and M); freed by free_edit_buffers (ig_host_edit.inc) */
+struct EditBuf {
+    int* edits = nullptr;               /* [cap][5] the caller's list, one chunk */
+    struct EditPlan* plan = nullptr;    /* [cap] */
+    int* dyn = nullptr;                 /* [cap][NDYN][N] the dynamic arrays of every edited state */
+    float *dist = nullptr, *stot = nullptr; /* [cap][M] the tables of every edited state ... */
+    int* len = nullptr;                 /* [cap][M] */
+    int2* cp = nullptr;                 /* [cap][M] */
+    unsigned long long* mask = nullptr; /* [mask_cap] per internal contig id: the edits of the chunk that touch it */
+    long long* acc = nullptr;           /* [EDIT_CHUNK][EDIT_ACC] the delta form's sums */
+    int cap = 0, N = 0, M = 0;
+    size_t mask_cap = 0;
+};
+
 struct ig_ctx {
     int device;
     hipStream_t stream;
@@ -697,6 +712,7 @@ struct ig_ctx {
     OrientBuf orient;
     GapBuf gap;
     SegPlaceBuf segplace;
+    EditBuf edit;
     DebugRows debug_rows;
     DebugRows debug_zoom; /* the last ig_debug_zoom_coarsen's result (ig_debug_zoom_fetch) */
     int* batch_out; /* committed moves, pending slot, (unused), candidates, predicted deltas used, contigs */

@@ -478,6 +478,19 @@ extern "C" int ig_get_valid_insert(ig_ctx* c, int32_t out12[12])
     return 0;
 }
 
+/* nz and z of the five normalised limbs {nz hi, nz lo, z hi, z lo, intra pairs} (either may be NULL): what ig_full_likelihood returns
+ * and what ig_edit_score returns for an edited genome (ig_host_edit.inc) -- one statement, so the two are the same doubles */
+static void likelihood_of_limbs(const long long h[5], double n_tot_pxl, float v_inter, double* nz, double* z)
+{
+    if (nz) *nz = ig_acc_to_double(h[0], h[1]);
+    if (z) { /* CL:755-759 with the float log_e of the kernels replaced by the host's double constant */
+        const double log_e = 0.43429448190325182;
+        const double val_intra = ig_acc_to_double(h[2], h[3]) * log_e;
+        const double val_inter = log_e * (n_tot_pxl - (double)h[4]) * -1.0 * (double)v_inter;
+        *z = val_intra + val_inter;
+    }
+}
+
 extern "C" int ig_full_likelihood(ig_ctx* c, int which, int use_prev, double* nz, double* z, int64_t* limbs5)
 {
     IG_JOIN(c);
@@ -496,18 +509,12 @@ extern "C" int ig_full_likelihood(ig_ctx* c, int which, int use_prev, double* nz
     HIPCK(hipStreamSynchronize(c->stream));
     ig_acc_normalize((int64_t*)&h[0], (int64_t*)&h[1]);
     ig_acc_normalize((int64_t*)&h[2], (int64_t*)&h[3]);
-    if (nz) *nz = ig_acc_to_double(h[0], h[1]);
-    if (z) { /* CL:755-759 with the float log_e of the kernels replaced by the host's double constant */
-        const double log_e = 0.43429448190325182;
-        double n_tot_pxl;
-        float v_inter;
-        const int vi_bits = (int)h[7];
-        memcpy(&n_tot_pxl, &h[5], sizeof n_tot_pxl); /* k_full_zero: n_tot_pxl and v_inter of the parameter set */
-        memcpy(&v_inter, &vi_bits, sizeof v_inter);
-        const double val_intra = ig_acc_to_double(h[2], h[3]) * log_e;
-        const double val_inter = log_e * (n_tot_pxl - (double)h[4]) * -1.0 * (double)v_inter;
-        *z = val_intra + val_inter;
-    }
+    double n_tot_pxl;
+    float v_inter;
+    const int vi_bits = (int)h[7];
+    memcpy(&n_tot_pxl, &h[5], sizeof n_tot_pxl); /* k_full_zero: n_tot_pxl and v_inter of the parameter set */
+    memcpy(&v_inter, &vi_bits, sizeof v_inter);
+    likelihood_of_limbs(h, n_tot_pxl, v_inter, nz, z);
     if (limbs5)
         for (int i = 0; i < 5; i++) limbs5[i] = h[i];
     return 0;

@@ -18,8 +18,8 @@ SRC = os.path.join(HERE, "csrc", "ig_hip.hip")
 SRC_HOST = os.path.join(HERE, "csrc", "ig_draw.cpp")  # host-only part: the candidate draw
 DEPS = [SRC, SRC_HOST] + [os.path.join(HERE, "csrc", f) for f in ("ig_ops.cuh", "ig_common.cuh", "ig_model.cuh", "ig_kernels_setup.cuh",
                                                           "ig_kernels_score.cuh", "ig_kernels_screen.cuh", "ig_kernels_commit.cuh",
-                                                          "ig_kernels_nuis.cuh", "ig_kernels_wave.cuh", "ig_kernels_genome.cuh", "ig_kernels_rows.cuh", "ig_kernels_map.cuh", "ig_kernels_law.cuh", "ig_kernels_junc.cuh", "ig_kernels_lift.cuh", "ig_kernels_join.cuh", "ig_kernels_emap.cuh", "ig_kernels_place.cuh", "ig_kernels_orient.cuh", "ig_kernels_bal.cuh", "ig_kernels_gap.cuh", "ig_kernels_zoom.cuh", "ig_kernels_segplace.cuh", "ig_host_core.inc", "ig_host_upload.inc", "ig_host_genome.inc", "ig_host_rows.inc",
-                                                          "ig_host_map.inc", "ig_host_law.inc", "ig_host_junc.inc", "ig_host_lift.inc", "ig_host_join.inc", "ig_host_emap.inc", "ig_host_place.inc", "ig_host_orient.inc", "ig_host_bal.inc", "ig_host_gap.inc", "ig_host_zoom.inc", "ig_host_segplace.inc",
+                                                          "ig_kernels_nuis.cuh", "ig_kernels_wave.cuh", "ig_kernels_genome.cuh", "ig_kernels_rows.cuh", "ig_kernels_map.cuh", "ig_kernels_law.cuh", "ig_kernels_junc.cuh", "ig_kernels_lift.cuh", "ig_kernels_join.cuh", "ig_kernels_emap.cuh", "ig_kernels_place.cuh", "ig_kernels_orient.cuh", "ig_kernels_bal.cuh", "ig_kernels_gap.cuh", "ig_kernels_zoom.cuh", "ig_kernels_segplace.cuh", "ig_kernels_edit.cuh", "ig_host_core.inc", "ig_host_upload.inc", "ig_host_genome.inc", "ig_host_rows.inc",
+                                                          "ig_host_map.inc", "ig_host_law.inc", "ig_host_junc.inc", "ig_host_lift.inc", "ig_host_join.inc", "ig_host_emap.inc", "ig_host_place.inc", "ig_host_orient.inc", "ig_host_bal.inc", "ig_host_gap.inc", "ig_host_zoom.inc", "ig_host_segplace.inc", "ig_host_edit.inc",
                                                           "ig_host_batch.inc", "ig_host_nuis.inc", "ig_host_debug.inc")] + \
        [os.path.join(ROOT, "include", f) for f in ("ig_detmath.h", "ig_detmath_tables.h", "instagraal_hip.h")]
 
@@ -36,6 +36,7 @@ GAP_SUPPORT_PASSES = ("observed", "model", "model_wave", "model_workgroup")  # i
 BALANCE_BUILD_PASSES = ("units", "count", "rows", "scatter", "sort_short", "sort_lds", "sort_long", "reduce")  # ig_debug_balance_build_time
 ZOOM_PASSES = ("rowstart", "words", "sort_short", "sort_lds", "sort_long", "reduce")  # the passes of ig_assembly_contacts_coarsen
 BALANCE_FORMS = ("default", "wave", "packed")  # ig_debug_balance_form
+EDIT_PASSES = ("plan", "state", "tables", "delta", "zero", "whole")  # ig_debug_edit_time
 MAX_CANDIDATES = 16
 
 FRAG_FIELDS = ("pos", "sub_pos", "id_c", "start_bp", "len_bp", "sub_len", "circ", "id", "prev", "next", "l_cont",
@@ -1225,6 +1226,55 @@ class Context:
         ck = C.c_int64()
         _ck(lib().ig_debug_segment_placement_time(self._h, C.c_int32(int(window)), C.c_int32(int(window) if min_hosts is None else int(min_hosts)), C.c_int32(int(f.size)),
                                                   _p(f), _p(l), C.c_int32(int(n)), _p(ms), C.byref(ck)))
+        return ms, int(ck.value)
+
+    # ---- segment edits: the moves the block-level reports propose, scored exactly and applied (the rule: rearrange.py)
+    @staticmethod
+    def _edits(edits):
+        e = np.asarray(edits)
+        if e.size and (e.ndim not in (1, 2) or e.shape[-1] != 5 or not np.issubdtype(e.dtype, np.integer)):
+            raise HipError("segment edits: an integer array [n, 5] of (first_bin, last_bin, anchor, side, flip)")
+        return np.ascontiguousarray(e, np.int32).reshape(-1, 5)
+
+    def edit_score(self, edits, form=0):
+        """the exact sums of the genome every edit would leave (``ig_edit_score``) -> (status int32 [n], limbs int64 [n, 5] in the order
+        of ``full_likelihood``'s, nz f64 [n], z f64 [n]).  ``form``: 0 the delta form, 1 the whole form (the from-scratch passes on every
+        edited genome); both give the same limbs.  Changes nothing a move reads."""
+        e = self._edits(edits)
+        n = int(e.shape[0])
+        status, limbs = np.zeros(n, np.int32), np.zeros((n, 5), np.int64)
+        nz, z = np.zeros(n, np.float64), np.zeros(n, np.float64)
+        _ck(lib().ig_edit_score(self._h, C.c_int32(n), _p(e), C.c_int32(int(form)), _p(status), _p(limbs), _p(nz), _p(z)))
+        return status, limbs, nz, z
+
+    def edit_state(self, edit):
+        """tests: the state one edit would leave, with the internal contig ids -> (soa17 int32 [17, N], status); nothing is committed"""
+        e = self._edits(edit)
+        if e.shape[0] != 1:
+            raise HipError("edit_state: one edit")
+        out = np.zeros((17, self.N), np.int32)
+        status = C.c_int32()
+        _ck(lib().ig_edit_state(self._h, _p(e), _p(out), C.byref(status)))
+        return out, int(status.value)
+
+    def edit_apply(self, edit):
+        """commits one edit (``ig_edit_apply``) -> (status, limbs int64 [5]: the maintained sums behind the call).  A status other
+        than 0 leaves everything as it was."""
+        e = self._edits(edit)
+        if e.shape[0] != 1:
+            raise HipError("edit_apply: one edit")
+        limbs = np.zeros(5, np.int64)
+        status = C.c_int32()
+        _ck(lib().ig_edit_apply(self._h, _p(e), C.byref(status), _p(limbs)))
+        return int(status.value), limbs
+
+    def debug_edit_time(self, edits, form=0, n=1):
+        """``edit_score`` n times with hipEvents around each pass -> (ms [n, 6]: ``EDIT_PASSES``, checksum of the statuses and limbs of
+        the last call: the two forms agree on it)"""
+        e = self._edits(edits)
+        ms = np.zeros((int(n), len(EDIT_PASSES)), np.float32)
+        ck = C.c_int64()
+        _ck(lib().ig_debug_edit_time(self._h, C.c_int32(int(e.shape[0])), _p(e), C.c_int32(int(form)), C.c_int32(int(n)), _p(ms), C.byref(ck)))
         return ms, int(ck.value)
 
     # ---- balancing the contact map of the current genome (the rule: balance.py)

@@ -1454,6 +1454,83 @@ class sampler:  # noqa: N801 - the reference's class name
         res = self.gap_support(level, junctions, gaps_kb, window, window_kb, True) if result is None else result
         return gs.gapped_joins(res, n, min_observed)
 
+    # ---------------------------------------------------------- segment edits
+    def score_rearrangements(self, edits, form="delta"):
+        """The exact likelihood of the genome every segment edit would leave (``ig_edit_score``; the rule: ``rearrange.py``).
+        ``edits``: int [n, 5] of (first_bin, last_bin, anchor, side, flip); ``form``: "delta" (one pass over the contacts per chunk of
+        64 edits, the hot path) or "whole" (the from-scratch passes per edit, the definition) -- the same limbs.  -> a structured array
+        (``rearrange.SCORE_DTYPE``): ``status``, ``nz``, ``z``, ``score`` = nz + z, ``delta`` against the current genome, ``limbs``.
+        Nothing a move reads is changed.  No reference counterpart."""
+        from . import rearrange as ra
+
+        if form not in ra.FORMS:
+            raise ValueError("score_rearrangements: form is 'delta' or 'whole' (got %r)" % (form,))
+        e = ra.as_edits(edits)
+        status, limbs, nz, z = self.ctx.edit_score(e, ra.FORMS.index(form))
+        nz0, z0, _ = self.ctx.full_likelihood(0)
+        out = np.zeros(e.shape[0], ra.SCORE_DTYPE)
+        out["status"], out["nz"], out["z"], out["limbs"] = status, nz, z, limbs
+        out["score"] = nz + z
+        out["delta"] = out["score"] - (nz0 + z0)
+        return out
+
+    def apply_rearrangement(self, edit):
+        """Commits one segment edit (``ig_edit_apply``) and refreshes ``likelihood_t``, ``n_contigs``, ``mean_length_contigs`` and
+        ``gpu_vect_frags``.  -> the new likelihood; ValueError (nothing changed) for an edit the rule refuses."""
+        status, limbs = self.ctx.edit_apply(edit)
+        if status:
+            raise ValueError("apply_rearrangement: the edit %s is refused with status %d (rearrange.check)" % (list(np.asarray(edit).ravel()), status))
+        nz, z, now = self.ctx.full_likelihood(0)
+        if not np.array_equal(now, limbs):
+            raise RuntimeError("apply_rearrangement: the maintained sums behind the edit are %s, the from-scratch passes give %s" % (limbs.tolist(), now.tolist()))
+        self.last_edit_limbs = limbs
+        self.o = self.likelihood_t = nz + z
+        n, m, _ = self.ctx.renumber_contigs()
+        self.n_contigs, self.mean_length_contigs = np.int32(n), np.float32(m)
+        self.gpu_vect_frags.copy_from_gpu()
+        return self.likelihood_t
+
+    def propose_rearrangements(self, n=20, window=None, orientation_window=None):
+        """The edits the block-level reports propose on the current genome (``rearrange.propose``): the in-place flip of each of the
+        ``n`` top ``inverted_segments`` (block level, window ``orientation_window``, default orientation support's), and for each of
+        the ``n`` top ``misplaced_segments`` (block level, then scaffold level, window ``window``, default 64) every bin boundary of
+        the best scaffold within the window of the best site, both ways round.  -> int32 [n_edits, 5]"""
+        from . import rearrange as ra, segment_placement as sp
+
+        w = sp.DEFAULT_WINDOW if window is None else int(window)
+        inv = self.inverted_segments(n, level="block", window=orientation_window)
+        mis = [self.misplaced_segments(n, level=level, window=w) for level in ("block", "scaffold")]
+        return ra.propose(self.ctx.download_state(), inv, mis, n, w)
+
+    def polish(self, max_rounds=10, n=20, min_gain=0.0, window=None, orientation_window=None):
+        """Greedy polishing by segment edits: each round proposes (``propose_rearrangements``), scores every proposal exactly
+        (``score_rearrangements``), takes the best edits on disjoint contigs (``rearrange.polish_round``) and applies them; it stops on
+        a round with nothing to apply.  RuntimeError if the sums an apply returns differ from the limbs predicted for that edit (the
+        first edit of a round exactly, the later ones by additivity).  Deterministic; draws nothing from numpy's generator.  -> the
+        log: a list of dicts (round, edit, delta, likelihood after)."""
+        from . import rearrange as ra
+
+        log = []
+        for rnd in range(int(max_rounds)):
+            edits = self.propose_rearrangements(n, window, orientation_window)
+            if edits.shape[0] == 0:
+                break
+            scores = self.score_rearrangements(edits)
+            take = ra.polish_round(scores, edits, self.ctx.download_state(), min_gain)
+            if not take:
+                break
+            # the five limbs as three exact integers (value = hi * 2^32 + lo): the deltas of edits on disjoint contigs add
+            exact = lambda l: ((int(l[0]) << 32) + int(l[1]), (int(l[2]) << 32) + int(l[3]), int(l[4]))  # noqa: E731
+            base = exact(self.ctx.full_likelihood(0)[2])
+            want = base
+            for i in take:
+                want = tuple(w + p - b for w, p, b in zip(want, exact(scores["limbs"][i]), base))
+                like = self.apply_rearrangement(edits[i])
+                if exact(self.last_edit_limbs) != want:
+                    raise RuntimeError("polish: the sums behind edit %s are %s, predicted %s" % (edits[i].tolist(), exact(self.last_edit_limbs), want))
+                log.append(dict(round=rnd, edit=edits[i].copy(), delta=float(scores["delta"][i]), likelihood=float(like)))
+        return log
+
     # ----------------------------------------------------------- expected map
     def expected_map(self, max_side=2048):
         """What the model in use (``param_simu``) predicts for the pixels of ``contact_map(max_side)`` (``ig_expected_map``; the
