@@ -735,6 +735,46 @@ int ig_edit_apply(ig_ctx* ctx, const int32_t edit[5], int32_t* status, int64_t* 
  * whole} (the passes of the other form stay 0); *checksum (may be NULL): the statuses, then the limbs of the last call, each word
  * weighted by its place: the two forms agree on it */
 int ig_debug_edit_time(ig_ctx* ctx, int32_t n_edits, const int32_t* edits, int32_t form, int32_t n, float* ms_n, int64_t* checksum);
+
+/* ---- cut and join scores: the closed part of the likelihood change of EVERY cut of a linear contig and of EVERY link of two linear
+ * contigs, as exact integers in the units of ig_edit_score, from one pass over the contacts each (the rule, stated once:
+ * instagraal_amd/cut_join.py).  A cut in front of bin f (f in a linear contig, prev[f] >= 0) is the edit
+ * (f, last bin of the contig, NEW_CONTIG, 0, 0); a link (sa, sb) of the linear contigs a < b (numbered 0 .. K - 1 in ascending
+ * internal contig id; side 0: the head, 1: the tail) keeps a and moves all of b behind a's last bin (sa = 1, flipped where sb = 1) or
+ * in front of a's first bin (sa = 0, flipped where sb = 0).  Delta limbs are differences of limbs {nz hi, nz lo, z hi, z lo, intra
+ * pairs}, hi = q >> 32 and lo = (uint32) q summed apart, not normalised; a delta is (nz + z) of the maintained sums plus the delta
+ * limbs minus (nz + z) of the maintained sums, each formed as ig_full_likelihood forms them.  What is left out is the internal
+ * part: the contacts whose two ends stay in one contig on one side, whose f32 separation changes only by rounding (and by the mirrored
+ * reference points of a flipped contig); ig_edit_score has it.  All calls need the sub-fragment table, the contacts, a state and the
+ * parameters, all contacts on one handle, no nuisance step or chain in flight; they change nothing a move reads; their buffers are
+ * kept from call to call (those sized by the contigs and the pairs grow only; a state of another size frees them all and starts again)
+ * and are freed by ig_destroy. */
+/* per bin f: valid[N] (a cut exists), contacts[N] (stored contacts that span the junction), limbs[N][5], delta[N]; 0 where no cut exists */
+int ig_cut_scores(ig_ctx* ctx, int32_t* valid, int64_t* contacts, int64_t* limbs, double* delta);
+/* every pair a < b of linear contigs with a contact between them: the build leaves the result on the host side of the handle until
+ * the next build or ig_join_scores_release.  fetch: per contig head_bin, tail_bin, n_sub, length_bp [K]; CSR rowptr[K + 1], col (b,
+ * ascending); per pair contacts, nz[4][2] (link 2 sa + sb), z[2] (equal for the four links), dni, delta[4]. */
+int ig_join_scores_build(ig_ctx* ctx, int64_t* n_contigs, int64_t* n_pairs);
+int ig_join_scores_fetch(ig_ctx* ctx, int32_t* head_bin, int32_t* tail_bin, int32_t* n_sub, int32_t* length_bp, int64_t* rowptr, int32_t* col, int64_t* contacts,
+                         int64_t* nz, int64_t* z, int64_t* dni, double* delta);
+int ig_join_scores_release(ig_ctx* ctx);
+/* tests: the form of the join pass, -1: by the number of pairs (up to 256: accumulators in LDS, beyond: global atomics per run of a
+ * wave), 0: LDS (windows of 256 pairs, one launch each), 1: atomics per run.  Both give the same bytes. */
+int ig_debug_cut_join_form(ig_ctx* ctx, int32_t form);
+/* the LIFT_C_* words of the pairs' rows of the last finished build (kept behind ig_join_scores_release) */
+int ig_debug_join_scores_forms(ig_ctx* ctx, int64_t out8[8]);
+/* what = 0: ig_cut_scores, 1: ig_join_scores_build, n times with hipEvents around each pass: ms_n[n][12] = {span, scan, zero, count,
+ * rowscan, scatter, sort_short, sort_lds, sort_long, reduce, terms, join_zero} (the other report's passes stay 0); *checksum (may be
+ * NULL): the integer words of the last result, each weighted by its place: the forms agree on it */
+int ig_debug_cut_join_time(ig_ctx* ctx, int32_t what, int32_t n, float* ms_n, int64_t* checksum);
+/* eval_q's ring-free branch on the CPU from include/ig_detmath.h, hot path selection included: q[k] = the quantised term of a contact
+ * of count[k] at separation s[k] kb and rank distance d[k] (trans[k] != 0: a trans pair; s and d play no part).  No context, no GPU. */
+int ig_contact_terms_host(const float params[8], float mean_kb, const float* s, const int32_t* d, const int32_t* trans, const int32_t* count, int64_t n, int64_t* q);
+/* tests: eval_q itself on the device for the same inputs (s >= 0, 0 <= d < 2^28), under parameter set 0 and its P_z table: the two agree
+ * bit for bit */
+int ig_debug_contact_terms(ig_ctx* ctx, const float* s, const int32_t* d, const int32_t* trans, const int32_t* count, int64_t n, int64_t* q);
+/* zero_q of a linear contig on the CPU: the sub-fragment of rank pos[k] in a contig of len[k] sub-fragments.  No context, no GPU. */
+int ig_zero_terms_host(const float params[8], float mean_kb, const int32_t* pos, const int32_t* len, int64_t n, int64_t* q);
 #ifdef __cplusplus
 }
 #endif

@@ -598,6 +598,39 @@ struct EditBuf {
     size_t mask_cap = 0;
 };
 
+/* cut and join scores (ig_kernels_cutjoin.cuh): buffers kept from call to call and freed by free_cutjoin_buffers (ig_host_cutjoin.inc):
+ * those sized by the contigs and by the pairs grow only while N and M stay; a genome of other sizes frees them all and starts again;
+ * the result of the last ig_join_scores_build stays on the host until it is released */
+struct CutJoinBuf {
+    int *slotl = nullptr, *kof = nullptr;    /* [N] the slot of every bin (-1: a ring), the number of its contig among the linear ones */
+    unsigned long long* diff = nullptr;      /* [3][N + 1] difference words: hi, lo, contacts */
+    unsigned long long* prof = nullptr;      /* [3][N + 1] their prefix sums */
+    unsigned long long* tot = nullptr;       /* the scans' chunk totals (3 arrays of N + 1, 2 of M + 2) */
+    long long* zcut = nullptr;               /* [2][N] the z limbs of the cuts */
+    int4* srec = nullptr;                    /* [M] (dist, contig, rank, slot) per sub-fragment: k_cut_span's one gather per end */
+    int4* brec = nullptr;                    /* [2 N] (sbp, spos, sl, lb), (ori, LB, SL, k) per bin: k_cj_join's */
+    unsigned long long* vk = nullptr;        /* [2][M + 2] quantize(-(v_inter k)) as limbs ... */
+    unsigned long long* vsum = nullptr;      /* [2][M + 2] ... and their prefix sums */
+    int N = 0, M = 0;
+    int* csl = nullptr;                      /* [cap_K] sub-fragments per linear contig */
+    long long* gc = nullptr;                 /* [2][cap_K] G of every linear contig */
+    long long cap_K = 0;
+    long long* acc = nullptr;                /* [cap_pairs][8] the nz limbs of the links */
+    long long* zacc = nullptr;               /* [cap_pairs][2] their z limbs */
+    long long cap_pairs = 0;
+    unsigned long long* sc = nullptr;        /* 1 scalar: the entries of the pairs' rows */
+    RowBuf rows;                             /* the pairs: K rows, out_col = b, out_cnt = contacts */
+    int form = -1;                           /* ig_debug_cut_join_form: -1 by the number of pairs, 0 LDS, 1 atomics per run */
+    /* the built result, on the host */
+    bool valid = false;
+    bool have_forms = false; /* forms[] is of a finished build: kept behind the release of its result */
+    long long K = 0, n_pairs = 0;
+    long long forms[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    std::vector<long long> h_rowptr, h_contacts, h_nz, h_z, h_dni;
+    std::vector<int> h_col, h_head, h_tail, h_nsub, h_lbp;
+    std::vector<double> h_delta;
+};
+
 struct ig_ctx {
     int device;
     hipStream_t stream;
@@ -713,6 +746,7 @@ struct ig_ctx {
     GapBuf gap;
     SegPlaceBuf segplace;
     EditBuf edit;
+    CutJoinBuf cutjoin;
     DebugRows debug_rows;
     DebugRows debug_zoom; /* the last ig_debug_zoom_coarsen's result (ig_debug_zoom_fetch) */
     int* batch_out; /* committed moves, pending slot, (unused), candidates, predicted deltas used, contigs */

@@ -18,8 +18,8 @@ SRC = os.path.join(HERE, "csrc", "ig_hip.hip")
 SRC_HOST = os.path.join(HERE, "csrc", "ig_draw.cpp")  # host-only part: the candidate draw
 DEPS = [SRC, SRC_HOST] + [os.path.join(HERE, "csrc", f) for f in ("ig_ops.cuh", "ig_common.cuh", "ig_model.cuh", "ig_kernels_setup.cuh",
                                                           "ig_kernels_score.cuh", "ig_kernels_screen.cuh", "ig_kernels_commit.cuh",
-                                                          "ig_kernels_nuis.cuh", "ig_kernels_wave.cuh", "ig_kernels_genome.cuh", "ig_kernels_rows.cuh", "ig_kernels_map.cuh", "ig_kernels_law.cuh", "ig_kernels_junc.cuh", "ig_kernels_lift.cuh", "ig_kernels_join.cuh", "ig_kernels_emap.cuh", "ig_kernels_place.cuh", "ig_kernels_orient.cuh", "ig_kernels_bal.cuh", "ig_kernels_gap.cuh", "ig_kernels_zoom.cuh", "ig_kernels_segplace.cuh", "ig_kernels_edit.cuh", "ig_host_core.inc", "ig_host_upload.inc", "ig_host_genome.inc", "ig_host_rows.inc",
-                                                          "ig_host_map.inc", "ig_host_law.inc", "ig_host_junc.inc", "ig_host_lift.inc", "ig_host_join.inc", "ig_host_emap.inc", "ig_host_place.inc", "ig_host_orient.inc", "ig_host_bal.inc", "ig_host_gap.inc", "ig_host_zoom.inc", "ig_host_segplace.inc", "ig_host_edit.inc",
+                                                          "ig_kernels_nuis.cuh", "ig_kernels_wave.cuh", "ig_kernels_genome.cuh", "ig_kernels_rows.cuh", "ig_kernels_map.cuh", "ig_kernels_law.cuh", "ig_kernels_junc.cuh", "ig_kernels_lift.cuh", "ig_kernels_join.cuh", "ig_kernels_emap.cuh", "ig_kernels_place.cuh", "ig_kernels_orient.cuh", "ig_kernels_bal.cuh", "ig_kernels_gap.cuh", "ig_kernels_zoom.cuh", "ig_kernels_segplace.cuh", "ig_kernels_edit.cuh", "ig_kernels_cutjoin.cuh", "ig_host_core.inc", "ig_host_upload.inc", "ig_host_genome.inc", "ig_host_rows.inc",
+                                                          "ig_host_map.inc", "ig_host_law.inc", "ig_host_junc.inc", "ig_host_lift.inc", "ig_host_join.inc", "ig_host_emap.inc", "ig_host_place.inc", "ig_host_orient.inc", "ig_host_bal.inc", "ig_host_gap.inc", "ig_host_zoom.inc", "ig_host_segplace.inc", "ig_host_edit.inc", "ig_host_cutjoin.inc",
                                                           "ig_host_batch.inc", "ig_host_nuis.inc", "ig_host_debug.inc")] + \
        [os.path.join(ROOT, "include", f) for f in ("ig_detmath.h", "ig_detmath_tables.h", "instagraal_hip.h")]
 
@@ -37,6 +37,9 @@ BALANCE_BUILD_PASSES = ("units", "count", "rows", "scatter", "sort_short", "sort
 ZOOM_PASSES = ("rowstart", "words", "sort_short", "sort_lds", "sort_long", "reduce")  # the passes of ig_assembly_contacts_coarsen
 BALANCE_FORMS = ("default", "wave", "packed")  # ig_debug_balance_form
 EDIT_PASSES = ("plan", "state", "tables", "delta", "zero", "whole")  # ig_debug_edit_time
+CUT_JOIN_PASSES = ("span", "scan", "zero", "count", "rowscan", "scatter", "sort_short", "sort_lds", "sort_long", "reduce", "terms", "join_zero")  # ig_debug_cut_join_time
+CUT_JOIN_LDS_PAIRS = 256  # CJ_LDS_PAIRS (csrc/ig_kernels_cutjoin.cuh): pairs up to which the join pass keeps its accumulators in LDS
+CONTIG_ARRAYS = ("head_bin", "tail_bin", "n_sub", "length_bp")  # ig_join_scores_fetch: per linear contig
 MAX_CANDIDATES = 16
 
 FRAG_FIELDS = ("pos", "sub_pos", "id_c", "start_bp", "len_bp", "sub_len", "circ", "id", "prev", "next", "l_cont",
@@ -120,6 +123,36 @@ def model_values_host(params, s):
     e_q, l_q = np.zeros(sep.shape, np.int64), np.zeros(sep.shape, np.int64)
     _ck(lib().ig_model_values_host(_p(p), _p(sep), C.c_int64(sep.size), _p(e_q), _p(l_q)))
     return e_q, l_q
+
+
+def _params8(params, who):
+    p = np.ascontiguousarray(params, np.float32).ravel()
+    if p.size != 8:
+        raise HipError("%s: eight parameters in the order of ig_params (got %d)" % (who, p.size))
+    return p
+
+
+def contact_terms_host(params, mean_kb, s, d, trans, count):
+    """the quantised likelihood terms of contacts on the CPU (``ig_contact_terms_host``: eval_q's ring-free branch restated from
+    include/ig_detmath.h, hot path selection included; no context, no GPU) -> int64 of the shape of ``s``.  ``s``: separation in kb
+    (f32), ``d``: rank distance, ``trans``: non-zero for a trans pair (s and d play no part then), ``count``: the observed count."""
+    p = _params8(params, "contact_terms_host")
+    sep = np.ascontiguousarray(s, np.float32)
+    dd, tt, cc = (np.ascontiguousarray(np.broadcast_to(np.asarray(a), sep.shape), np.int32) for a in (d, trans, count))
+    q = np.zeros(sep.shape, np.int64)
+    _ck(lib().ig_contact_terms_host(_p(p), C.c_float(float(np.float32(mean_kb))), _p(sep), _p(dd), _p(tt), _p(cc), C.c_int64(sep.size), _p(q)))
+    return q
+
+
+def zero_terms_host(params, mean_kb, pos, length):
+    """the quantised zero-pixel terms of sub-fragments of linear contigs on the CPU (``ig_zero_terms_host``: zero_q with s_tot == 0) ->
+    int64 of the shape of ``pos``: rank ``pos`` in a contig of ``length`` sub-fragments"""
+    p = _params8(params, "zero_terms_host")
+    pp = np.ascontiguousarray(pos, np.int32)
+    ll = np.ascontiguousarray(np.broadcast_to(np.asarray(length), pp.shape), np.int32)
+    q = np.zeros(pp.shape, np.int64)
+    _ck(lib().ig_zero_terms_host(_p(p), C.c_float(float(np.float32(mean_kb))), _p(pp), _p(ll), C.c_int64(pp.size), _p(q)))
+    return q
 
 
 def as_int32_exact(a, name="array"):
@@ -1275,6 +1308,59 @@ class Context:
         ms = np.zeros((int(n), len(EDIT_PASSES)), np.float32)
         ck = C.c_int64()
         _ck(lib().ig_debug_edit_time(self._h, C.c_int32(int(e.shape[0])), _p(e), C.c_int32(int(form)), C.c_int32(int(n)), _p(ms), C.byref(ck)))
+        return ms, int(ck.value)
+
+    # ---- cut and join scores: the closed part of the likelihood change of every cut and every link (the rule: cut_join.py)
+    def cut_scores(self):
+        """``ig_cut_scores`` -> dict: valid (bool [N]: a cut in front of the bin exists), contacts (int64 [N]), limbs (int64 [N, 5]: the
+        delta limbs), delta (f64 [N]); zeros where no cut exists.  Changes nothing a move reads."""
+        n = self.N
+        valid, contacts = np.zeros(n, np.int32), np.zeros(n, np.int64)
+        limbs, delta = np.zeros((n, 5), np.int64), np.zeros(n, np.float64)
+        _ck(lib().ig_cut_scores(self._h, _p(valid), _p(contacts), _p(limbs), _p(delta)))
+        return dict(valid=valid != 0, contacts=contacts, limbs=limbs, delta=delta)
+
+    def join_scores(self):
+        """``ig_join_scores_build`` / ``_fetch`` / ``_release`` -> dict: K, n_pairs; per linear contig (ascending internal id)
+        head_bin, tail_bin, n_sub, length_bp (int32 [K]); CSR rowptr (int64 [K + 1]), col (int32, b > a ascending); per pair contacts
+        (int64), nz (int64 [n_pairs, 4, 2], link 2 sa + sb, side 0 the head), z (int64 [n_pairs, 2]), dni (int64), delta (f64 [n_pairs, 4])"""
+        nk, npair = C.c_int64(), C.c_int64()
+        _ck(lib().ig_join_scores_build(self._h, C.byref(nk), C.byref(npair)))
+        K, P = int(nk.value), int(npair.value)
+        out = dict(K=K, n_pairs=P, rowptr=np.zeros(K + 1, np.int64), col=np.zeros(P, np.int32), contacts=np.zeros(P, np.int64),
+                   nz=np.zeros((P, 4, 2), np.int64), z=np.zeros((P, 2), np.int64), dni=np.zeros(P, np.int64), delta=np.zeros((P, 4), np.float64))
+        for k in CONTIG_ARRAYS:
+            out[k] = np.zeros(K, np.int32)
+        try:
+            _ck(lib().ig_join_scores_fetch(self._h, *[_p(out[k]) for k in CONTIG_ARRAYS + ("rowptr", "col", "contacts", "nz", "z", "dni", "delta")]))
+        finally:
+            _ck(lib().ig_join_scores_release(self._h))
+        return out
+
+    def debug_contact_terms(self, s, d, trans, count):
+        """tests: eval_q on the device for the inputs of ``contact_terms_host`` (``ig_debug_contact_terms``) -> int64 of the shape of ``s``"""
+        sep = np.ascontiguousarray(s, np.float32)
+        dd, tt, cc = (np.ascontiguousarray(np.broadcast_to(np.asarray(a), sep.shape), np.int32) for a in (d, trans, count))
+        q = np.zeros(sep.shape, np.int64)
+        _ck(lib().ig_debug_contact_terms(self._h, _p(sep), _p(dd), _p(tt), _p(cc), C.c_int64(sep.size), _p(q)))
+        return q
+
+    def debug_cut_join_form(self, form=-1):
+        """tests: the form of the join pass: -1 by the number of pairs, 0 accumulators in LDS, 1 atomics per run of a wave"""
+        _ck(lib().ig_debug_cut_join_form(self._h, C.c_int32(int(form))))
+
+    def debug_join_scores_forms(self):
+        """the LIFT_C_* words of the pairs' rows of the last finished ``join_scores`` build (the handle keeps them behind the release)"""
+        out = np.zeros(8, np.int64)
+        _ck(lib().ig_debug_join_scores_forms(self._h, _p(out)))
+        return out
+
+    def debug_cut_join_time(self, what="cuts", n=1):
+        """``cut_scores`` (what = "cuts") or the build of ``join_scores`` ("joins") n times with hipEvents around each pass ->
+        (ms [n, 12]: ``CUT_JOIN_PASSES``, checksum of the integer words of the last result: the forms agree on it)"""
+        ms = np.zeros((int(n), len(CUT_JOIN_PASSES)), np.float32)
+        ck = C.c_int64()
+        _ck(lib().ig_debug_cut_join_time(self._h, C.c_int32(("cuts", "joins").index(what)), C.c_int32(int(n)), _p(ms), C.byref(ck)))
         return ms, int(ck.value)
 
     # ---- balancing the contact map of the current genome (the rule: balance.py)

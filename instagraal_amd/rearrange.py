@@ -209,6 +209,21 @@ def propose(state, inverted=None, misplaced=(), n=20, window=64):
     return as_edits(edits)
 
 
+def propose_cuts_joins(state, cuts=None, joins=None, n=20):
+    """The edits of the ``n`` weakest cuts (``cuts``: what ``sampler.cut_scores`` returns) and of the ``n`` strongest joins (``joins``:
+    ``sampler.join_scores``), cuts first, each list by falling delta (``cut_join.weakest_cuts``, ``cut_join.strongest_joins``); either
+    may be None.  An edit the rule refuses on ``state`` is left out.  -> int32 [n_edits, 5]"""
+    from . import cut_join as cj
+
+    st = np.asarray(state)
+    edits = []
+    if cuts is not None:
+        edits += [tuple(int(x) for x in e) for e in cj.weakest_cuts(st, cuts, n)["edit"]]
+    if joins is not None:
+        edits += [tuple(int(x) for x in e) for e in cj.strongest_joins(joins, n)["edit"]]
+    return as_edits([e for e in edits if check(st, e) == OK])
+
+
 def polish_round(scores, edits, state, min_gain=0.0):
     """the edits one round applies -> their indices: those with status 0 and delta > ``min_gain``, by descending delta (ties by index),
     skipping any edit that shares a touched contig with one taken before it in this round.  The deltas of edits on disjoint sets of

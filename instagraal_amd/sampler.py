@@ -1502,17 +1502,56 @@ class sampler:  # noqa: N801 - the reference's class name
         mis = [self.misplaced_segments(n, level=level, window=w) for level in ("block", "scaffold")]
         return ra.propose(self.ctx.download_state(), inv, mis, n, w)
 
-    def polish(self, max_rounds=10, n=20, min_gain=0.0, window=None, orientation_window=None):
+    def propose_cuts_joins(self, n=20, cuts=True, joins=True):
+        """The edits of the ``n`` ``weakest_cuts`` and of the ``n`` ``strongest_joins`` of the current genome
+        (``rearrange.propose_cuts_joins``) -> int32 [n_edits, 5]"""
+        from . import rearrange as ra
+
+        return ra.propose_cuts_joins(self.ctx.download_state(), self.cut_scores() if cuts else None, self.join_scores() if joins else None, n)
+
+    # ---------------------------------------------------------- cut and join scores
+    def cut_scores(self):
+        """The likelihood change of EVERY cut of a linear contig, as far as it has a closed structure (``ig_cut_scores``; the rule:
+        ``cut_join.py``): the cis contacts that span the junction become trans, the zero-pixel sum and the intra pair count of the two
+        halves replace the contig's.  -> dict per bin f (the cut in front of it): ``valid``, ``contacts``, ``limbs`` (the delta limbs,
+        exact integers in the units of ``score_rearrangements``), ``delta``.  What is left out (the contacts inside each half, whose
+        f32 separation is rounded anew) is small: the scores rank, ``score_rearrangements`` decides.  No reference counterpart."""
+        return self.ctx.cut_scores()
+
+    def join_scores(self):
+        """The same for EVERY link of two linear contigs with a contact between them, in its four orientations
+        (``ig_join_scores_build``) -> dict: the linear contigs (``head_bin``, ``tail_bin``, ``n_sub``, ``length_bp``, numbered in
+        ascending internal id), CSR ``rowptr`` / ``col`` over the pairs a < b, per pair ``contacts``, ``nz`` [4][2], ``z`` [2],
+        ``dni``, ``delta`` [4] (link 2 sa + sb, side 0 the head, 1 the tail)."""
+        return self.ctx.join_scores()
+
+    def weakest_cuts(self, n=20, cuts=None):
+        """the ``n`` cuts with the largest positive delta first -> ``cut_join.CUT_DTYPE`` rows, each with its edit"""
+        from . import cut_join as cj
+
+        return cj.weakest_cuts(self.ctx.download_state(), self.cut_scores() if cuts is None else cuts, n)
+
+    def strongest_joins(self, n=20, joins=None):
+        """the ``n`` links with the largest positive delta first, one row per link -> ``cut_join.LINK_DTYPE`` rows, each with its
+        canonical edit"""
+        from . import cut_join as cj
+
+        return cj.strongest_joins(self.join_scores() if joins is None else joins, n)
+
+    def polish(self, max_rounds=10, n=20, min_gain=0.0, window=None, orientation_window=None, cuts=False, joins=False):
         """Greedy polishing by segment edits: each round proposes (``propose_rearrangements``), scores every proposal exactly
         (``score_rearrangements``), takes the best edits on disjoint contigs (``rearrange.polish_round``) and applies them; it stops on
         a round with nothing to apply.  RuntimeError if the sums an apply returns differ from the limbs predicted for that edit (the
-        first edit of a round exactly, the later ones by additivity).  Deterministic; draws nothing from numpy's generator.  -> the
-        log: a list of dicts (round, edit, delta, likelihood after)."""
+        first edit of a round exactly, the later ones by additivity).  Deterministic; draws nothing from numpy's generator.
+        ``cuts`` / ``joins``: also propose the weakest cuts / the strongest joins (``cut_scores``, ``join_scores``); they are scored
+        and checked like every other proposal.  -> the log: a list of dicts (round, edit, delta, likelihood after)."""
         from . import rearrange as ra
 
         log = []
         for rnd in range(int(max_rounds)):
             edits = self.propose_rearrangements(n, window, orientation_window)
+            if cuts or joins:
+                edits = np.concatenate([edits, self.propose_cuts_joins(n, cuts, joins)])
             if edits.shape[0] == 0:
                 break
             scores = self.score_rearrangements(edits)

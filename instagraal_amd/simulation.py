@@ -195,7 +195,7 @@ class instagraal_class:
 
     def full_em(self, n_cycles, n_neighbours, bomb, id_start_sample_param, save_matrix=False, save_law=False, save_junctions=False,
                 save_contacts=False, save_joins=False, save_residuals=False, save_placements=False, save_orientations=False, save_weights=False, save_gaps=False,
-                save_resolutions=False, save_segment_placements=False, polish=False):  # IG:196-291
+                save_resolutions=False, save_segment_placements=False, polish=False, save_cut_join=False):  # IG:196-291
         sampler = self.simulation.sampler
         if bomb:
             sampler.bomb_the_genome()
@@ -250,9 +250,15 @@ class instagraal_class:
         if polish:  # (once, behind the last cycle and in front of every report below: greedy segment edits, scored exactly)
             from . import rearrange as ra
 
-            ra.write_polish_log(self._out("polish.txt"), sampler.polish())
+            every = polish == "all"  # (cuts and joins proposed next to the flips and the moves: DESIGN 4.24)
+            ra.write_polish_log(self._out("polish.txt"), sampler.polish(cuts=every, joins=every))
             sampler.gpu_vect_frags.copy_from_gpu()
             self.simulation.export_new_fasta()  # (info_frags.txt and genome.fasta of the polished genome)
+        if save_cut_join:  # (once, behind the last cycle and the polishing: the cuts and the links the likelihood would take)
+            from . import cut_join as cj
+
+            cj.write_cuts(self._out("cuts.txt"), sampler.weakest_cuts())
+            cj.write_links(self._out("links.txt"), sampler.strongest_joins())
         if save_contacts:  # (once, behind the last cycle: the table is large)
             sampler.write_assembly_contacts(self._out("assembly_contacts"), level="sub")
         if save_resolutions:  # (once, behind the last cycle, beside assembly_contacts/: the fixed-resolution maps and the scaffold matrix)
@@ -304,7 +310,8 @@ class instagraal_class:
 def run_instagraal(hic_folder, reference_fa, output_folder=None, level=4, cycles=100, coverage_std=1, neighborhood=5, device=0,
                    circular=False, bomb=False, pyramid_only=False, save_pickle=False, save_matrix=False, simple=False, save_law=False,
                    save_junctions=False, save_contacts=False, save_joins=False, save_residuals=False, save_placements=False,
-                   save_orientations=False, save_weights=False, save_gaps=False, save_resolutions=False, save_segment_placements=False, polish=False):
+                   save_orientations=False, save_weights=False, save_gaps=False, save_resolutions=False, save_segment_placements=False, polish=False,
+                   save_cut_join=False):
     """IG:502-581 (defaults of cli/main.py: level 4, 100 cycles, 5 neighbours, 1 std).  The three trailing switches of the
     reference's signature (IG:512-514) are accepted: ``save_pickle`` dumps the run object to ``graal.pkl`` as the reference
     tries to (IG:589-594: a warning when it cannot be pickled -- device handles here, h5py handles there); ``save_matrix``
@@ -347,7 +354,10 @@ def run_instagraal(hic_folder, reference_fa, output_folder=None, level=4, cycles
     contacts would put it in there (``sampler.segment_placement``); ``polish`` (an addition too) runs ``sampler.polish``
     once, behind the last cycle and in front of every ``save_*`` report that is written once: greedy segment edits proposed by the
     block-level reports and scored exactly, logged to ``polish.txt`` (round, edit, delta, likelihood); ``info_frags.txt``,
-    ``genome.fasta`` and those reports then describe the polished genome (``rearrange.py``)."""
+    ``genome.fasta`` and those reports then describe the polished genome (``rearrange.py``); ``polish="all"`` also proposes
+    the weakest cuts and the strongest joins (``cut_join.py``); ``save_cut_join`` (an addition too) writes ``cuts.txt`` and ``links.txt``
+    once, behind the last cycle and the polishing: the cuts and the links with the largest positive likelihood change, each with its
+    edit (``sampler.weakest_cuts``, ``sampler.strongest_joins``)."""
     import warnings
 
     if simple and not pyramid_only:
@@ -369,7 +379,7 @@ def run_instagraal(hic_folder, reference_fa, output_folder=None, level=4, cycles
     p2.full_em(n_cycles=cycles, n_neighbours=neighborhood, bomb=bomb, id_start_sample_param=4, save_matrix=save_matrix, save_law=save_law,
                save_junctions=save_junctions, save_contacts=save_contacts, save_joins=save_joins, save_residuals=save_residuals, save_placements=save_placements,
                save_orientations=save_orientations, save_weights=save_weights, save_gaps=save_gaps, save_resolutions=save_resolutions,
-               save_segment_placements=save_segment_placements, polish=polish)
+               save_segment_placements=save_segment_placements, polish=polish, save_cut_join=save_cut_join)
     if save_pickle:  # IG:589-594
         import pickle
 
