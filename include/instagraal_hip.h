@@ -775,6 +775,47 @@ int ig_contact_terms_host(const float params[8], float mean_kb, const float* s, 
 int ig_debug_contact_terms(ig_ctx* ctx, const float* s, const int32_t* d, const int32_t* trans, const int32_t* count, int64_t n, int64_t* q);
 /* zero_q of a linear contig on the CPU: the sub-fragment of rank pos[k] in a contig of len[k] sub-fragments.  No context, no GPU. */
 int ig_zero_terms_host(const float params[8], float mean_kb, const int32_t* pos, const int32_t* len, int64_t n, int64_t* q);
+
+/* ---- read pairs lifted onto the current genome: Hi-C read pairs, aligned to the INPUT contigs, in the coordinates of the scaffolds as
+ * they stand, kept on the device; from them the pixels at any unit and the distance histogram per strand combination (the rule, stated
+ * once: instagraal_amd/pairs_lift.py).  A SESSION lives between ig_pairs_begin and ig_pairs_end (ig_destroy frees a
+ * live one).  It is begun under one genome: every later call compares the state with the one the session was begun under and refuses
+ * once a move, an edit or an upload has changed it (end the session and begin again with a table of the new genome).  All calls need a
+ * state, the whole genome on one handle, no nuisance step or chain in flight; they change nothing a move reads.
+ *
+ * The source table: n_intervals intervals sorted by (contig, src_start), src_rowptr[n_contigs + 1] over the contig ids; per interval
+ * [src_start, src_end) on its contig (0-based, half-open, not overlapping), the rank of its scaffold among the n_scaffolds placed ones
+ * (at most 2^30 of them; -1: not placed), new_start inside the scaffold, reversed (0 / 1) and its position in the genome order (0 .. n_positions - 1);
+ * scaffold_len[n_scaffolds] in bp, each at most 2^31 - 1; bin_unit[n_positions]: the unit of every position among the n_bin_units placed
+ * bins.  reserve_pairs: room in the store from the start (it grows by itself, under a check of the free device memory: a refusal
+ * leaves the session as it was). */
+int ig_pairs_begin(ig_ctx* ctx, const int32_t* src_rowptr, int32_t n_contigs, const int32_t* src_start, const int32_t* src_end, const int32_t* new_start,
+                   const int32_t* scaffold, const uint8_t* reversed, const int32_t* position, int64_t n_intervals, const int64_t* scaffold_len, int32_t n_scaffolds,
+                   const int32_t* bin_unit, int64_t n_positions, int64_t n_bin_units, int64_t reserve_pairs);
+/* One chunk of n pairs: contig ids (anything outside 0 .. n_contigs - 1: unknown) and 1-based positions of the two ends; strands (may
+ * be NULL: all '+'): bit 0 set where end 1 was read on '-', bit 1 where end 2 was.  The nine per-pair outputs (all given, or all NULL)
+ * are in input order: scaffold (-1), 1-based position (0), position of the interval in the genome order (-1) and reversed bit per end;
+ * status 0 kept, 1 end 1 not covered, 2 end 2 not covered, 3 an end on an unplaced sub-fragment.  The kept pairs are appended to the
+ * store (in no particular order).  scalars: {pairs in, kept, end 1 not covered, end 2 not covered, unplaced, pairs stored, 0, 0}. */
+int ig_pairs_lift(ig_ctx* ctx, const int32_t* c1, const int32_t* p1, const int32_t* c2, const int32_t* p2, const uint8_t* strands, int64_t n, int32_t* scaffold1,
+                  int32_t* pos1, int32_t* unit1, uint8_t* rev1, int32_t* scaffold2, int32_t* pos2, int32_t* unit2, uint8_t* rev2, uint8_t* status, int64_t scalars[8]);
+/* The pixels of the stored pairs: kind 0 the positions, 1 the placed bins, 2 fixed bins of binsize bp (first_unit[scaffold] + position
+ * / binsize), 3 the scaffolds; keys (min, max), equal keys summed, the diagonal kept.  The result REPLACES the handle's
+ * assembly-contacts snapshot: ig_assembly_contacts_rows, _fetch, _coarsen and _release serve it as they serve a build from the
+ * contacts.  scalars: the eight words of ig_assembly_contacts_build (entries: the stored pairs). */
+int ig_pairs_pixels_build(ig_ctx* ctx, int32_t kind, int64_t binsize, int64_t* n_units, int64_t* n_entries, int64_t scalars[8]);
+/* The stored pairs with both ends on one scaffold by distance and strand combination: counts[4][n_edges - 1] (++, +-, -+, --), bin =
+ * clip(the last edge <= |pos2 - pos1|, 0, n_edges - 2); 2 <= n_edges <= 512 edges in bp, >= 0, ascending.  flip_strands: an end on a
+ * reversed interval has its strand flipped.  scalars: {pairs stored, counted, on two scaffolds, 0 ...}. */
+int ig_pairs_law(ig_ctx* ctx, const int64_t* edges_bp, int32_t n_edges, int32_t flip_strands, int64_t* counts, int64_t scalars[8]);
+/* empties the store; the table and the buffers stay */
+int ig_pairs_clear(ig_ctx* ctx);
+int ig_pairs_end(ig_ctx* ctx);
+/* the three passes n times with hipEvents around each: every repeat empties the store, lifts the chunk, counts the law and builds the
+ * pixels: ms_n[n][9] = {lift, count, scan, scatter, sort_short, sort_lds, sort_long, reduce, law}; *checksum (may be NULL): the scalars
+ * and the histogram of the last repeat, each word weighted by its place */
+int ig_debug_pairs_time(ig_ctx* ctx, const int32_t* c1, const int32_t* p1, const int32_t* c2, const int32_t* p2, const uint8_t* strands, int64_t n_pairs, int32_t kind,
+                        int64_t binsize, const int64_t* edges_bp, int32_t n_edges, int32_t n, float* ms_n, int64_t* checksum);
 #ifdef __cplusplus
 }
 #endif

@@ -631,6 +631,33 @@ struct CutJoinBuf {
     std::vector<double> h_delta;
 };
 
+/* read pairs lifted onto the current genome (ig_kernels_pairs.cuh): one session between ig_pairs_begin and ig_pairs_end, freed by
+ * free_pairs_buffers (ig_host_pairs.inc): the source table, the store of the kept pairs (grows under the free-memory guard), the
+ * staging arrays of a piece of a chunk (grow-only) and the genome's stamp the session was begun under */
+struct PairsBuf {
+    bool live = false;
+    int n_contigs = 0, K = 0;             /* input contig ids 0 .. n_contigs - 1; placed scaffolds */
+    long long n_iv = 0, T = 0, n_bin_units = 0;
+    int* rowptr = nullptr;                /* [n_contigs + 1] the intervals of every contig */
+    int* start = nullptr;                 /* [n_iv] their starts: the words the search reads */
+    struct PairsIv* iv = nullptr;         /* [n_iv] one 16-byte record each, gathered once per end */
+    int* bin_unit = nullptr;              /* [T] the unit of every position at "bin" */
+    std::vector<long long> scaffold_len;  /* [K] */
+    int4* ends = nullptr;                 /* the store: [cap] (scaffold, 0-based position) of both ends */
+    int2* unit = nullptr;                 /* [cap] the positions of the two intervals */
+    unsigned char* flag = nullptr;        /* [cap] PAIRS_F_* */
+    long long cap = 0, size = 0;
+    unsigned long long* sc = nullptr;     /* PAIRS_SC_WORDS (ig_host_pairs.inc): the cursor, the lift's scalars, the emit's */
+    int* in[4] = {nullptr, nullptr, nullptr, nullptr};                         /* a piece's c1, p1, c2, p2 */
+    unsigned char* in_strands = nullptr;
+    int* out_i[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};    /* scaffold1, pos1, unit1, scaffold2, pos2, unit2 */
+    unsigned char* out_b[3] = {nullptr, nullptr, nullptr};                     /* rev1, rev2, status */
+    long long piece_cap = 0;
+    long long* edges = nullptr;           /* [PAIRS_MAX_EDGES] */
+    unsigned long long* counts = nullptr; /* [4][PAIRS_MAX_EDGES - 1] */
+    unsigned long long stamp = 0;         /* of the state the table was made from: a session does not outlive a change of the genome */
+};
+
 struct ig_ctx {
     int device;
     hipStream_t stream;
@@ -747,6 +774,7 @@ struct ig_ctx {
     SegPlaceBuf segplace;
     EditBuf edit;
     CutJoinBuf cutjoin;
+    PairsBuf pairs;
     DebugRows debug_rows;
     DebugRows debug_zoom; /* the last ig_debug_zoom_coarsen's result (ig_debug_zoom_fetch) */
     int* batch_out; /* committed moves, pending slot, (unused), candidates, predicted deltas used, contigs */

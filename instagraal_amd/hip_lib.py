@@ -18,8 +18,8 @@ SRC = os.path.join(HERE, "csrc", "ig_hip.hip")
 SRC_HOST = os.path.join(HERE, "csrc", "ig_draw.cpp")  # host-only part: the candidate draw
 DEPS = [SRC, SRC_HOST] + [os.path.join(HERE, "csrc", f) for f in ("ig_ops.cuh", "ig_common.cuh", "ig_model.cuh", "ig_kernels_setup.cuh",
                                                           "ig_kernels_score.cuh", "ig_kernels_screen.cuh", "ig_kernels_commit.cuh",
-                                                          "ig_kernels_nuis.cuh", "ig_kernels_wave.cuh", "ig_kernels_genome.cuh", "ig_kernels_rows.cuh", "ig_kernels_map.cuh", "ig_kernels_law.cuh", "ig_kernels_junc.cuh", "ig_kernels_lift.cuh", "ig_kernels_join.cuh", "ig_kernels_emap.cuh", "ig_kernels_place.cuh", "ig_kernels_orient.cuh", "ig_kernels_bal.cuh", "ig_kernels_gap.cuh", "ig_kernels_zoom.cuh", "ig_kernels_segplace.cuh", "ig_kernels_edit.cuh", "ig_kernels_cutjoin.cuh", "ig_host_core.inc", "ig_host_upload.inc", "ig_host_genome.inc", "ig_host_rows.inc",
-                                                          "ig_host_map.inc", "ig_host_law.inc", "ig_host_junc.inc", "ig_host_lift.inc", "ig_host_join.inc", "ig_host_emap.inc", "ig_host_place.inc", "ig_host_orient.inc", "ig_host_bal.inc", "ig_host_gap.inc", "ig_host_zoom.inc", "ig_host_segplace.inc", "ig_host_edit.inc", "ig_host_cutjoin.inc",
+                                                          "ig_kernels_nuis.cuh", "ig_kernels_wave.cuh", "ig_kernels_genome.cuh", "ig_kernels_rows.cuh", "ig_kernels_map.cuh", "ig_kernels_law.cuh", "ig_kernels_junc.cuh", "ig_kernels_lift.cuh", "ig_kernels_join.cuh", "ig_kernels_emap.cuh", "ig_kernels_place.cuh", "ig_kernels_orient.cuh", "ig_kernels_bal.cuh", "ig_kernels_gap.cuh", "ig_kernels_zoom.cuh", "ig_kernels_segplace.cuh", "ig_kernels_edit.cuh", "ig_kernels_cutjoin.cuh", "ig_kernels_pairs.cuh", "ig_host_core.inc", "ig_host_upload.inc", "ig_host_genome.inc", "ig_host_rows.inc",
+                                                          "ig_host_map.inc", "ig_host_law.inc", "ig_host_junc.inc", "ig_host_lift.inc", "ig_host_join.inc", "ig_host_emap.inc", "ig_host_place.inc", "ig_host_orient.inc", "ig_host_bal.inc", "ig_host_gap.inc", "ig_host_zoom.inc", "ig_host_segplace.inc", "ig_host_edit.inc", "ig_host_cutjoin.inc", "ig_host_pairs.inc",
                                                           "ig_host_batch.inc", "ig_host_nuis.inc", "ig_host_debug.inc")] + \
        [os.path.join(ROOT, "include", f) for f in ("ig_detmath.h", "ig_detmath_tables.h", "instagraal_hip.h")]
 
@@ -39,6 +39,7 @@ BALANCE_FORMS = ("default", "wave", "packed")  # ig_debug_balance_form
 EDIT_PASSES = ("plan", "state", "tables", "delta", "zero", "whole")  # ig_debug_edit_time
 CUT_JOIN_PASSES = ("span", "scan", "zero", "count", "rowscan", "scatter", "sort_short", "sort_lds", "sort_long", "reduce", "terms", "join_zero")  # ig_debug_cut_join_time
 CUT_JOIN_LDS_PAIRS = 256  # CJ_LDS_PAIRS (csrc/ig_kernels_cutjoin.cuh): pairs up to which the join pass keeps its accumulators in LDS
+PAIRS_PASSES = ("lift",) + ASSEMBLY_CONTACTS_PASSES + ("law",)  # ig_debug_pairs_time
 CONTIG_ARRAYS = ("head_bin", "tail_bin", "n_sub", "length_bp")  # ig_join_scores_fetch: per linear contig
 MAX_CANDIDATES = 16
 
@@ -952,6 +953,106 @@ class Context:
         ne, sc = C.c_int64(), np.zeros(8, np.int64)
         _ck(lib().ig_assembly_contacts_coarsen(self._h, _p(t), C.c_int64(t.size), C.c_int64(int(n_coarse)), C.byref(ne), _p(sc)))
         return self._lift_result(n_coarse, ne, sc)
+
+    # ---- read pairs lifted onto the current genome (the rule: pairs_lift.py)
+    @staticmethod
+    def _i32(a, what):
+        src = np.asarray(a)
+        if src.ndim != 1 or not (src.size == 0 or src.dtype.kind in "iu"):
+            raise HipError("%s: one vector of integers" % what)
+        if src.size and (int(src.min()) < -(1 << 31) or int(src.max()) >= 1 << 31):
+            raise HipError("%s: out of range (32 bits)" % what)
+        return np.ascontiguousarray(src, np.int32)
+
+    def pairs_begin(self, table, reserve_pairs=0):
+        """opens the session over ``pairs_lift.source_table``'s dict: the table goes to the device, the store is empty"""
+        iv = table["intervals"]
+        rowptr = self._i32(table["src_rowptr"], "pairs_begin: src_rowptr")
+        cols = [self._i32(iv[k], "pairs_begin: " + k) for k in ("src_start", "src_end", "new_start", "scaffold", "position")]
+        rev = np.ascontiguousarray(iv["reversed"] != 0, np.uint8)
+        slen = np.ascontiguousarray(table["scaffold_len"], np.int64)
+        unit = self._i32(table["bin_unit"], "pairs_begin: bin_unit")
+        _ck(lib().ig_pairs_begin(self._h, _p(rowptr), C.c_int32(rowptr.size - 1), _p(cols[0]), _p(cols[1]), _p(cols[2]), _p(cols[3]), _p(rev), _p(cols[4]),
+                                 C.c_int64(iv.size), _p(slen), C.c_int32(slen.size), _p(unit), C.c_int64(unit.size), C.c_int64(int(table["n_bin_units"])),
+                                 C.c_int64(int(reserve_pairs))))
+
+    def pairs_lift(self, c1, p1, c2, p2, strands=None, outputs=True):
+        """one chunk: contig ids and 1-based positions (a position outside 1 .. 2^31 - 1 is covered by nothing), ``strands``: uint8 codes
+        or None -> the dict ``pairs_lift.lift_host`` returns (without the per-pair arrays where ``outputs`` is False) plus
+        ``pairs_stored``; the kept pairs are appended to the session's store"""
+        from .pairs_lift import SCALARS
+
+        def ids(a):
+            if isinstance(a, np.ndarray) and a.dtype == np.int32:  # (as they are: a negative id is an unknown contig)
+                return np.ascontiguousarray(a.ravel())
+            a = np.asarray(a, np.int64).ravel()
+            return np.ascontiguousarray(np.where((a < 0) | (a >= 1 << 31), -1, a), np.int32)
+
+        def pos(a):
+            if isinstance(a, np.ndarray) and a.dtype == np.int32:  # (as they are: a position below 1 is covered by nothing)
+                return np.ascontiguousarray(a.ravel())
+            a = np.asarray(a, np.int64).ravel()
+            return np.ascontiguousarray(np.where((a < 1) | (a >= 1 << 31), 0, a), np.int32)
+
+        a = [ids(c1), pos(p1), ids(c2), pos(p2)]
+        n = a[0].size
+        if any(x.size != n for x in a):
+            raise HipError("pairs_lift: the four arrays of the pairs have one length")
+        st = None
+        if strands is not None:
+            st = np.ascontiguousarray(strands, np.uint8).ravel()
+            if st.size != n:
+                raise HipError("pairs_lift: one strand code per pair")
+        sc = np.zeros(8, np.int64)
+        out = {}
+        if outputs:
+            for k in ("scaffold1", "pos1", "unit1", "scaffold2", "pos2", "unit2"):
+                out[k] = np.zeros(n, np.int32)
+            for k in ("rev1", "rev2", "status"):
+                out[k] = np.zeros(n, np.uint8)
+        o = lambda k: _p(out[k]) if outputs else None  # noqa: E731
+        _ck(lib().ig_pairs_lift(self._h, _p(a[0]), _p(a[1]), _p(a[2]), _p(a[3]), None if st is None else _p(st), C.c_int64(n), o("scaffold1"), o("pos1"), o("unit1"),
+                                o("rev1"), o("scaffold2"), o("pos2"), o("unit2"), o("rev2"), o("status"), _p(sc)))
+        out.update((k, int(v)) for k, v in zip(SCALARS[:6], sc))
+        return out
+
+    def pairs_pixels(self, kind, binsize=0):
+        """the pixels of the stored pairs (``kind``: one of ``pairs_lift.UNIT_KINDS``) as the handle's assembly-contacts snapshot -> dict
+        as ``assembly_contacts_units``; the entries come through ``assembly_contacts_fetch``, a zoom chain through
+        ``assembly_contacts_coarsen``"""
+        from .pairs_lift import UNIT_KINDS
+
+        nu, ne, sc = C.c_int64(), C.c_int64(), np.zeros(8, np.int64)
+        _ck(lib().ig_pairs_pixels_build(self._h, C.c_int32(UNIT_KINDS.index(kind) if kind in UNIT_KINDS else int(kind)), C.c_int64(int(binsize)), C.byref(nu),
+                                        C.byref(ne), _p(sc)))
+        return self._lift_result(nu.value, ne, sc)
+
+    def pairs_law(self, edges_bp, flip_strands=True):
+        """-> (counts int64 [4][n_edges - 1], dict of pairs_stored, pairs_cis, pairs_trans)"""
+        e = np.ascontiguousarray(edges_bp, np.int64).ravel()
+        counts, sc = np.zeros((4, max(e.size - 1, 1)), np.int64), np.zeros(8, np.int64)
+        _ck(lib().ig_pairs_law(self._h, _p(e), C.c_int32(e.size), C.c_int32(int(bool(flip_strands))), _p(counts), _p(sc)))
+        return counts, dict(pairs_stored=int(sc[0]), pairs_cis=int(sc[1]), pairs_trans=int(sc[2]))
+
+    def pairs_clear(self):
+        _ck(lib().ig_pairs_clear(self._h))
+
+    def pairs_end(self):
+        _ck(lib().ig_pairs_end(self._h))
+
+    def debug_pairs_time(self, c1, p1, c2, p2, strands, kind, binsize, edges_bp, n=1):
+        """the lift of the chunk, the law and the pixel build n times with hipEvents around each pass -> (ms [n, 9]: ``PAIRS_PASSES``,
+        checksum)"""
+        from .pairs_lift import UNIT_KINDS
+
+        a = [self._i32(x, "debug_pairs_time") for x in (c1, p1, c2, p2)]
+        st = None if strands is None else np.ascontiguousarray(strands, np.uint8).ravel()
+        e = np.ascontiguousarray(edges_bp, np.int64).ravel()
+        ms = np.zeros((int(n), len(PAIRS_PASSES)), np.float32)
+        ck = C.c_int64()
+        _ck(lib().ig_debug_pairs_time(self._h, _p(a[0]), _p(a[1]), _p(a[2]), _p(a[3]), None if st is None else _p(st), C.c_int64(a[0].size),
+                                      C.c_int32(UNIT_KINDS.index(kind)), C.c_int64(int(binsize)), _p(e), C.c_int32(e.size), C.c_int32(int(n)), _p(ms), C.byref(ck)))
+        return ms, int(ck.value)
 
     def balance_build_units(self, unit, n_units, ignore_diags=2):
         """``balance_build("bin")`` with the caller's unit of every position -> the dict ``balance_build`` returns (level: "units")"""

@@ -972,7 +972,8 @@ class sampler:  # noqa: N801 - the reference's class name
         entries (u, u), first in their rows, as ``contact_map`` adds it to its image; their total is ``contacts_diagonal``.
         ``balance=True`` (or a dict of ``balance()``'s parameters): the dict gains ``weight`` (f64 per unit, ``balance(level)``) and
         ``balanced`` (count * weight[row] * weight[col] per entry; nan where a unit has no weight).
-        No reference counterpart on the device (post.py lifts the raw pairs over)."""
+        The reference's counterpart, post.py, lifts the raw read pairs over instead: that is ``pairs_contacts``, which is not
+        capped at sub-fragment resolution."""
         from . import assembly_contacts as ac
 
         res, order, table, diag, total = self._assembly_contacts_frame(level, diagonal)
@@ -1075,7 +1076,8 @@ class sampler:  # noqa: N801 - the reference's class name
         scaffold), or a caller's ``(unit, n_units)`` per position.  -> the dict ``assembly_contacts`` returns, with ``bins`` the table of
         the fixed bins (contig, start, end; None for a caller's units), ``unit`` per position and ``units_without_position`` -- the
         fixed bins no midpoint falls into: above 0 the resolution is below what the fragments carry.  ``diagonal`` and ``balance`` as
-        in ``assembly_contacts``.  No reference counterpart on the device (post.py bins the raw pairs on the host)."""
+        in ``assembly_contacts``.  The reference's post.py bins the raw read pairs instead: ``pairs_contacts(pairs, binsize)`` does that on the
+        device, a pair counted where it falls."""
         from . import assembly_contacts as ac, balance as bal, zoom_levels as zl
 
         order, table_sub, d = self._zoom_frame(diagonal)
@@ -1147,6 +1149,231 @@ class sampler:  # noqa: N801 - the reference's class name
         finally:
             self.ctx.assembly_contacts_release()
         return out
+
+    # ------------------------------------------------------- read pairs lifted
+    contig_names = None  # {input contig name: id in S_o_A_sub_frags["id_c"]} (``simulation`` sets it): lets the pairs come by name
+
+    def pairs_begin(self, reserve_pairs=0):
+        """Opens a pairs session on the genome as it stands (``ig_pairs_begin``; the rule: ``pairs_lift.py``): the source table of
+        ``pairs_lift.source_table`` goes to the device, the store of lifted pairs is empty.  A session open already is ended.  The
+        session belongs to this genome: once a move or an edit has changed it the device REFUSES every further call of the session
+        (``HipError``) until it is ended and begun again.  -> the table"""
+        from . import assembly_contacts as ac, pairs_lift as pl
+
+        self.pairs_end()
+        sub = self.S_o_A_sub_frags
+        order = self.ctx.contact_map_order().astype(np.int64)
+        parent = self.np_sub_frags_2_frags["x"].astype(np.int64)
+        g = self.gpu_vect_frags.copy_from_gpu()
+        table = pl.source_table(sub["id_c"], sub["len_bp"], order, parent, g.id_c, g.ori, start_bp=sub["start_bp"] if "start_bp" in sub else None,
+                                names=self.contig_names)
+        table["table_sub"] = ac.bins_table(order, parent, g.id_c, g.ori, sub["len_bp"], "sub")
+        table["table_bin"] = ac.bins_table(order, parent, g.id_c, g.ori, sub["len_bp"], "bin")
+        self.ctx.pairs_begin(table, reserve_pairs)
+        self._pairs = table
+        return table
+
+    def pairs_end(self):
+        """ends the open pairs session, if there is one: the store and the table leave the device"""
+        if getattr(self, "_pairs", None) is not None:
+            self._pairs = None
+            self.ctx.pairs_end()
+
+    def lift_pairs(self, contig, pos1, contig2, pos2, strands=None):
+        """Lifts read pairs from input-contig coordinates (``contig``, ``contig2``: ids as in ``S_o_A_sub_frags["id_c"]``, or names;
+        1-based positions; ``strands``: ``pairs_lift.strand_codes`` or None) to the genome as it stands (``ig_pairs_lift``) -> the
+        dict ``pairs_lift.lift_host`` returns: scaffold (its rank among the placed ones), 1-based position, position of the interval
+        hit and reversed bit per end, the status code per pair, the scalars.  The kept pairs are appended to the store of the open
+        session (one is opened if need be), from which ``pairs_contacts(None)`` and ``pairs_distance_law(None)`` are built."""
+        from . import pairs_lift as pl
+
+        if getattr(self, "_pairs", None) is None:
+            self.pairs_begin()
+        t = self._pairs
+        return self.ctx.pairs_lift(pl.contig_ids(t, contig), pos1, pl.contig_ids(t, contig2), pos2, strands)
+
+    def _pairs_fresh(self):
+        """a session of its own for a call that brings its pairs: REFUSED while a session is open -- its store holds what the caller
+        lifted, and is not thrown away behind their back (``pairs_end()`` first, or pass ``pairs=None`` to build from that store)"""
+        if getattr(self, "_pairs", None) is not None:
+            raise ValueError("pairs: a session is open and its store would be lost: pairs_end() first, or pass pairs=None to build from what it holds")
+        return self.pairs_begin()
+
+    def _pairs_load(self, pairs, chunk_pairs=None):
+        """``pairs``: None (the open session's store as it is), a path (a 4DN pairs file, read chunk by chunk) or arrays ``(contig,
+        pos1, contig2, pos2[, strands])``: a fresh session with them lifted (refused while one is open: ``_pairs_fresh``) -> the summed
+        scalars (plus ``malformed`` for a file)"""
+        from . import pairs_lift as pl
+
+        if pairs is None:
+            if getattr(self, "_pairs", None) is None:
+                raise ValueError("pairs: no session is open (lift_pairs first, or give the pairs)")
+            return {}
+        t = self._pairs_fresh()
+        total = dict.fromkeys(pl.SCALARS[:5], 0)
+        try:
+            if isinstance(pairs, (str, bytes)) or hasattr(pairs, "__fspath__"):
+                if t["names"] is None:
+                    raise ValueError("pairs: a pairs file names its contigs and this sampler has no contig_names")
+                malformed = 0
+                for ch in pl.read_pairs(pairs, t["names"], chunk_pairs or pl.DEFAULT_CHUNK_PAIRS):
+                    malformed = ch["malformed"]
+                    res = self.ctx.pairs_lift(ch["c1"], ch["p1"], ch["c2"], ch["p2"], ch["strands"], outputs=False)
+                    for k in total:
+                        total[k] += res[k]
+                total["malformed"] = malformed
+            else:
+                res = self.ctx.pairs_lift(pl.contig_ids(t, pairs[0]), pairs[1], pl.contig_ids(t, pairs[2]), pairs[3], pairs[4] if len(pairs) > 4 else None, outputs=False)
+                total.update((k, res[k]) for k in total)
+        except BaseException:
+            self.pairs_end()  # (the session was this call's own: a failed load leaves none)
+            raise
+        return total
+
+    def _pairs_bins(self, kind, binsize):
+        from . import assembly_contacts as ac, zoom_levels as zl
+
+        t = self._pairs
+        if kind == "sub":
+            return t["table_sub"]
+        if kind == "bin":
+            return t["table_bin"]
+        if kind == "scaffold":
+            return zl.scaffold_table(t["table_sub"])
+        return zl.binnify(ac.chrom_sizes(t["table_sub"]), binsize)
+
+    def pairs_contacts(self, pairs, binsize=None, units=None, balance=False):
+        """The map of read pairs at any resolution (``ig_pairs_pixels_build``): the pairs lifted onto the genome as it stands and
+        counted per pixel -- ``binsize`` in bp (the bins of ``zoom_levels.binnify``; a pair counts where it falls), or ``units`` "sub"
+        (the positions), "bin" (the placed bins: the rows of info_frags.txt) or "scaffold".  ``pairs``: a path or arrays -- lifted in a
+        session of the call's own, ended behind it, and REFUSED (ValueError) while a session is open, whose store it would discard -- or
+        None: the open session's store, which stays.  -> the dict ``resolution_contacts`` returns (rowptr, col, count, the scalars, ``bins``, ``chrom_sizes``,
+        ``binsize``) plus the lift's scalars.  ``balance``: not offered here -- the balancer builds its rows from the contacts, not
+        from a built snapshot."""
+        from . import assembly_contacts as ac, pairs_lift as pl
+
+        if balance:
+            raise NotImplementedError("pairs_contacts: balancing a map of pairs is not offered (the balancer reads the contacts, not a built snapshot)")
+        if (binsize is None) == (units is None):
+            raise ValueError("pairs: give binsize (bp) or units (\"sub\", \"bin\", \"scaffold\"), not both")
+        lifted = self._pairs_load(pairs)
+        try:
+            kind, B, _, _ = pl.check_units(self._pairs, units if binsize is None else binsize)
+            res = self.ctx.pairs_pixels(kind, B)
+            try:
+                col, count = self.ctx.assembly_contacts_fetch(0, res["n_entries"])
+            finally:
+                self.ctx.assembly_contacts_release()
+            res.pop("n_entries")
+            res.update(col=col, count=count, bins=self._pairs_bins(kind, B), chrom_sizes=ac.chrom_sizes(self._pairs["table_sub"]), binsize=B if kind == "binsize" else None,
+                       units=kind)
+            res.update(lifted)
+        finally:
+            if pairs is not None:
+                self.pairs_end()
+        return res
+
+    def write_pairs_zoom_levels(self, folder, pairs, resolutions=_zoom_levels.DEFAULT_RESOLUTIONS, scaffolds=True, balance=False, block_rows=None):
+        """``write_zoom_levels`` from read pairs: the same folders and writers, every level from the store of lifted pairs -- one
+        build at the finest bin size of a run of multiples, coarsenings on the device behind it (``zoom_levels.plan``), the scaffold
+        matrix coarsened from the last level.  -> a list, per level: ``level``, ``made``, ``folder``, the scalars, ``pixels_written``."""
+        from . import assembly_contacts as ac, zoom_levels as zl
+
+        if balance:
+            raise NotImplementedError("write_pairs_zoom_levels: balancing a map of pairs is not offered (the balancer reads the contacts, not a built snapshot)")
+        res_list = zl.check_resolutions(resolutions)
+        steps = list(zip(res_list, zl.plan(res_list)))
+        rows = ac.DEFAULT_BLOCK_ROWS if block_rows is None else block_rows
+        lifted = self._pairs_load(pairs)
+        out = []
+        try:
+            sizes = ac.chrom_sizes(self._pairs["table_sub"])
+            for i, (B, made) in enumerate(steps + ([("scaffolds", ("coarsen", "scaffolds"))] if scaffolds else [])):
+                if B == "scaffolds":
+                    bins, where = zl.scaffold_table(self._pairs["table_sub"]), zl.scaffold_folder(folder)
+                    res = self.ctx.assembly_contacts_coarsen(*zl.scaffold_map(sizes, res_list[-1]))
+                else:
+                    bins, where = zl.binnify(sizes, B), zl.level_folder(folder, B)
+                    if made[0] == "direct":
+                        res = self.ctx.pairs_pixels("binsize", B)
+                    else:
+                        res = self.ctx.assembly_contacts_coarsen(*zl.coarse_map(sizes, res_list[i - 1], made[1]))
+                n = zl.write_level(where, bins, res["rowptr"], self.ctx.assembly_contacts_fetch, rows)
+                one = {k: res[k] for k in ac.SCALARS}
+                one.update(level=B, made=made, folder=where, pixels_written=n)
+                one.update(lifted)
+                out.append(one)
+        finally:
+            self.ctx.assembly_contacts_release()
+            if pairs is not None:
+                self.pairs_end()
+        return out
+
+    def pairs_distance_law(self, pairs, edges_bp=None, flip_strands=True):
+        """P(s) of the read pairs on the genome as it stands, per strand combination (``ig_pairs_law``): the lifted pairs with both ends
+        on one scaffold by |pos2 - pos1|.  ``edges_bp``: None for the distance law's default edges in bp.  ``flip_strands``: an end on
+        a reversed bin has its strand flipped; False leaves the strands as read, as the reference does.  -> dict: ``counts`` (int64
+        [4][n_edges - 1]: ++ +- -+ --), ``edges_bp``, ``norm_p`` (``pairs_lift.normalise``), pairs_stored / pairs_cis / pairs_trans and
+        the lift's scalars."""
+        from . import pairs_lift as pl
+
+        lifted = self._pairs_load(pairs)
+        try:
+            if edges_bp is None:
+                edges_bp = pl.default_edges_bp(self.mean_kb(), max(float(self._pairs["scaffold_len"].max(initial=0)) / 1000.0, 1.0))
+            e = pl.check_edges(edges_bp)
+            counts, sc = self.ctx.pairs_law(e, flip_strands)
+        finally:
+            if pairs is not None:
+                self.pairs_end()
+        out = dict(counts=counts, edges_bp=e, norm_p=pl.normalise(counts, e), flip_strands=bool(flip_strands))
+        out.update(sc)
+        out.update(lifted)
+        return out
+
+    def display_pairs_distance_law(self, filename, pairs, edges_bp=None, flip_strands=True):
+        """``pairs_distance_law`` as a log-log plot, one curve per strand combination -> the law"""
+        from matplotlib.backends.backend_agg import FigureCanvasAgg
+        from matplotlib.figure import Figure
+
+        from . import distance_law as dlaw, pairs_lift as pl
+
+        law = self.pairs_distance_law(pairs, edges_bp, flip_strands)
+        x = dlaw.bin_centres(law["edges_bp"])
+        fig = Figure(figsize=(6, 4.5))
+        FigureCanvasAgg(fig)
+        ax = fig.subplots()
+        for k, name in enumerate(pl.STRAND_COMBOS):
+            y = law["norm_p"][k]
+            ok = np.isfinite(y) & (y > 0) & (x > 0)
+            if ok.any():
+                ax.loglog(x[ok], y[ok], label=name)
+        ax.set_xlabel("distance (bp)")
+        ax.set_ylabel("P(s)")
+        if ax.get_legend_handles_labels()[0]:
+            ax.legend()
+        fig.savefig(filename, dpi=150, bbox_inches="tight")
+        return law
+
+    def write_lifted_pairs(self, pairs_path, out_path, chunk_pairs=None, keep_session=False):
+        """Rewrites a 4DN pairs file in the coordinates of the genome as it stands, gzip-compressed (``pairs_lift.write_lifted_pairs``:
+        the header rewritten as the reference does, the kept pairs in input order), lifting on the device -> the scalars, ``malformed``
+        and ``lines``.  The text is parsed and formatted on the host: that, not the lift, bounds this call -- so ``keep_session=True``
+        leaves the session open with every kept pair (and its strands) in the store: ``pairs_contacts(None, ...)``,
+        ``write_pairs_zoom_levels(folder, None, ...)`` and ``pairs_distance_law(None)`` then build from the one reading of the file
+        (``pairs_end()`` behind them).  Refused while a session is open, as every call that brings its pairs."""
+        from . import pairs_lift as pl
+
+        t = self._pairs_fresh()
+        done = False
+        try:
+            out = pl.write_lifted_pairs(pairs_path, out_path, t, lambda c1, p1, c2, p2, strands: self.ctx.pairs_lift(c1, p1, c2, p2, strands),
+                                        chunk_pairs or pl.DEFAULT_CHUNK_PAIRS)
+            done = True
+            return out
+        finally:
+            if not (done and keep_session):
+                self.pairs_end()
 
     # ---------------------------------------------------------------- balance
     def balance(self, level="bin", max_side=2048, ignore_diags=2, min_nnz=10, min_count=0, mad_max=0, tol=1e-5, max_iters=200):

@@ -135,6 +135,7 @@ class simulation:
         self.n_frags = args["n_new_frags"]
         self.new_S_o_A_frags, self.new_sub_S_o_A_frags = args["S_o_A_frags"], args["S_o_A_sub_frags"]
         self.sampler = sampler_lib(**args, device_id=device_id, keep_all_scores=False)  # (nobody reads them: CL:1414-1454)
+        self.sampler.contig_names = {n: i + 1 for i, n in enumerate(self.hic_pyr.list_contigs_name)}  # (the ids of S_o_A_sub_frags["id_c"]: pairs come by name)
         # SS:157-171
         g = self.sampler.gpu_vect_frags
         g.copy_from_gpu()
@@ -195,7 +196,7 @@ class instagraal_class:
 
     def full_em(self, n_cycles, n_neighbours, bomb, id_start_sample_param, save_matrix=False, save_law=False, save_junctions=False,
                 save_contacts=False, save_joins=False, save_residuals=False, save_placements=False, save_orientations=False, save_weights=False, save_gaps=False,
-                save_resolutions=False, save_segment_placements=False, polish=False, save_cut_join=False):  # IG:196-291
+                save_resolutions=False, save_segment_placements=False, polish=False, save_cut_join=False, pairs=None, save_lifted_pairs=False):  # IG:196-291
         sampler = self.simulation.sampler
         if bomb:
             sampler.bomb_the_genome()
@@ -259,6 +260,20 @@ class instagraal_class:
 
             cj.write_cuts(self._out("cuts.txt"), sampler.weakest_cuts())
             cj.write_links(self._out("links.txt"), sampler.strongest_joins())
+        if pairs is not None:  # (once, behind the last cycle and the polishing: the read pairs on the final genome, at bp resolution)
+            from . import pairs_lift as pl, zoom_levels as zl
+
+            sampler.pairs_end()
+            try:  # (ONE reading of the text, which is what bounds this block: lifted once into one session, everything built from its store)
+                if save_lifted_pairs:
+                    sampler.write_lifted_pairs(pairs, self._out("lifted.pairs.gz"), keep_session=True)
+                else:
+                    sampler._pairs_load(pairs)
+                sampler.write_pairs_zoom_levels(self._out("pairs_zoom_levels"), None, zl.DEFAULT_RESOLUTIONS if save_resolutions in (False, True) else tuple(save_resolutions))
+                law = sampler.pairs_distance_law(None)
+                pl.write_law(self._out("pairs_law.txt"), law["counts"], law["edges_bp"])
+            finally:
+                sampler.pairs_end()
         if save_contacts:  # (once, behind the last cycle: the table is large)
             sampler.write_assembly_contacts(self._out("assembly_contacts"), level="sub")
         if save_resolutions:  # (once, behind the last cycle, beside assembly_contacts/: the fixed-resolution maps and the scaffold matrix)
@@ -311,7 +326,7 @@ def run_instagraal(hic_folder, reference_fa, output_folder=None, level=4, cycles
                    circular=False, bomb=False, pyramid_only=False, save_pickle=False, save_matrix=False, simple=False, save_law=False,
                    save_junctions=False, save_contacts=False, save_joins=False, save_residuals=False, save_placements=False,
                    save_orientations=False, save_weights=False, save_gaps=False, save_resolutions=False, save_segment_placements=False, polish=False,
-                   save_cut_join=False):
+                   save_cut_join=False, pairs=None, save_lifted_pairs=False):
     """IG:502-581 (defaults of cli/main.py: level 4, 100 cycles, 5 neighbours, 1 std).  The three trailing switches of the
     reference's signature (IG:512-514) are accepted: ``save_pickle`` dumps the run object to ``graal.pkl`` as the reference
     tries to (IG:589-594: a warning when it cannot be pickled -- device handles here, h5py handles there); ``save_matrix``
@@ -357,7 +372,12 @@ def run_instagraal(hic_folder, reference_fa, output_folder=None, level=4, cycles
     ``genome.fasta`` and those reports then describe the polished genome (``rearrange.py``); ``polish="all"`` also proposes
     the weakest cuts and the strongest joins (``cut_join.py``); ``save_cut_join`` (an addition too) writes ``cuts.txt`` and ``links.txt``
     once, behind the last cycle and the polishing: the cuts and the links with the largest positive likelihood change, each with its
-    edit (``sampler.weakest_cuts``, ``sampler.strongest_joins``)."""
+    edit (``sampler.weakest_cuts``, ``sampler.strongest_joins``); ``pairs`` (an addition too: the path of the 4DN pairs file the
+    contacts came from, aligned to the input contigs) writes once, behind the last cycle and any polishing, ``pairs_zoom_levels/`` -- the
+    folders of ``zoom_levels/`` built from the read pairs lifted onto the final genome, a pair counted where it falls (bin sizes:
+    ``save_resolutions`` where it is a tuple, else the defaults) -- and ``pairs_law.txt``, their distance histogram per strand
+    combination; with ``save_lifted_pairs`` also ``lifted.pairs.gz``, the pairs file in the coordinates of ``genome.fasta``
+    (``sampler.write_pairs_zoom_levels``, ``sampler.pairs_distance_law``, ``sampler.write_lifted_pairs``)."""
     import warnings
 
     if simple and not pyramid_only:
@@ -379,7 +399,7 @@ def run_instagraal(hic_folder, reference_fa, output_folder=None, level=4, cycles
     p2.full_em(n_cycles=cycles, n_neighbours=neighborhood, bomb=bomb, id_start_sample_param=4, save_matrix=save_matrix, save_law=save_law,
                save_junctions=save_junctions, save_contacts=save_contacts, save_joins=save_joins, save_residuals=save_residuals, save_placements=save_placements,
                save_orientations=save_orientations, save_weights=save_weights, save_gaps=save_gaps, save_resolutions=save_resolutions,
-               save_segment_placements=save_segment_placements, polish=polish, save_cut_join=save_cut_join)
+               save_segment_placements=save_segment_placements, polish=polish, save_cut_join=save_cut_join, pairs=pairs, save_lifted_pairs=save_lifted_pairs)
     if save_pickle:  # IG:589-594
         import pickle
 
