@@ -816,6 +816,43 @@ int ig_pairs_end(ig_ctx* ctx);
  * and the histogram of the last repeat, each word weighted by its place */
 int ig_debug_pairs_time(ig_ctx* ctx, const int32_t* c1, const int32_t* p1, const int32_t* c2, const int32_t* p2, const uint8_t* strands, int64_t n_pairs, int32_t kind,
                         int64_t binsize, const int64_t* edges_bp, int32_t n_edges, int32_t n, float* ms_n, int64_t* checksum);
+
+/* ---- the input folder from an assembly FASTA and read pairs: the restriction digest of the records, G + C per fragment, the fragment
+ * of every pair end and the pixels (the rule, stated once: instagraal_amd/pre.py).  A SESSION lives between
+ * ig_pre_begin and ig_pre_end (ig_destroy frees a live one) on a created handle; it needs no contacts and no state and changes nothing
+ * a move reads; no nuisance step or chain may be in flight.
+ *
+ * seq: n_bytes bytes, the records one behind the other with a zero byte (the separator) behind each: rec_off[0] == 0, rec_off[r + 1]
+ * == rec_off[r] + rec_len[r] + 1, n_bytes == rec_off[n_records - 1] + rec_len[n_records - 1] + 1.  The offsets are 64-bit (a genome
+ * may exceed 2^31 bytes), a record is 1 .. 2^31 - 2 bases of ABCDGHKMNRSTVWY in either case; anything else is refused naming the record
+ * and the position.  The bytes go to the device in pieces. */
+int ig_pre_begin(ig_ctx* ctx, const uint8_t* seq, int64_t n_bytes, const int64_t* rec_off, const int32_t* rec_len, int32_t n_records);
+/* The digest under 1 .. 4 enzymes: site_len[e] (1 .. 16) letters, the cut behind cut[e] (0 .. site_len[e]) of them, masks[e][16]: per
+ * site letter the bits of the bases it accepts (A 1, C 2, G 4, T 8), or 16: any letter (the site letter N).  A match at the 0-based
+ * start s of a record cuts at s + cut; the cuts of all enzymes with 0 and the record's length bound its fragments.
+ * frags_per_record[n_records], *n_frags: their numbers.  ms (may be NULL): the times of the four passes {sites, scan, cuts, fragments}.
+ * An earlier digest of the session, its store and its pixels are gone. */
+int ig_pre_digest(ig_ctx* ctx, int32_t n_enzymes, const int32_t* site_len, const int32_t* cut, const uint8_t* masks, int64_t* frags_per_record, int64_t* n_frags,
+                  float* ms);
+/* the fragments first .. first + n - 1 in the order of the records: record, start, end (0-based, half-open, inside the record), G + C */
+int ig_pre_fragments(ig_ctx* ctx, int64_t first, int64_t n, int32_t* frag_rec, int32_t* start, int32_t* end, int32_t* gc_count);
+/* One chunk of pairs: the record (-1: unknown) and the 1-based position of both ends.  The fragment of an end is the last of its
+ * record that starts at or before position - 1: none for a position <= 0 or an unknown record, the record's last for a position beyond
+ * its end.  A pair with both is appended to the session's store, which grows.  scalars: the chunk's {pairs_in, pairs_kept,
+ * end1_without_fragment, end2_without_fragment, ends_beyond_record}, the pairs stored in all, 0, 0.  ms (may be NULL): the kernel's
+ * time.  An earlier build's pixels are gone. */
+int ig_pre_add_pairs(ig_ctx* ctx, const int32_t* c1, const int32_t* p1, const int32_t* c2, const int32_t* p2, int64_t n, int64_t scalars[8], float* ms);
+/* The pixels of the store: every stored pair adds 1 at (min, max) of its two fragments; rows by bin1, columns ascending, equal ones
+ * summed.  scalars: {pairs_in, pairs_kept, end1_without_fragment, end2_without_fragment, ends_beyond_record, pixels} over every chunk
+ * since the digest or ig_pre_clear, the fragments, the stored pairs.  ms (may be NULL): the seven passes of the row builder. */
+int ig_pre_pixels_build(ig_ctx* ctx, int64_t* n_pixels, int64_t scalars[8], float* ms);
+/* rowptr[n_frags + 1] of the built pixels (n_rowptr: the caller's capacity) */
+int ig_pre_pixels_rows(ig_ctx* ctx, int64_t* rowptr, int64_t n_rowptr);
+/* the pixels first .. first + n - 1 in the order of (bin1, bin2): bin2 and the count */
+int ig_pre_pixels_fetch(ig_ctx* ctx, int64_t first, int64_t n, int32_t* col, int64_t* count);
+/* empties the store and its scalars and drops the pixels; the sequence, the digest and the buffers stay */
+int ig_pre_clear(ig_ctx* ctx);
+int ig_pre_end(ig_ctx* ctx);
 #ifdef __cplusplus
 }
 #endif

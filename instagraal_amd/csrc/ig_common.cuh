@@ -658,6 +658,31 @@ struct PairsBuf {
     unsigned long long stamp = 0;         /* of the state the table was made from: a session does not outlive a change of the genome */
 };
 
+/* the input folder from a FASTA and read pairs (ig_kernels_pre.cuh): one session between ig_pre_begin and ig_pre_end, freed by
+ * free_pre_buffers (ig_host_pre.inc): the sequence bytes, the fragment table of the last digest, the store of the kept pairs (grows
+ * under the free-memory guard), the staging arrays of a piece of a chunk (grow-only) and the built pixels */
+struct PreBuf {
+    bool live = false, digested = false, built = false;
+    int R = 0;                             /* records */
+    long long n_bytes = 0, n_runs = 0, W = 0; /* the coordinate: bytes, runs of 16, 64-bit bitmap words */
+    unsigned char* seq = nullptr;          /* [16 (n_runs + 1)] the records and their separators, zero behind them */
+    long long* off = nullptr;              /* [R] */
+    int* len = nullptr;                    /* [R] */
+    std::vector<long long> h_first;        /* [R + 1] the records' first fragments on the host */
+    long long n_frags = 0;
+    long long* rec_first = nullptr;        /* [R + 1] the first global fragment of every record */
+    int *frag_rec = nullptr, *start = nullptr, *end = nullptr, *gc = nullptr; /* [n_frags] */
+    int2* store = nullptr;                 /* [cap] (min, max) of the two fragments of a kept pair */
+    long long cap = 0, size = 0;
+    long long totals[5] = {0, 0, 0, 0, 0}; /* PRE_NS scalars summed over the chunks */
+    unsigned long long* sc = nullptr;      /* PRE_SC_WORDS (ig_host_pre.inc): the cursor, the assign pass's scalars, the emit's */
+    int* in[4] = {nullptr, nullptr, nullptr, nullptr}; /* a piece's c1, p1, c2, p2 */
+    long long piece_cap = 0;
+    RowBuf rows;                           /* the pixels: rows.rowptr [n_frags + 1], rows.out_col, rows.out_cnt [n_out] */
+    long long n_out = 0;
+    long long forms[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+};
+
 struct ig_ctx {
     int device;
     hipStream_t stream;
@@ -775,6 +800,7 @@ struct ig_ctx {
     EditBuf edit;
     CutJoinBuf cutjoin;
     PairsBuf pairs;
+    PreBuf pre;
     DebugRows debug_rows;
     DebugRows debug_zoom; /* the last ig_debug_zoom_coarsen's result (ig_debug_zoom_fetch) */
     int* batch_out; /* committed moves, pending slot, (unused), candidates, predicted deltas used, contigs */

@@ -16,6 +16,7 @@ static void free_segplace_buffers(ig_ctx* c); /* ig_host_segplace.inc */
 static void free_edit_buffers(ig_ctx* c);     /* ig_host_edit.inc */
 static void free_cutjoin_buffers(ig_ctx* c);  /* ig_host_cutjoin.inc */
 static void free_pairs_buffers(ig_ctx* c);    /* ig_host_pairs.inc */
+static void free_pre_buffers(ig_ctx* c);      /* ig_host_pre.inc */
 static void flush_pending_sums(ig_ctx* c); /* behind a decisively accepted nuisance step: see k_nuis_promote */
 
 /* ---- the launches of a run's NEXT step on a helper thread ------------------------------------------------------------------
@@ -417,6 +418,7 @@ extern "C" void ig_destroy(ig_ctx* c)
     free_edit_buffers(c);
     free_cutjoin_buffers(c);
     free_pairs_buffers(c);
+    free_pre_buffers(c);
     hipFree(c->st_block);
     hipFree(c->tab.dist);
     hipFree(c->tab_prev.dist);

@@ -18,8 +18,8 @@ SRC = os.path.join(HERE, "csrc", "ig_hip.hip")
 SRC_HOST = os.path.join(HERE, "csrc", "ig_draw.cpp")  # host-only part: the candidate draw
 DEPS = [SRC, SRC_HOST] + [os.path.join(HERE, "csrc", f) for f in ("ig_ops.cuh", "ig_common.cuh", "ig_model.cuh", "ig_kernels_setup.cuh",
                                                           "ig_kernels_score.cuh", "ig_kernels_screen.cuh", "ig_kernels_commit.cuh",
-                                                          "ig_kernels_nuis.cuh", "ig_kernels_wave.cuh", "ig_kernels_genome.cuh", "ig_kernels_rows.cuh", "ig_kernels_map.cuh", "ig_kernels_law.cuh", "ig_kernels_junc.cuh", "ig_kernels_lift.cuh", "ig_kernels_join.cuh", "ig_kernels_emap.cuh", "ig_kernels_place.cuh", "ig_kernels_orient.cuh", "ig_kernels_bal.cuh", "ig_kernels_gap.cuh", "ig_kernels_zoom.cuh", "ig_kernels_segplace.cuh", "ig_kernels_edit.cuh", "ig_kernels_cutjoin.cuh", "ig_kernels_pairs.cuh", "ig_host_core.inc", "ig_host_upload.inc", "ig_host_genome.inc", "ig_host_rows.inc",
-                                                          "ig_host_map.inc", "ig_host_law.inc", "ig_host_junc.inc", "ig_host_lift.inc", "ig_host_join.inc", "ig_host_emap.inc", "ig_host_place.inc", "ig_host_orient.inc", "ig_host_bal.inc", "ig_host_gap.inc", "ig_host_zoom.inc", "ig_host_segplace.inc", "ig_host_edit.inc", "ig_host_cutjoin.inc", "ig_host_pairs.inc",
+                                                          "ig_kernels_nuis.cuh", "ig_kernels_wave.cuh", "ig_kernels_genome.cuh", "ig_kernels_rows.cuh", "ig_kernels_map.cuh", "ig_kernels_law.cuh", "ig_kernels_junc.cuh", "ig_kernels_lift.cuh", "ig_kernels_join.cuh", "ig_kernels_emap.cuh", "ig_kernels_place.cuh", "ig_kernels_orient.cuh", "ig_kernels_bal.cuh", "ig_kernels_gap.cuh", "ig_kernels_zoom.cuh", "ig_kernels_segplace.cuh", "ig_kernels_edit.cuh", "ig_kernels_cutjoin.cuh", "ig_kernels_pairs.cuh", "ig_kernels_pre.cuh", "ig_host_core.inc", "ig_host_upload.inc", "ig_host_genome.inc", "ig_host_rows.inc",
+                                                          "ig_host_map.inc", "ig_host_law.inc", "ig_host_junc.inc", "ig_host_lift.inc", "ig_host_join.inc", "ig_host_emap.inc", "ig_host_place.inc", "ig_host_orient.inc", "ig_host_bal.inc", "ig_host_gap.inc", "ig_host_zoom.inc", "ig_host_segplace.inc", "ig_host_edit.inc", "ig_host_cutjoin.inc", "ig_host_pairs.inc", "ig_host_pre.inc",
                                                           "ig_host_batch.inc", "ig_host_nuis.inc", "ig_host_debug.inc")] + \
        [os.path.join(ROOT, "include", f) for f in ("ig_detmath.h", "ig_detmath_tables.h", "instagraal_hip.h")]
 
@@ -40,6 +40,7 @@ EDIT_PASSES = ("plan", "state", "tables", "delta", "zero", "whole")  # ig_debug_
 CUT_JOIN_PASSES = ("span", "scan", "zero", "count", "rowscan", "scatter", "sort_short", "sort_lds", "sort_long", "reduce", "terms", "join_zero")  # ig_debug_cut_join_time
 CUT_JOIN_LDS_PAIRS = 256  # CJ_LDS_PAIRS (csrc/ig_kernels_cutjoin.cuh): pairs up to which the join pass keeps its accumulators in LDS
 PAIRS_PASSES = ("lift",) + ASSEMBLY_CONTACTS_PASSES + ("law",)  # ig_debug_pairs_time
+PRE_DIGEST_PASSES = ("sites", "scan", "cuts", "fragments")  # ig_pre_digest
 CONTIG_ARRAYS = ("head_bin", "tail_bin", "n_sub", "length_bp")  # ig_join_scores_fetch: per linear contig
 MAX_CANDIDATES = 16
 
@@ -1053,6 +1054,88 @@ class Context:
         _ck(lib().ig_debug_pairs_time(self._h, _p(a[0]), _p(a[1]), _p(a[2]), _p(a[3]), None if st is None else _p(st), C.c_int64(a[0].size),
                                       C.c_int32(UNIT_KINDS.index(kind)), C.c_int64(int(binsize)), _p(e), C.c_int32(e.size), C.c_int32(int(n)), _p(ms), C.byref(ck)))
         return ms, int(ck.value)
+
+    # ---- the input folder from a FASTA and read pairs (the rule: pre.py)
+    def pre_begin(self, seq, rec_off, rec_len):
+        """opens the session over ``pre.concatenate``'s arrays: the records one behind the other, a zero byte behind each"""
+        s = np.ascontiguousarray(seq, np.uint8).ravel()
+        off = np.ascontiguousarray(rec_off, np.int64).ravel()
+        ln = self._i32(rec_len, "pre_begin: rec_len")
+        if off.size != ln.size:
+            raise HipError("pre_begin: one offset and one length per record")
+        _ck(lib().ig_pre_begin(self._h, _p(s), C.c_int64(s.size), _p(off), _p(ln), C.c_int32(ln.size)))
+        self._pre_records = int(ln.size)
+
+    def pre_digest(self, enzymes, piece=1 << 22, times=False):
+        """``enzymes``: [(site, cut)] -> the dict ``pre.digest`` returns without the names, plus ``gc_count`` (int64 [n_frags]) and
+        with ``times`` ``ms`` (float32 [4]: ``PRE_DIGEST_PASSES``)"""
+        from . import pre
+
+        enzymes = pre.expand_enzymes(enzymes)
+        R = getattr(self, "_pre_records", 0)
+        ln = np.array([len(s) for s, _ in enzymes], np.int32)
+        cut = np.array([c for _, c in enzymes], np.int32)
+        masks = np.ascontiguousarray(np.stack([pre.site_masks(s) for s, _ in enzymes]), np.uint8)
+        per, nf = np.zeros(R, np.int64), C.c_int64()
+        ms = np.zeros(len(PRE_DIGEST_PASSES), np.float32) if times else None
+        _ck(lib().ig_pre_digest(self._h, C.c_int32(ln.size), _p(ln), _p(cut), _p(masks), _p(per), C.byref(nf), _p(ms)))
+        n = int(nf.value)
+        cols = [np.zeros(n, np.int32) for _ in range(4)]
+        for a in range(0, n, int(piece)):
+            m = min(int(piece), n - a)
+            v = [x[a:a + m] for x in cols]
+            _ck(lib().ig_pre_fragments(self._h, C.c_int64(a), C.c_int64(m), _p(v[0]), _p(v[1]), _p(v[2]), _p(v[3])))
+        out = dict(rec_first=np.concatenate(([0], np.cumsum(per))).astype(np.int64), frag_rec=cols[0], start=cols[1].astype(np.int64), end=cols[2].astype(np.int64),
+                   gc_count=cols[3].astype(np.int64), n_frags=n, enzymes=enzymes)
+        out["rec_len"] = np.zeros(R, np.int64)
+        last = out["rec_first"][1:] - 1
+        out["rec_len"][:] = out["end"][last]
+        if times:
+            out["ms"] = ms
+        return out
+
+    def pre_add_pairs(self, c1, p1, c2, p2, times=False):
+        """one chunk: record (-1: unknown) and 1-based position of both ends -> the chunk's scalars (``pre.SCALARS[:5]``, ``pairs_stored``)"""
+        from .pre import SCALARS
+
+        a = [self._i32(x, "pre_add_pairs") for x in (c1, p1, c2, p2)]
+        if len({x.size for x in a}) != 1:
+            raise HipError("pre_add_pairs: the four arrays of the pairs have one length")
+        sc = np.zeros(8, np.int64)
+        ms = np.zeros(1, np.float32) if times else None
+        _ck(lib().ig_pre_add_pairs(self._h, _p(a[0]), _p(a[1]), _p(a[2]), _p(a[3]), C.c_int64(a[0].size), _p(sc), _p(ms)))
+        out = {k: int(sc[i]) for i, k in enumerate(SCALARS[:5])}
+        out["pairs_stored"] = int(sc[5])
+        if times:
+            out["ms"] = float(ms[0])
+        return out
+
+    def pre_pixels(self, piece=1 << 22, times=False):
+        """the pixels of the stored pairs -> the dict ``pre.pixels_host`` returns, plus ``n_frags`` and ``pairs_stored``"""
+        from .pre import SCALARS
+
+        npx, sc = C.c_int64(), np.zeros(8, np.int64)
+        ms = np.zeros(len(ASSEMBLY_CONTACTS_PASSES), np.float32) if times else None
+        _ck(lib().ig_pre_pixels_build(self._h, C.byref(npx), _p(sc), _p(ms)))
+        U, n = int(sc[6]), int(npx.value)
+        rowptr, col, count = np.zeros(U + 1, np.int64), np.zeros(n, np.int32), np.zeros(n, np.int64)
+        _ck(lib().ig_pre_pixels_rows(self._h, _p(rowptr), C.c_int64(rowptr.size)))
+        for a in range(0, n, int(piece)):
+            m = min(int(piece), n - a)
+            vc, vn = col[a:a + m], count[a:a + m]
+            _ck(lib().ig_pre_pixels_fetch(self._h, C.c_int64(a), C.c_int64(m), _p(vc), _p(vn)))
+        out = dict(rowptr=rowptr, col=col.astype(np.int64), count=count)
+        out.update({k: int(sc[i]) for i, k in enumerate(SCALARS)})
+        out.update(n_frags=U, pairs_stored=int(sc[7]))
+        if times:
+            out["ms"] = ms
+        return out
+
+    def pre_clear(self):
+        _ck(lib().ig_pre_clear(self._h))
+
+    def pre_end(self):
+        _ck(lib().ig_pre_end(self._h))
 
     def balance_build_units(self, unit, n_units, ignore_diags=2):
         """``balance_build("bin")`` with the caller's unit of every position -> the dict ``balance_build`` returns (level: "units")"""
