@@ -853,6 +853,33 @@ int ig_pre_pixels_fetch(ig_ctx* ctx, int64_t first, int64_t n, int32_t* col, int
 /* empties the store and its scalars and drops the pixels; the sequence, the digest and the buffers stay */
 int ig_pre_clear(ig_ctx* ctx);
 int ig_pre_end(ig_ctx* ctx);
+
+/* ---- the polished FASTA of the polish step: the composition of the input records and the output file stitched from their bases (the
+ * rule, stated once: instagraal_amd/scaffold_polish.py).  A SESSION lives between ig_seq_begin and ig_seq_end (ig_destroy
+ * frees a live one) on a created handle; it needs no contacts and no state and changes nothing a move reads; no nuisance step or chain
+ * may be in flight.  ig_seq_begin takes the layout of ig_pre_begin and refuses what it refuses. */
+int ig_seq_begin(ig_ctx* ctx, const uint8_t* seq, int64_t n_bytes, const int64_t* rec_off, const int32_t* rec_len, int32_t n_records);
+/* counts[n_records][8]: per record the letters A, C, G, T, N of either case, the other letters, the lower-case letters, all bases.
+ * ms (may be NULL): the kernel's time. */
+int ig_seq_composition(ig_ctx* ctx, int64_t* counts, float* ms);
+/* The plan of the output file.  Output record j: the header literal[hdr_lit[j] .. + hdr_len[j]), then a body of body_len[j] bases, a
+ * newline behind every `width` of them and behind the last line; rec_off[n_out + 1]: the file offset of every header, the file's size
+ * last; its pieces are piece_first[j] .. piece_first[j + 1] - 1.  Piece p: `length[p]` (1 .. 2^31 - 1) bases from `start[p]` of the
+ * input record src[p] (-1: of the literal buffer), as they are (ori[p] == 1) or as their reverse complement (-1; never a literal
+ * piece), at the base body[p] of its body.  Refused, naming the record or the piece: a piece outside its source, pieces that do not
+ * tile their body in ascending order without gap or overlap, offsets that are not those of the headers, bodies and lines.  An
+ * earlier plan of the session and its counts are gone. */
+int ig_seq_plan(ig_ctx* ctx, int32_t n_out, int32_t width, const int64_t* rec_off, const int32_t* hdr_len, const int64_t* hdr_lit, const int64_t* body_len,
+                const int64_t* piece_first, int64_t n_pieces, const int32_t* src, const int64_t* start, const int64_t* length, const int32_t* ori,
+                const int64_t* body, const uint8_t* literal, int64_t n_literal);
+/* The bytes first_byte .. first_byte + n_bytes - 1 of the file into out.  first_byte is a multiple of 16; so is n_bytes unless the
+ * window ends with the file.  A window that begins where the windows counted so far end (the first: at 0) adds the classes of its
+ * body bases to the counts of ig_seq_out_composition; any other is stitched only.  ms (may be NULL): the kernel's time. */
+int ig_seq_window(ig_ctx* ctx, int64_t first_byte, int64_t n_bytes, uint8_t* out, float* ms);
+/* counts[n_out][8] of the stitched bodies, junctions included (n_counts: the caller's capacity in words): refused until the windows
+ * fetched in file order have reached the file's end */
+int ig_seq_out_composition(ig_ctx* ctx, int64_t* counts, int64_t n_counts);
+int ig_seq_end(ig_ctx* ctx);
 #ifdef __cplusplus
 }
 #endif

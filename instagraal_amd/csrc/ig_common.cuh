@@ -683,6 +683,30 @@ struct PreBuf {
     long long forms[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 };
 
+/* the polished FASTA of the polish step (ig_kernels_seq.cuh): one session between ig_seq_begin and ig_seq_end, freed by
+ * free_seq_buffers (ig_host_seq.inc): the sequence bytes, the input's counts, the plan of the output file, one window of it */
+struct SeqPiece;
+struct SeqBuf {
+    bool live = false, planned = false;
+    int R = 0;
+    long long n_bytes = 0, n_runs = 0;
+    unsigned char* base = nullptr;          /* [16 + 16 (n_runs + 1)] 16 zero bytes, the records and their separators, zero behind them */
+    long long* off = nullptr;               /* [R] */
+    unsigned long long* counts = nullptr;   /* [R][SEQ_NC] */
+    std::vector<long long> h_off;           /* [R] the records' offsets and lengths on the host: what ig_seq_plan checks the pieces against */
+    std::vector<int> h_len;
+    int n_out = 0, width = 0;
+    long long n_pieces = 0, file_bytes = 0;
+    long long counted = 0;                  /* the file bytes whose bases out_counts holds: the windows stitched in file order end here */
+    long long *rec_off = nullptr, *hdr_lit = nullptr, *piece_first = nullptr, *p_body = nullptr;
+    int* hdr_len = nullptr;
+    SeqPiece* piece = nullptr;
+    unsigned char* lit = nullptr;
+    unsigned long long* out_counts = nullptr; /* [n_out][SEQ_NC] */
+    unsigned char* win = nullptr;           /* [win_cap] the window being stitched (grow-only) */
+    long long win_cap = 0;
+};
+
 struct ig_ctx {
     int device;
     hipStream_t stream;
@@ -801,6 +825,7 @@ struct ig_ctx {
     CutJoinBuf cutjoin;
     PairsBuf pairs;
     PreBuf pre;
+    SeqBuf seq;
     DebugRows debug_rows;
     DebugRows debug_zoom; /* the last ig_debug_zoom_coarsen's result (ig_debug_zoom_fetch) */
     int* batch_out; /* committed moves, pending slot, (unused), candidates, predicted deltas used, contigs */

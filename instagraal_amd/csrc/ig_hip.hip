@@ -6,7 +6,7 @@
  *
  * One translation unit; the device code lives in the ig_kernels_*.cuh parts included below, the host side (handles, uploads, the
  * launch sequences, the extern "C" entry points) in the ig_host_*.inc parts: core, upload; genome and rows, the layers the reports
- * on the current genome share; map, law, junc, lift, join, emap, place, orient, bal, gap, one per report; edit, the segment edits; cutjoin, the cut and join scores; pairs, the read pairs lifted onto the genome; pre, the input folder from a FASTA and read pairs; batch, nuis, debug.
+ * on the current genome share; map, law, junc, lift, join, emap, place, orient, bal, gap, one per report; edit, the segment edits; cutjoin, the cut and join scores; pairs, the read pairs lifted onto the genome; pre, the input folder from a FASTA and read pairs; seq, the polished FASTA of the polish step; batch, nuis, debug.
  *
  * A batch of W moves (CL:1401-1465 each) is one launch sequence on one stream, no host round trip inside:
  *   k_gather        O(N)            local fragment lists of the touched contigs, uniq-mutation lists, flags
@@ -38,7 +38,8 @@
  * 4.13 (4.19); the gap support of the joins: k_gap_junctions, k_gap_paint, k_gap_observed, k_gap_model (4.20); the segment edits: k_edit_plan, k_edit_state, k_edit_delta,
  * k_edit_zero_delta, k_edit_commit (4.23); the cut and join scores: k_cut_span, k_cut_zero, k_cj_vk, k_cj_pairs_emit, k_cj_join,
  * k_cj_contig_zero, k_cj_join_zero (4.24); the read pairs lifted onto the genome: k_pairs_lift, k_pairs_emit, k_pairs_law (4.25); the input
- * folder from a FASTA and read pairs: k_pre_sites, k_pre_marks, k_pre_popc, k_pre_cuts, k_pre_frags, k_pre_assign, k_pre_emit (4.26).
+ * folder from a FASTA and read pairs: k_pre_sites, k_pre_marks, k_pre_popc, k_pre_cuts, k_pre_frags, k_pre_assign, k_pre_emit (4.26); the polished FASTA
+ * of the polish step: k_seq_composition, k_seq_stitch (4.27).
  *
  * Environment knobs (tests, fault injection and tuning only; the table in INTEGRATION.md section 4 is the reference): IG_BATCH_W, IG_WINDOW
  * (widths), IG_POOL_ENTRIES, IG_WIDE_LISTS, IG_NO_HOST_FLAG, IG_POISON_ALLOC / IG_POISON_ONLY (force the rare paths), IG_SCREEN,
@@ -77,8 +78,9 @@
 #include "ig_kernels_cutjoin.cuh"
 #include "ig_kernels_pairs.cuh"
 #include "ig_kernels_pre.cuh"
+#include "ig_kernels_seq.cuh"
 
-/* ================================================================== host side (one translation unit, twenty-three parts) */
+/* ================================================================== host side (one translation unit, twenty-four parts) */
 #include "ig_host_core.inc"
 #include "ig_host_upload.inc"
 #include "ig_host_genome.inc"
@@ -99,6 +101,7 @@
 #include "ig_host_cutjoin.inc"
 #include "ig_host_pairs.inc"
 #include "ig_host_pre.inc"
+#include "ig_host_seq.inc"
 #include "ig_host_batch.inc"
 #include "ig_host_nuis.inc"
 #include "ig_host_debug.inc"

@@ -76,16 +76,24 @@ static inline bool pre_host_valid(unsigned char b)
     return (b & 0xc0u) == 0x40u && i < 26u && ((PRE_LETTERS >> i) & 1u);
 }
 
-/* seq: n_bytes bytes, the records one behind the other with a zero byte behind each: rec_off[0] == 0, rec_off[r + 1] == rec_off[r] +
- * rec_len[r] + 1, n_bytes == rec_off[R - 1] + rec_len[R - 1] + 1.  The bytes go to the device in pieces. */
-extern "C" int ig_pre_begin(ig_ctx* c, const uint8_t* seq, int64_t n_bytes, const int64_t* rec_off, const int32_t* rec_len, int32_t n_records)
+/* whether each of the eight bytes of w is A, C, G, T or N in either case: per letter, the bytes equal to it get their top bit set
+ * (a byte x is zero where ((x & 0x7f) + 0x7f) | x has its top bit clear: no carry leaves a byte) */
+static inline bool pre_host_plain8(uint64_t w)
 {
-    IG_JOIN(c);
-    HIPCK(hipSetDevice(c->device));
-    const char* who = "ig_pre_begin";
-    PreBuf& p = c->pre;
-    if (p.live) return fail("%s: a session is open (ig_pre_end first)", who);
-    if (c->nuis_in_flight || c->chain_busy) return fail("%s: a nuisance step or a chain is in flight", who);
+    const uint64_t ones = 0x0101010101010101ull, low7 = 0x7f7f7f7f7f7f7f7full, top = 0x8080808080808080ull;
+    const uint64_t up = w & ~(0x20ull * ones);
+    uint64_t hit = 0;
+    for (const unsigned char letter : {'A', 'C', 'G', 'T', 'N'}) {
+        const uint64_t x = up ^ (letter * ones);
+        hit |= ~(((x & low7) + low7) | x) & top;
+    }
+    return hit == top;
+}
+
+/* the layout ig_pre_begin and ig_seq_begin take, checked before anything is allocated: the records one behind the other with a zero
+ * byte behind each, every base a letter of the alphabet */
+static int records_layout_check(const char* who, const uint8_t* seq, int64_t n_bytes, const int64_t* rec_off, const int32_t* rec_len, int32_t n_records)
+{
     if (n_records < 1 || n_bytes < 2) return fail("%s: bad sizes (%d records, %lld bytes)", who, n_records, (long long)n_bytes);
     if (!seq || !rec_off || !rec_len) return fail("%s: NULL argument", who);
     const int R = n_records;
@@ -99,9 +107,37 @@ extern "C" int ig_pre_begin(ig_ctx* c, const uint8_t* seq, int64_t n_bytes, cons
         if (seq[at - 1] != 0) return fail("%s: the byte behind record %d is %d, not the separator 0", who, r, (int)seq[at - 1]);
     }
     if (at != n_bytes) return fail("%s: the records and their separators are %lld bytes, not %lld", who, at, (long long)n_bytes);
-    for (int r = 0; r < R; r++) /* the rule's refusal of a character outside the alphabet, before anything is allocated */
-        for (long long k = rec_off[r], e = rec_off[r] + rec_len[r]; k < e; k++)
+    for (int r = 0; r < R; r++) { /* the rule's refusal of a character outside the alphabet, before anything is allocated */
+        long long k = rec_off[r];
+        const long long e = rec_off[r] + rec_len[r];
+        while (k < e) {
+            if (e - k >= 8) { /* eight bytes at a time where all of them are A, C, G, T or N of either case: nearly every word of a genome */
+                uint64_t w;
+                memcpy(&w, seq + k, 8);
+                if (pre_host_plain8(w)) {
+                    k += 8;
+                    continue;
+                }
+            }
             if (!pre_host_valid(seq[k])) return fail("%s: record %d, position %lld: the character 0x%02x is not one of ABCDGHKMNRSTVWY", who, r, k - rec_off[r] + 1, (unsigned)seq[k]);
+            k++;
+        }
+    }
+    return 0;
+}
+
+/* seq: n_bytes bytes, the records one behind the other with a zero byte behind each: rec_off[0] == 0, rec_off[r + 1] == rec_off[r] +
+ * rec_len[r] + 1, n_bytes == rec_off[R - 1] + rec_len[R - 1] + 1.  The bytes go to the device in pieces. */
+extern "C" int ig_pre_begin(ig_ctx* c, const uint8_t* seq, int64_t n_bytes, const int64_t* rec_off, const int32_t* rec_len, int32_t n_records)
+{
+    IG_JOIN(c);
+    HIPCK(hipSetDevice(c->device));
+    const char* who = "ig_pre_begin";
+    PreBuf& p = c->pre;
+    if (p.live) return fail("%s: a session is open (ig_pre_end first)", who);
+    if (c->nuis_in_flight || c->chain_busy) return fail("%s: a nuisance step or a chain is in flight", who);
+    if (records_layout_check(who, seq, n_bytes, rec_off, rec_len, n_records)) return -1;
+    const int R = n_records;
     const long long n_runs = (n_bytes + PRE_RUN - 1) / PRE_RUN, W = (n_runs + 3) / 4 + 1;
     if (W > 0x7fffffffll) return fail("%s: %lld bytes make %lld bitmap words, more than 2^31 - 1", who, (long long)n_bytes, W);
     const unsigned long long padded = (unsigned long long)(n_runs + 1) * PRE_RUN;

@@ -18,8 +18,8 @@ SRC = os.path.join(HERE, "csrc", "ig_hip.hip")
 SRC_HOST = os.path.join(HERE, "csrc", "ig_draw.cpp")  # host-only part: the candidate draw
 DEPS = [SRC, SRC_HOST] + [os.path.join(HERE, "csrc", f) for f in ("ig_ops.cuh", "ig_common.cuh", "ig_model.cuh", "ig_kernels_setup.cuh",
                                                           "ig_kernels_score.cuh", "ig_kernels_screen.cuh", "ig_kernels_commit.cuh",
-                                                          "ig_kernels_nuis.cuh", "ig_kernels_wave.cuh", "ig_kernels_genome.cuh", "ig_kernels_rows.cuh", "ig_kernels_map.cuh", "ig_kernels_law.cuh", "ig_kernels_junc.cuh", "ig_kernels_lift.cuh", "ig_kernels_join.cuh", "ig_kernels_emap.cuh", "ig_kernels_place.cuh", "ig_kernels_orient.cuh", "ig_kernels_bal.cuh", "ig_kernels_gap.cuh", "ig_kernels_zoom.cuh", "ig_kernels_segplace.cuh", "ig_kernels_edit.cuh", "ig_kernels_cutjoin.cuh", "ig_kernels_pairs.cuh", "ig_kernels_pre.cuh", "ig_host_core.inc", "ig_host_upload.inc", "ig_host_genome.inc", "ig_host_rows.inc",
-                                                          "ig_host_map.inc", "ig_host_law.inc", "ig_host_junc.inc", "ig_host_lift.inc", "ig_host_join.inc", "ig_host_emap.inc", "ig_host_place.inc", "ig_host_orient.inc", "ig_host_bal.inc", "ig_host_gap.inc", "ig_host_zoom.inc", "ig_host_segplace.inc", "ig_host_edit.inc", "ig_host_cutjoin.inc", "ig_host_pairs.inc", "ig_host_pre.inc",
+                                                          "ig_kernels_nuis.cuh", "ig_kernels_wave.cuh", "ig_kernels_genome.cuh", "ig_kernels_rows.cuh", "ig_kernels_map.cuh", "ig_kernels_law.cuh", "ig_kernels_junc.cuh", "ig_kernels_lift.cuh", "ig_kernels_join.cuh", "ig_kernels_emap.cuh", "ig_kernels_place.cuh", "ig_kernels_orient.cuh", "ig_kernels_bal.cuh", "ig_kernels_gap.cuh", "ig_kernels_zoom.cuh", "ig_kernels_segplace.cuh", "ig_kernels_edit.cuh", "ig_kernels_cutjoin.cuh", "ig_kernels_pairs.cuh", "ig_kernels_pre.cuh", "ig_kernels_seq.cuh", "ig_host_core.inc", "ig_host_upload.inc", "ig_host_genome.inc", "ig_host_rows.inc",
+                                                          "ig_host_map.inc", "ig_host_law.inc", "ig_host_junc.inc", "ig_host_lift.inc", "ig_host_join.inc", "ig_host_emap.inc", "ig_host_place.inc", "ig_host_orient.inc", "ig_host_bal.inc", "ig_host_gap.inc", "ig_host_zoom.inc", "ig_host_segplace.inc", "ig_host_edit.inc", "ig_host_cutjoin.inc", "ig_host_pairs.inc", "ig_host_pre.inc", "ig_host_seq.inc",
                                                           "ig_host_batch.inc", "ig_host_nuis.inc", "ig_host_debug.inc")] + \
        [os.path.join(ROOT, "include", f) for f in ("ig_detmath.h", "ig_detmath_tables.h", "instagraal_hip.h")]
 
@@ -41,6 +41,7 @@ CUT_JOIN_PASSES = ("span", "scan", "zero", "count", "rowscan", "scatter", "sort_
 CUT_JOIN_LDS_PAIRS = 256  # CJ_LDS_PAIRS (csrc/ig_kernels_cutjoin.cuh): pairs up to which the join pass keeps its accumulators in LDS
 PAIRS_PASSES = ("lift",) + ASSEMBLY_CONTACTS_PASSES + ("law",)  # ig_debug_pairs_time
 PRE_DIGEST_PASSES = ("sites", "scan", "cuts", "fragments")  # ig_pre_digest
+SEQ_CLASSES = 8  # SEQ_NC (csrc/ig_kernels_seq.cuh): scaffold_polish.CLASSES
 CONTIG_ARRAYS = ("head_bin", "tail_bin", "n_sub", "length_bp")  # ig_join_scores_fetch: per linear contig
 MAX_CANDIDATES = 16
 
@@ -1136,6 +1137,58 @@ class Context:
 
     def pre_end(self):
         _ck(lib().ig_pre_end(self._h))
+
+    # ---- the polished FASTA of the polish step (the rule: scaffold_polish.py)
+    def seq_begin(self, seq, rec_off, rec_len):
+        """opens the session over ``pre.concatenate``'s arrays, like ``pre_begin``"""
+        s = np.ascontiguousarray(seq, np.uint8).ravel()
+        off = np.ascontiguousarray(rec_off, np.int64).ravel()
+        ln = self._i32(rec_len, "seq_begin: rec_len")
+        if off.size != ln.size:
+            raise HipError("seq_begin: one offset and one length per record")
+        _ck(lib().ig_seq_begin(self._h, _p(s), C.c_int64(s.size), _p(off), _p(ln), C.c_int32(ln.size)))
+        self._seq_records = int(ln.size)
+
+    def seq_composition(self, times=None):
+        """-> int64 [R, 8] (``scaffold_polish.CLASSES``); ``times``: a dict whose ``composition`` list gets the kernel's ms"""
+        counts = np.zeros((getattr(self, "_seq_records", 0), SEQ_CLASSES), np.int64)
+        ms = np.zeros(1, np.float32) if times is not None else None
+        _ck(lib().ig_seq_composition(self._h, _p(counts), _p(ms)))
+        if times is not None:
+            times.setdefault("composition", []).append(float(ms[0]))
+        return counts
+
+    def seq_plan(self, plan):
+        """uploads the tables of ``scaffold_polish.stitch_plan``"""
+        a = {k: np.ascontiguousarray(plan[k], np.int64).ravel() for k in ("rec_off", "hdr_lit", "body_len", "piece_first", "start", "length", "body")}
+        b = {k: np.ascontiguousarray(plan[k], np.int32).ravel() for k in ("hdr_len", "src", "ori")}
+        lit = np.ascontiguousarray(plan["literal"], np.uint8).ravel()
+        n_out = b["hdr_len"].size
+        if a["rec_off"].size != n_out + 1 or a["piece_first"].size != n_out + 1 or a["hdr_lit"].size != n_out or a["body_len"].size != n_out:
+            raise HipError("seq_plan: the tables of the output records have %d and %d + 1 entries" % (n_out, n_out))
+        if len({b["src"].size, b["ori"].size, a["start"].size, a["length"].size, a["body"].size}) != 1:
+            raise HipError("seq_plan: the five arrays of the pieces have one length")
+        _ck(lib().ig_seq_plan(self._h, C.c_int32(n_out), C.c_int32(int(plan["width"])), _p(a["rec_off"]), _p(b["hdr_len"]), _p(a["hdr_lit"]), _p(a["body_len"]),
+                              _p(a["piece_first"]), C.c_int64(b["src"].size), _p(b["src"]), _p(a["start"]), _p(a["length"]), _p(b["ori"]), _p(a["body"]), _p(lit),
+                              C.c_int64(lit.size)))
+
+    def seq_window(self, first_byte, out, times=None):
+        """fills ``out`` (a contiguous uint8 array) with the file's bytes from ``first_byte`` on; ``times``: ``stitch`` gets the kernel's ms"""
+        if not (isinstance(out, np.ndarray) and out.dtype == np.uint8 and out.flags.c_contiguous and out.flags.writeable):
+            raise HipError("seq_window: the window is a contiguous writeable uint8 array")
+        ms = np.zeros(1, np.float32) if times is not None else None
+        _ck(lib().ig_seq_window(self._h, C.c_int64(int(first_byte)), C.c_int64(out.size), _p(out), _p(ms)))
+        if times is not None:
+            times.setdefault("stitch", []).append(float(ms[0]))
+
+    def seq_out_composition(self, n_out):
+        """-> int64 [n_out, 8] of the stitched bodies, once every window has been fetched in file order"""
+        counts = np.zeros((int(n_out), SEQ_CLASSES), np.int64)
+        _ck(lib().ig_seq_out_composition(self._h, _p(counts), C.c_int64(counts.size)))
+        return counts
+
+    def seq_end(self):
+        _ck(lib().ig_seq_end(self._h))
 
     def balance_build_units(self, unit, n_units, ignore_diags=2):
         """``balance_build("bin")`` with the caller's unit of every position -> the dict ``balance_build`` returns (level: "units")"""

@@ -424,3 +424,30 @@ def run_from_pairs(fasta, pairs, enzymes, output_folder, **run_kw):
     folder = os.path.join(str(output_folder), "pre")
     pre.run_pre(fasta, pairs, enzymes, folder)
     return run_instagraal(folder, str(fasta), output_folder=str(output_folder), **run_kw)
+
+
+def run_and_polish(hic_folder, reference_fa, output_folder=None, post_polish=False, stats=False, junction="", lost="reference", **run_kw):
+    """``run_instagraal`` with the reference's polish step and its statistics behind it; both switches default to off, and
+    with both off this IS ``run_instagraal``: the same files, the same output.  ``post_polish`` runs ``scaffold_polish.polish_assembly`` in
+    its polishing mode on the run's final ``info_frags.txt`` and ``reference_fa`` into ``<run folder>/polished/`` (``junction``, ``lost``:
+    its arguments; the FASTA is stitched on the run's device).  ``stats`` writes ``assembly_stats_comparison.txt`` into the run folder and
+    prints it: the comparison table of the input, ``genome.fasta`` and, with ``post_polish``, the polished genome.  Returns what
+    ``run_instagraal`` returns; the polish's result is its ``polish_result``."""
+    p2 = run_instagraal(hic_folder, reference_fa, output_folder=output_folder, **run_kw)
+    if run_kw.get("pyramid_only") or not (post_polish or stats):
+        return p2
+    from . import assembly_stats, scaffold_polish
+
+    sim = p2.simulation
+    folder = sim.output_folder
+    results = {"input": assembly_stats.compute_assembly_stats(str(reference_fa)), "genome.fasta": assembly_stats.compute_assembly_stats(sim.new_fasta)}
+    if post_polish:
+        p2.polish_result = scaffold_polish.polish_assembly(sim.info_frags, str(reference_fa), os.path.join(folder, "polished"), mode="polishing", junction=junction, lost=lost,
+                                                           device=True, device_id=run_kw.get("device", 0))
+        results["polished"] = p2.polish_result["stats"]["polished"]
+    if stats:
+        text = assembly_stats.format_comparison_table(results)
+        with open(os.path.join(folder, "assembly_stats_comparison.txt"), "w") as h:
+            h.write(text)
+        print(text)
+    return p2
