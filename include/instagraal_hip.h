@@ -880,6 +880,35 @@ int ig_seq_window(ig_ctx* ctx, int64_t first_byte, int64_t n_bytes, uint8_t* out
  * fetched in file order have reached the file's end */
 int ig_seq_out_composition(ig_ctx* ctx, int64_t* counts, int64_t n_counts);
 int ig_seq_end(ig_ctx* ctx);
+
+/* ---- the contact levels of the pyramid: the level of a contact list (the upper-triangular sum over (min, max), rows and columns
+ * ascending, 64-bit sums), the partners of every fragment, and the next level from the current one through a table (the rule, stated
+ * once: instagraal_amd/pyramid_levels.py).  A SESSION lives between ig_pyr_begin and ig_pyr_end (ig_destroy frees a
+ * live one) on a created handle; it needs no contacts and no state and changes nothing a move reads; no nuisance step or chain may be
+ * in flight.  All ids are 0-based.  A sum of 2^31 or more anywhere in a level is refused, naming the pixel; the current level stays.
+ *
+ * ig_pyr_begin: the level-0 list of n entries over n_frags fragments in file order; it goes to the device in pieces.  Refused, naming
+ * the entry: an id outside 0 .. n_frags - 1, a negative count, a count of 2^31 or more.  *is_canonical: every a <= b and the pairs (a,
+ * b) strictly ascending: the list is its own level. */
+int ig_pyr_begin(ig_ctx* ctx, int32_t n_frags, const int32_t* a, const int32_t* b, const int64_t* count, int64_t n, int32_t* is_canonical);
+/* the level of the uploaded list becomes the current level.  ms (may be NULL): the seven passes of the row builder. */
+int ig_pyr_matrix(ig_ctx* ctx, int64_t* n_pixels, float* ms);
+/* deg[n_frags] of the current level: deg[i] is the number of j with (M + M^T)[i, j] != 0: a stored zero is no partner, a diagonal
+ * entry counts once */
+int ig_pyr_degrees(ig_ctx* ctx, int32_t* deg);
+/* The next level from the current one, which stays on the device: lut[n_old] (n_old: the fragments of the current level) is the new
+ * id of every fragment or -1 (destroyed), ascending wherever it is not -1 and below n_new; an entry with a destroyed end is dropped.
+ * skip_first (0 or 1): the first entry of the current level -- of the uploaded list, where no level has been made of it: in file order
+ * -- is lost (quirk Q-P1 of the binning).  scalars: {entries_in, skipped, dropped_by_lut, entries_kept, pixels, largest_sum, 0, 0}.
+ * ms (may be NULL): the seven passes of the row builder. */
+int ig_pyr_remap(ig_ctx* ctx, const int32_t* lut, int32_t n_old, int32_t n_new, int32_t skip_first, int64_t* n_pixels, int64_t scalars[8], float* ms);
+/* rowptr[n_frags + 1] of the current level (n_rowptr: the caller's capacity) */
+int ig_pyr_rows(ig_ctx* ctx, int64_t* rowptr, int64_t n_rowptr);
+/* the entries first .. first + n - 1 of the current level as the three int32 rows of the level's matrix: row, column, count */
+int ig_pyr_fetch(ig_ctx* ctx, int64_t first, int64_t n, int32_t* row, int32_t* col, int32_t* count);
+int ig_pyr_end(ig_ctx* ctx);
+/* entries per upload piece of ig_pyr_begin (0: the default): for tests of the upload in pieces */
+int ig_debug_pyr_piece(ig_ctx* ctx, int64_t entries);
 #ifdef __cplusplus
 }
 #endif

@@ -707,6 +707,29 @@ struct SeqBuf {
     long long win_cap = 0;
 };
 
+/* the contact levels of the pyramid (ig_kernels_pyr.cuh): one session between ig_pyr_begin and ig_pyr_end, freed by free_pyr_buffers
+ * (ig_host_pyr.inc): the uploaded list until a level has been made of it, then the current level in one of two RowBufs that swap
+ * roles with every remap, the table of a remap (grow-only) */
+struct PyrBuf {
+    bool live = false, have_level = false;  /* have_level: the current level is rows[cur]; else it is the uploaded list */
+    int canonical = 0;                      /* the uploaded list was its own level */
+    int n_frags = 0;                        /* fragments of the current level */
+    long long n0 = 0;                       /* entries of the uploaded list */
+    int *a = nullptr, *b = nullptr, *cnt = nullptr; /* [n0] the uploaded list in file order */
+    int* lut = nullptr;                     /* [lut_cap] the table of a remap */
+    long long lut_cap = 0;
+    unsigned* deg = nullptr;                /* [deg_cap] the degrees (grow-only) */
+    long long deg_cap = 0;
+    int* out[3] = {nullptr, nullptr, nullptr}; /* [out_cap] a fetched stretch: rows, columns, counts (grow-only) */
+    long long out_cap = 0;
+    unsigned long long* sc = nullptr;       /* PYR_SC_WORDS (ig_host_pyr.inc) */
+    RowBuf rows[2];                         /* rows[cur]: rowptr [n_frags + 1], out_col, out_cnt [n_out] */
+    int cur = 0;
+    long long n_out = 0;
+    long long piece = 0;                    /* ig_debug_pyr_piece: entries per upload piece (0: the default) */
+    long long forms[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+};
+
 struct ig_ctx {
     int device;
     hipStream_t stream;
@@ -826,6 +849,7 @@ struct ig_ctx {
     PairsBuf pairs;
     PreBuf pre;
     SeqBuf seq;
+    PyrBuf pyr;
     DebugRows debug_rows;
     DebugRows debug_zoom; /* the last ig_debug_zoom_coarsen's result (ig_debug_zoom_fetch) */
     int* batch_out; /* committed moves, pending slot, (unused), candidates, predicted deltas used, contigs */

@@ -79,8 +79,9 @@
 #include "ig_kernels_pairs.cuh"
 #include "ig_kernels_pre.cuh"
 #include "ig_kernels_seq.cuh"
+#include "ig_kernels_pyr.cuh"
 
-/* ================================================================== host side (one translation unit, twenty-four parts) */
+/* ================================================================== host side (one translation unit, twenty-five parts) */
 #include "ig_host_core.inc"
 #include "ig_host_upload.inc"
 #include "ig_host_genome.inc"
@@ -102,6 +103,7 @@
 #include "ig_host_pairs.inc"
 #include "ig_host_pre.inc"
 #include "ig_host_seq.inc"
+#include "ig_host_pyr.inc"
 #include "ig_host_batch.inc"
 #include "ig_host_nuis.inc"
 #include "ig_host_debug.inc"

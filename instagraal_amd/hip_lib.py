@@ -18,8 +18,8 @@ SRC = os.path.join(HERE, "csrc", "ig_hip.hip")
 SRC_HOST = os.path.join(HERE, "csrc", "ig_draw.cpp")  # host-only part: the candidate draw
 DEPS = [SRC, SRC_HOST] + [os.path.join(HERE, "csrc", f) for f in ("ig_ops.cuh", "ig_common.cuh", "ig_model.cuh", "ig_kernels_setup.cuh",
                                                           "ig_kernels_score.cuh", "ig_kernels_screen.cuh", "ig_kernels_commit.cuh",
-                                                          "ig_kernels_nuis.cuh", "ig_kernels_wave.cuh", "ig_kernels_genome.cuh", "ig_kernels_rows.cuh", "ig_kernels_map.cuh", "ig_kernels_law.cuh", "ig_kernels_junc.cuh", "ig_kernels_lift.cuh", "ig_kernels_join.cuh", "ig_kernels_emap.cuh", "ig_kernels_place.cuh", "ig_kernels_orient.cuh", "ig_kernels_bal.cuh", "ig_kernels_gap.cuh", "ig_kernels_zoom.cuh", "ig_kernels_segplace.cuh", "ig_kernels_edit.cuh", "ig_kernels_cutjoin.cuh", "ig_kernels_pairs.cuh", "ig_kernels_pre.cuh", "ig_kernels_seq.cuh", "ig_host_core.inc", "ig_host_upload.inc", "ig_host_genome.inc", "ig_host_rows.inc",
-                                                          "ig_host_map.inc", "ig_host_law.inc", "ig_host_junc.inc", "ig_host_lift.inc", "ig_host_join.inc", "ig_host_emap.inc", "ig_host_place.inc", "ig_host_orient.inc", "ig_host_bal.inc", "ig_host_gap.inc", "ig_host_zoom.inc", "ig_host_segplace.inc", "ig_host_edit.inc", "ig_host_cutjoin.inc", "ig_host_pairs.inc", "ig_host_pre.inc", "ig_host_seq.inc",
+                                                          "ig_kernels_nuis.cuh", "ig_kernels_wave.cuh", "ig_kernels_genome.cuh", "ig_kernels_rows.cuh", "ig_kernels_map.cuh", "ig_kernels_law.cuh", "ig_kernels_junc.cuh", "ig_kernels_lift.cuh", "ig_kernels_join.cuh", "ig_kernels_emap.cuh", "ig_kernels_place.cuh", "ig_kernels_orient.cuh", "ig_kernels_bal.cuh", "ig_kernels_gap.cuh", "ig_kernels_zoom.cuh", "ig_kernels_segplace.cuh", "ig_kernels_edit.cuh", "ig_kernels_cutjoin.cuh", "ig_kernels_pairs.cuh", "ig_kernels_pre.cuh", "ig_kernels_seq.cuh", "ig_kernels_pyr.cuh", "ig_host_core.inc", "ig_host_upload.inc", "ig_host_genome.inc", "ig_host_rows.inc",
+                                                          "ig_host_map.inc", "ig_host_law.inc", "ig_host_junc.inc", "ig_host_lift.inc", "ig_host_join.inc", "ig_host_emap.inc", "ig_host_place.inc", "ig_host_orient.inc", "ig_host_bal.inc", "ig_host_gap.inc", "ig_host_zoom.inc", "ig_host_segplace.inc", "ig_host_edit.inc", "ig_host_cutjoin.inc", "ig_host_pairs.inc", "ig_host_pre.inc", "ig_host_seq.inc", "ig_host_pyr.inc",
                                                           "ig_host_batch.inc", "ig_host_nuis.inc", "ig_host_debug.inc")] + \
        [os.path.join(ROOT, "include", f) for f in ("ig_detmath.h", "ig_detmath_tables.h", "instagraal_hip.h")]
 
@@ -1189,6 +1189,70 @@ class Context:
 
     def seq_end(self):
         _ck(lib().ig_seq_end(self._h))
+
+    # ---- the contact levels of the pyramid (the rule: pyramid_levels.py)
+    def pyr_begin(self, n_frags, a, b, count):
+        """opens the session over the level-0 list (0-based ids, file order) -> whether the list is canonical (its own level)"""
+        a, b = self._i32(a, "pyr_begin: a"), self._i32(b, "pyr_begin: b")
+        cnt = np.ascontiguousarray(count, np.int64).ravel()
+        if not (a.size == b.size == cnt.size):
+            raise HipError("pyr_begin: one a, one b and one count per entry")
+        flag = C.c_int32()
+        _ck(lib().ig_pyr_begin(self._h, C.c_int32(int(n_frags)), _p(a), _p(b), _p(cnt), C.c_int64(a.size), C.byref(flag)))
+        self._pyr_frags = int(n_frags)
+        return bool(flag.value)
+
+    def pyr_matrix(self, times=None):
+        """the level of the uploaded list becomes the current level -> its pixels; ``times``: a list that gets the passes' ms
+        (float32 [7]: ``ASSEMBLY_CONTACTS_PASSES``)"""
+        n = C.c_int64()
+        ms = np.zeros(len(ASSEMBLY_CONTACTS_PASSES), np.float32) if times is not None else None
+        _ck(lib().ig_pyr_matrix(self._h, C.byref(n), _p(ms)))
+        if times is not None:
+            times.append(ms)
+        return int(n.value)
+
+    def pyr_degrees(self):
+        """-> int64 [n_frags]: the partners of every fragment of the current level (``pyramid_levels.degrees``)"""
+        deg = np.zeros(getattr(self, "_pyr_frags", 0), np.int32)
+        _ck(lib().ig_pyr_degrees(self._h, _p(deg)))
+        return deg.astype(np.int64)
+
+    def pyr_remap(self, lut, n_new, skip_first, times=None):
+        """the next level from the current one through ``lut`` (int [n_old]: the new id or -1) -> the dict of
+        ``pyramid_levels.SCALARS``; ``times`` as in ``pyr_matrix``"""
+        from .pyramid_levels import SCALARS
+
+        t = self._i32(lut, "pyr_remap: lut")
+        n, sc = C.c_int64(), np.zeros(8, np.int64)
+        ms = np.zeros(len(ASSEMBLY_CONTACTS_PASSES), np.float32) if times is not None else None
+        _ck(lib().ig_pyr_remap(self._h, _p(t), C.c_int32(t.size), C.c_int32(int(n_new)), C.c_int32(1 if skip_first else 0), C.byref(n), _p(sc), _p(ms)))
+        self._pyr_frags = int(n_new)
+        if times is not None:
+            times.append(ms)
+        return {k: int(sc[i]) for i, k in enumerate(SCALARS)}
+
+    def pyr_level(self, piece=1 << 22):
+        """the current level -> (data3: int32 [3, nnz] = rows, columns, counts; rowptr: int64 [n_frags + 1])"""
+        U = getattr(self, "_pyr_frags", 0)
+        rowptr = np.zeros(U + 1, np.int64)
+        _ck(lib().ig_pyr_rows(self._h, _p(rowptr), C.c_int64(rowptr.size)))
+        n = int(rowptr[-1])
+        data3 = np.zeros((3, n), np.int32)
+        for a in range(0, n, int(piece)):
+            m = min(int(piece), n - a)
+            v = [np.zeros(m, np.int32) for _ in range(3)]
+            _ck(lib().ig_pyr_fetch(self._h, C.c_int64(a), C.c_int64(m), _p(v[0]), _p(v[1]), _p(v[2])))
+            for k in range(3):
+                data3[k, a:a + m] = v[k]
+        return data3, rowptr
+
+    def pyr_end(self):
+        _ck(lib().ig_pyr_end(self._h))
+
+    def debug_pyr_piece(self, entries):
+        """entries per upload piece of ``pyr_begin`` (0: the default)"""
+        _ck(lib().ig_debug_pyr_piece(self._h, C.c_int64(int(entries))))
 
     def balance_build_units(self, unit, n_units, ignore_diags=2):
         """``balance_build("bin")`` with the caller's unit of every position -> the dict ``balance_build`` returns (level: "units")"""

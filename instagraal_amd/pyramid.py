@@ -171,17 +171,16 @@ def fill_sparse_pyramid_level(store, level, contact_file, nfrags):
 # ------------------------------------------------------------------------------------------------ binning
 
 
-def subsample_data_set(contig_info, fragments_list, fact_sub_sample, abs_fragments_contacts, new_abs_fragments_contacts_file,
-                       min_bin_per_contig, new_contig_list_file, new_fragments_list_file, old_2_new_file):
-    """PS:468-724: bins of `fact_sub_sample` consecutive fragments inside every contig that has at least
-    `min_bin_per_contig` such bins (float32 test, PS:516); other contigs keep their fragments."""
+def subsample_tables(contig_info, fragments_list, fact_sub_sample, min_bin_per_contig, new_contig_list_file, new_fragments_list_file,
+                     old_2_new_file):
+    """The table part of `subsample_data_set`: writes the contig list, the fragment list and the sub->super index of the binned
+    level.  Returns (old2new, n_new): the 1-based new absolute id of every old fragment (int64) and the number of new fragments."""
     if fact_sub_sample <= 1:
         shutil.copy(fragments_list, new_fragments_list_file)
         shutil.copy(contig_info, new_contig_list_file)
-        shutil.copy(abs_fragments_contacts, new_abs_fragments_contacts_file)
         nfrags = file_len(fragments_list) - 1
         _write_table(old_2_new_file, ("current_id", "super_id"), [(i + 1, i + 1) for i in range(nfrags)])
-        return nfrags
+        return np.arange(1, nfrags + 1, dtype=np.int64), nfrags
 
     # -- which new bin every old fragment falls in, contig by contig
     old2new = []           # 1-based new absolute id per old absolute id (0-based list)
@@ -217,32 +216,41 @@ def subsample_data_set(contig_info, fragments_list, fact_sub_sample, abs_fragmen
         frag_rows.append((b["id_rel"], b["contig"], b["start_pos"], b["end_pos"], b["end_pos"] - b["start_pos"], np.array(b["gc"]).mean(),
                           b["init_last"] - b["init_first"] + 1, b["init_first"], b["init_last"], b["first"], b["last"]))
     _write_table(new_fragments_list_file, FRAG_HEADER_LN, frag_rows)
-
-    # -- contacts.  Q-P1: the reference consumes the header with readline() and then starts its loop at index 1 of
-    #    the remaining lines, so the FIRST contact of every level's list is dropped when binning (PS:672-677).
-    if abs_fragments_contacts != "SIMU":
-        fa, fb, nc = _read_contacts(abs_fragments_contacts, skip_first_data_line=True)
-        o2n = np.array(old2new, np.int64)
-        f1, f2, tot = _accumulate_contacts(o2n[fa] - 1, o2n[fb] - 1, nc)
-        _write_table(new_abs_fragments_contacts_file, CONTACT_HEADER, zip(f1.tolist(), f2.tolist(), tot.tolist()))
     _write_table(old_2_new_file, ("current_id", "super_id"), [(i + 1, v) for i, v in enumerate(old2new)])
-    return len(new_frags)
+    return np.array(old2new, np.int64), len(new_frags)
+
+
+def subsample_contacts(abs_fragments_contacts, new_abs_fragments_contacts_file, old2new, fact_sub_sample):
+    """The contact part of `subsample_data_set`.  Q-P1: the reference consumes the header with readline() and then starts its loop
+    at index 1 of the remaining lines, so the FIRST contact of every level's list is dropped when binning (PS:672-677)."""
+    if fact_sub_sample <= 1:
+        shutil.copy(abs_fragments_contacts, new_abs_fragments_contacts_file)
+        return
+    fa, fb, nc = _read_contacts(abs_fragments_contacts, skip_first_data_line=True)
+    f1, f2, tot = _accumulate_contacts(old2new[fa] - 1, old2new[fb] - 1, nc)
+    _write_table(new_abs_fragments_contacts_file, CONTACT_HEADER, zip(f1.tolist(), f2.tolist(), tot.tolist()))
+
+
+def subsample_data_set(contig_info, fragments_list, fact_sub_sample, abs_fragments_contacts, new_abs_fragments_contacts_file,
+                       min_bin_per_contig, new_contig_list_file, new_fragments_list_file, old_2_new_file):
+    """PS:468-724: bins of `fact_sub_sample` consecutive fragments inside every contig that has at least
+    `min_bin_per_contig` such bins (float32 test, PS:516); other contigs keep their fragments.  The table part and the contact
+    part, one behind the other."""
+    old2new, n_new = subsample_tables(contig_info, fragments_list, fact_sub_sample, min_bin_per_contig, new_contig_list_file,
+                                      new_fragments_list_file, old_2_new_file)
+    if abs_fragments_contacts != "SIMU":
+        subsample_contacts(abs_fragments_contacts, new_abs_fragments_contacts_file, old2new, fact_sub_sample)
+    return n_new
 
 
 # ------------------------------------------------------------------------------------------------ filter
 
 
-def remove_problematic_fragments(contig_info, fragments_list, abs_fragments_contacts, new_contig_list_file, new_fragments_list_file,
-                                 new_abs_fragments_contacts_file, level0, thresh_factor=1):
-    """PS:731-1029.  `level0` = (data3, nfrags) of the unfiltered level 0.  A fragment is "problematic" when the share of
-    fragments it has a contact with is <= mean - thresh_factor * std or > mean + 50 * std (float32 statistics), or when it
-    is shorter than 50 bp.  Walking every contig, a problematic fragment is not emitted: it is glued to the following
-    fragments until a good one closes the run (the emitted fragment spans the whole run); a run still open at the end of
-    a contig is destroyed together with its contacts.  Returns the lower threshold."""
-    data3, nfrags = level0
-    csr = sp.csr_matrix((data3[2, :], data3[0:2, :]), shape=(nfrags, nfrags))
-    full = csr + csr.transpose()
-    sparsity = np.float32(np.diff(full.indptr)) / np.float32(nfrags)
+def filter_tables(contig_info, fragments_list, new_contig_list_file, new_fragments_list_file, degrees, nfrags, thresh_factor=1):
+    """The table part of `remove_problematic_fragments`: `degrees[i]` = the number of fragments that fragment i has a contact with
+    (int32 [nfrags]).  Writes the contig list and the fragment list of the filtered level.  Returns (lut, thresh): lut[old] = the
+    0-based new id of every fragment, or -1 for a destroyed one (int64), and the lower threshold."""
+    sparsity = np.float32(np.asarray(degrees, np.int32)) / np.float32(nfrags)
     mean_s, std_s = sparsity.mean(), sparsity.std()
     thresh = mean_s - thresh_factor * std_s
     thresh_max = mean_s + 50 * std_s
@@ -302,15 +310,36 @@ def remove_problematic_fragments(contig_info, fragments_list, abs_fragments_cont
             cumul += st["n_new"]
     _write_table(new_contig_list_file, CONTIG_HEADER, rows)
 
-    fa, fb, nc = _read_contacts(abs_fragments_contacts)
-    lut = np.full(len(frows) + 2, -1, np.int64)
+    lut = np.full(len(frows), -1, np.int64)
     for k, v in old2new.items():
         if v != "destroyed":
-            lut[k] = v - 1
-    na, nb = lut[fa + 1], lut[fb + 1]
+            lut[k - 1] = v - 1
+    return lut, thresh
+
+
+def filter_contacts(abs_fragments_contacts, new_abs_fragments_contacts_file, lut):
+    """The contact part of `remove_problematic_fragments`: every contact of the file through `lut`, the destroyed ones dropped."""
+    fa, fb, nc = _read_contacts(abs_fragments_contacts)
+    na, nb = lut[fa], lut[fb]
     keep = (na >= 0) & (nb >= 0)
     f1, f2, tot = _accumulate_contacts(na[keep], nb[keep], nc[keep])
     _write_table(new_abs_fragments_contacts_file, CONTACT_HEADER, zip(f1.tolist(), f2.tolist(), tot.tolist()))
+
+
+def remove_problematic_fragments(contig_info, fragments_list, abs_fragments_contacts, new_contig_list_file, new_fragments_list_file,
+                                 new_abs_fragments_contacts_file, level0, thresh_factor=1):
+    """PS:731-1029.  `level0` = (data3, nfrags) of the unfiltered level 0.  A fragment is "problematic" when the share of
+    fragments it has a contact with is <= mean - thresh_factor * std or > mean + 50 * std (float32 statistics), or when it
+    is shorter than 50 bp.  Walking every contig, a problematic fragment is not emitted: it is glued to the following
+    fragments until a good one closes the run (the emitted fragment spans the whole run); a run still open at the end of
+    a contig is destroyed together with its contacts.  Returns the lower threshold.  The table part and the contact part, one
+    behind the other."""
+    data3, nfrags = level0
+    csr = sp.csr_matrix((data3[2, :], data3[0:2, :]), shape=(nfrags, nfrags))
+    full = csr + csr.transpose()
+    lut, thresh = filter_tables(contig_info, fragments_list, new_contig_list_file, new_fragments_list_file, np.diff(full.indptr), nfrags,
+                                thresh_factor=thresh_factor)
+    filter_contacts(abs_fragments_contacts, new_abs_fragments_contacts_file, lut)
     return thresh
 
 
@@ -490,15 +519,15 @@ class Level:
         self.n_contigs = n_contigs
         # mean trans contact level (PS:1876-1898): contacts of the upper-triangular level matrix whose row lies in a contig
         # and whose column does not, over the number of trans pairs
+        # -- in one pass over the entries, not one slice per contig: the exact integer sum of the counts whose row and column lie
+        #    in different contigs; the intra pairs as the same float additions in contig order as the reference's loop makes
         total_trans = 0
         n_tot_intra = 0
-        for c in range(1, n_contigs + 1):
-            members = np.nonzero(cid == c)[0]
-            rows_c = self.sparse_mat_csr[members, :]
-            intra = rows_c.tocsc()[:, members]
-            total_trans += rows_c.sum()
-            total_trans -= intra.sum()
-            n_tot_intra += len(members) * (len(members) - 1) / 2
+        if n_contigs:
+            trans = cid[data3[0, :]] != cid[data3[1, :]]
+            total_trans = np.int64(data3[2, trans].sum(dtype=np.int64))
+        for members in l_cont[1:n_contigs + 1].tolist():
+            n_tot_intra += members * (members - 1) / 2
         n_tot = n * (n - 1) / 2 - n_tot_intra
         with np.errstate(invalid="ignore", divide="ignore"):
             self.mean_value_trans = total_trans / np.float32(n_tot)

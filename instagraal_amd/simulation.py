@@ -426,6 +426,22 @@ def run_from_pairs(fasta, pairs, enzymes, output_folder, **run_kw):
     return run_instagraal(folder, str(fasta), output_folder=str(output_folder), **run_kw)
 
 
+def run_device_pyramid(hic_folder, reference_fa, output_folder=None, **run_kw):
+    """``run_instagraal`` with the pyramid's contact levels built on the device first:
+    ``pyramid_device.build_and_filter`` writes the pyramid where ``run_instagraal`` will look for it -- the same folders, byte for
+    byte -- with ``coverage_std`` and ``device`` taken from ``run_kw``; ``run_instagraal`` then runs unchanged, finds every level
+    present and rebuilds none.  FASTA + pairs: ``pre.run_pre`` followed by this.  Returns what ``run_instagraal`` returns."""
+    from . import pyramid_device
+
+    root = str(output_folder) if output_folder else os.path.join(os.getcwd(), "results")
+    os.makedirs(root, exist_ok=True)
+    device = run_kw.get("device", 0)
+    hic_pyr = pyramid_device.build_and_filter(str(hic_folder), SIZE_PYRAMID, FACTOR, thresh_factor=run_kw.get("coverage_std", 1), output_folder=root,
+                                              device=True if device is None or isinstance(device, bool) else device)
+    hic_pyr.close()
+    return run_instagraal(hic_folder, reference_fa, output_folder=output_folder, **run_kw)
+
+
 def run_and_polish(hic_folder, reference_fa, output_folder=None, post_polish=False, stats=False, junction="", lost="reference", **run_kw):
     """``run_instagraal`` with the reference's polish step and its statistics behind it; both switches default to off, and
     with both off this IS ``run_instagraal``: the same files, the same output.  ``post_polish`` runs ``scaffold_polish.polish_assembly`` in
