@@ -909,6 +909,28 @@ int ig_pyr_fetch(ig_ctx* ctx, int64_t first, int64_t n, int32_t* row, int32_t* c
 int ig_pyr_end(ig_ctx* ctx);
 /* entries per upload piece of ig_pyr_begin (0: the default): for tests of the upload in pieces */
 int ig_debug_pyr_piece(ig_ctx* ctx, int64_t entries);
+
+/* ---- the balancing's rows from a BUILT map (the rule: entries_of_rows, instagraal_amd/balance.py): a second build
+ * for the balancer above, not a second balancer.  ig_balance_build_snapshot fills the rows ig_balance_rows / _fetch / _run / _release
+ * serve from the handle's snapshot -- what ig_assembly_contacts_build (level 1), ig_assembly_contacts_build_units,
+ * ig_assembly_contacts_coarsen or ig_pairs_pixels_build left on the device -- without a pass over the contacts: an entry (u, v, c) with
+ * u == v, with v - u < ignore_diags (>= 1) or outside the mode is counted and dropped, every other one is kept as (u, v, c) and (v, u, c).
+ * mode: 0 all; 1 cis: group[u] == group[v]; 2 trans: group[u] != group[v]; group: int32 [n_group = the snapshot's units], none
+ * negative (NULL at mode 0).  A count is NOT limited to 32 bits; a unit's total is, to 2^53 - 1.  The snapshot stays as it is: a fetch or
+ * a coarsening behind this call sees the same bytes.  scalars: within_observed, band_observed, other_observed, kept_observed, entries
+ * (2 * kept), entries_in (the snapshot's), n_units, entries_out.  Refused, naming the reason, with nothing built: no snapshot, a level 0
+ * snapshot, ignore_diags < 1, a mode outside 0 .. 2, a mode without its groups, a negative group, a nuisance step or a chain in flight, a sharded handle,
+ * more than 2^31 - 1 entries, a total of 2^53 or more, rows that do not fit the free device memory beside the snapshot. */
+int ig_balance_build_snapshot(ig_ctx* ctx, int32_t ignore_diags, int32_t mode, const int32_t* group, int64_t n_group, int64_t* n_units, int64_t* n_entries,
+                              int64_t scalars[8]);
+/* tests: the same build over caller CSR data (upper triangular: col >= row, strictly ascending in a row; rowptr [n_rows + 1]) on a bare
+ * handle.  The data is checked on the host (a single count of 2^53 or more is refused there: the totals are 64-bit sums), becomes the handle's snapshot (level 2: ig_assembly_contacts_rows / _fetch / _coarsen see it)
+ * and the one implementation builds from it. */
+int ig_debug_balance_snapshot(ig_ctx* ctx, const int64_t* rowptr, const int32_t* col, const int64_t* count, int64_t n_rows, int32_t ignore_diags, int32_t mode,
+                              const int32_t* group, int64_t n_group, int64_t* n_units, int64_t* n_entries, int64_t scalars[8]);
+/* the build from the resident snapshot (ignore_diags 2, mode 0) n times, hipEvents around each pass -> ms_n [n][7]: count, rows, scatter,
+ * sort_short, sort_lds, sort_long, gather */
+int ig_debug_balance_snapshot_time(ig_ctx* ctx, int32_t n, float* ms_n);
 #ifdef __cplusplus
 }
 #endif

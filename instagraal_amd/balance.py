@@ -37,6 +37,16 @@ unit of sub-fragment s, -1 where it is not placed.
 
   Stop after the first iteration with var < ``tol``, or after ``max_iters``.  One more marg is computed from the final b;
   scale = vec_sum(marg_final) / k_final, weight = b / sqrt(scale), nan where the unit is masked or marg_final == 0.
+
+THE ENTRIES OF A BUILT MAP (``entries_of_rows``; the device: ``ig_balance_build_snapshot``, csrc/ig_kernels_balsnap.cuh).  Every map
+the project builds is an upper-triangular CSR snapshot (col >= row, the columns of a row strictly ascending, int64 counts, the
+diagonal allowed); its entries are the rule's ENTRIES without a pass over the contacts.  An entry (u, v, c), by the first test it
+meets: u == v -> ``within_observed``; v - u < ``ignore_diags`` -> ``band_observed``; outside the MODE -> ``other_observed`` ("cis"
+keeps group[u] == group[v], "trans" group[u] != group[v], "all" everything; ``group``: the scaffold of every unit); otherwise kept as
+(u, v, c) and (v, u, c).  The kept entries are distinct, so nothing is summed and a single count is NOT limited to 32 bits (a pixel
+of the scaffold matrix holds everything between two scaffolds); a unit's total still has to stay below 2^53.
+
+      within_observed + band_observed + other_observed + kept_observed == count.sum();  entries == 2 * (kept entries) == entries_out
 """
 from __future__ import annotations
 
@@ -49,6 +59,10 @@ OBSERVED_SCALARS = SCALARS[:4]
 LANES = 64
 DEFAULTS = dict(ignore_diags=2, min_nnz=10, min_count=0, mad_max=0, tol=1e-5, max_iters=200)
 MAX_TOTAL = 1 << 53
+MODES = ("all", "cis", "trans")
+# the order of ig_balance_build_snapshot's scalars[8]
+SNAPSHOT_SCALARS = ("within_observed", "band_observed", "other_observed", "kept_observed", "entries", "entries_in", "n_units", "entries_out")
+SNAPSHOT_OBSERVED_SCALARS = SNAPSHOT_SCALARS[:4]
 BALANCE_COLUMNS = ("unit", "scaffold", "start", "end", "weight")
 
 
@@ -130,6 +144,91 @@ def entries_host(key, n_units, row, col, cnt, ignore_diags=2):
     return dict(rowptr=rowptr, col=o_col.astype(np.int32), count=summed, nnz=nnz, total=total, unplaced_observed=int(cnt[unpl].sum()),
                 within_observed=int(cnt[within].sum()), band_observed=int(cnt[band].sum()), kept_observed=int(c.sum()), entries=2 * int(kept.sum()),
                 n_placed=int((key >= 0).sum()), n_units=U, entries_out=int(keys.size))
+
+
+def check_mode(mode):
+    """-> 0 "all", 1 "cis", 2 "trans"; ValueError otherwise"""
+    if mode not in MODES:
+        raise ValueError("balance: mode is one of %r (got %r)" % (MODES, mode))
+    return MODES.index(mode)
+
+
+def check_rows(rowptr, col, count):
+    """an upper-triangular CSR map -> (rowptr int64 [U + 1], col int64, count int64, the row of every entry); ValueError where it is
+    not one: rowptr from 0 and non-decreasing, ending at the number of entries; col >= row, below U, strictly ascending in a row;
+    no negative count"""
+    rowptr = np.asarray(rowptr, np.int64)
+    col, count = np.asarray(col, np.int64), np.asarray(count, np.int64)
+    if rowptr.ndim != 1 or rowptr.size < 1 or rowptr[0] != 0 or (np.diff(rowptr) < 0).any():
+        raise ValueError("balance: rowptr has n_units + 1 words, starts at 0 and does not decrease")
+    U = rowptr.size - 1
+    if col.ndim != 1 or col.shape != count.shape or col.size != int(rowptr[-1]):
+        raise ValueError("balance: col and count have rowptr[-1] = %d entries each (got %d, %d)" % (int(rowptr[-1]), col.size, count.size))
+    row = np.repeat(np.arange(U, dtype=np.int64), np.diff(rowptr))
+    if col.size:
+        if (col < row).any() or (col >= U).any():
+            raise ValueError("balance: the map is upper triangular: row <= col < %d" % U)
+        same = row[1:] == row[:-1]
+        if (col[1:][same] <= col[:-1][same]).any():
+            raise ValueError("balance: the columns of a row ascend strictly")
+        if (count < 0).any():
+            raise ValueError("balance: a negative count")
+    return rowptr, col, count, row
+
+
+def check_group(group, n_units, mode):
+    """-> group as int64 [U], or None where the mode needs none; ValueError for a mode other than "all" without one, a wrong length
+    and a negative group"""
+    if check_mode(mode) == 0:
+        return None
+    if group is None:
+        raise ValueError("balance: mode %r needs the group (the scaffold) of every unit" % (mode,))
+    g = np.asarray(group, np.int64)
+    if g.shape != (int(n_units),):
+        raise ValueError("balance: group has one entry per unit (%d, got shape %r)" % (int(n_units), g.shape))
+    if g.size and int(g.min()) < 0:
+        raise ValueError("balance: a negative group")
+    return g
+
+
+def entries_of_rows(rowptr, col, count, ignore_diags=2, group=None, mode="all"):
+    """The entries of the rule from a built map (the module's docstring).  rowptr, col, count: an upper-triangular CSR map; group:
+    int [U] for ``mode`` "cis" / "trans" -> the dict of ``entries_host`` (rowptr, col int32, count int64, nnz, total) with the scalars
+    of SNAPSHOT_SCALARS"""
+    d = check_ignore_diags(ignore_diags)
+    m = check_mode(mode)
+    rowptr, v, c, u = check_rows(rowptr, col, count)
+    U = rowptr.size - 1
+    g = check_group(group, U, mode)
+    within = u == v
+    band = ~within & (v - u < d)
+    other = np.zeros(u.size, bool)
+    if m:
+        same = g[u] == g[v]
+        other = ~within & ~band & (~same if m == 1 else same)
+    kept = ~within & ~band & ~other
+    ku, kv, kc = u[kept], v[kept], c[kept]
+    e_row, e_col, e_cnt = np.concatenate([ku, kv]), np.concatenate([kv, ku]), np.concatenate([kc, kc])
+    o = np.lexsort((e_col, e_row))
+    e_row, e_col, e_cnt = e_row[o], e_col[o], e_cnt[o]
+    nnz = np.bincount(e_row, minlength=U).astype(np.int64)[:U]
+    out_ptr = np.zeros(U + 1, np.int64)
+    out_ptr[1:] = np.cumsum(nnz)
+    psum = lambda a: int(a.sum(dtype=object)) if a.size else 0  # (a sum of int64 wraps silently: Python integers)
+    hi, lo = np.zeros(U, np.int64), np.zeros(U, np.int64)  # the halves summed apart: neither sum can wrap below 2^31 entries
+    np.add.at(hi, e_row, e_cnt >> 32)
+    np.add.at(lo, e_row, e_cnt & 0xffffffff)
+    too_much = (hi >= (1 << 21)) | (lo >= MAX_TOTAL)
+    total = np.where(too_much, 0, (hi << 32) + lo)
+    if (too_much | (total >= MAX_TOTAL)).any():
+        raise ValueError("balance: a unit's contacts sum to 2^53 or more (counts must convert to doubles exactly)")
+    return dict(rowptr=out_ptr, col=e_col.astype(np.int32), count=e_cnt, nnz=nnz, total=total, within_observed=psum(c[within]), band_observed=psum(c[band]),
+                other_observed=psum(c[other]), kept_observed=psum(kc), entries=2 * int(kept.sum()), entries_in=int(c.size), n_units=U, entries_out=int(e_cnt.size))
+
+
+def snapshot_observed_total(result):
+    """every count of the map, wherever it went"""
+    return sum(int(result[k]) for k in SNAPSHOT_OBSERVED_SCALARS)
 
 
 def observed_total(result):
@@ -274,6 +373,14 @@ def balance_host(position, row, col, cnt, level="bin", unit=None, max_side=2048,
     return out
 
 
+def balance_rows_host(rowptr, col, count, group=None, mode="all", ignore_diags=2, min_nnz=10, min_count=0, mad_max=0, tol=1e-5, max_iters=200):
+    """The whole rule from a built map: ``entries_of_rows``, then the mask, the iterations and the finish of ``balance_host``."""
+    ent = entries_of_rows(rowptr, col, count, ignore_diags, group, mode)
+    out = balance_entries(ent, min_nnz, min_count, mad_max, tol, max_iters)
+    out.update(level="units", mode=mode, ignore_diags=int(ignore_diags))
+    return out
+
+
 def balanced(count, row, col, weight):
     """count * weight[row] * weight[col] -> f64 (nan where a unit has no weight)"""
     w = np.asarray(weight, np.float64)
@@ -297,6 +404,16 @@ def write_weights(path, table, result):
                                                                      "converged", "scale") if k in result)
                 + " " + " ".join("%s=%d" % (k, result[k]) for k in SCALARS if k in result) + "\n")
     return int(w.size)
+
+
+def write_snapshot_weights(path, table, result):
+    """``write_weights`` for a result balanced from a built map (``balance_rows_host``, or the device's), and one more comment line
+    behind it: the mode and the scalars only that route has (``other_observed``, ``entries_in``) -- a file written under "cis" tells so.
+    ``read_weights`` reads both forms.  -> the number of units written"""
+    n = write_weights(path, table, result)
+    with open(path, "a") as f:
+        f.write("# source=snapshot mode=%s other_observed=%d entries_in=%d\n" % (result["mode"], result["other_observed"], result["entries_in"]))
+    return n
 
 
 def read_weights(path):

@@ -18,8 +18,8 @@ SRC = os.path.join(HERE, "csrc", "ig_hip.hip")
 SRC_HOST = os.path.join(HERE, "csrc", "ig_draw.cpp")  # host-only part: the candidate draw
 DEPS = [SRC, SRC_HOST] + [os.path.join(HERE, "csrc", f) for f in ("ig_ops.cuh", "ig_common.cuh", "ig_model.cuh", "ig_kernels_setup.cuh",
                                                           "ig_kernels_score.cuh", "ig_kernels_screen.cuh", "ig_kernels_commit.cuh",
-                                                          "ig_kernels_nuis.cuh", "ig_kernels_wave.cuh", "ig_kernels_genome.cuh", "ig_kernels_rows.cuh", "ig_kernels_map.cuh", "ig_kernels_law.cuh", "ig_kernels_junc.cuh", "ig_kernels_lift.cuh", "ig_kernels_join.cuh", "ig_kernels_emap.cuh", "ig_kernels_place.cuh", "ig_kernels_orient.cuh", "ig_kernels_bal.cuh", "ig_kernels_gap.cuh", "ig_kernels_zoom.cuh", "ig_kernels_segplace.cuh", "ig_kernels_edit.cuh", "ig_kernels_cutjoin.cuh", "ig_kernels_pairs.cuh", "ig_kernels_pre.cuh", "ig_kernels_seq.cuh", "ig_kernels_pyr.cuh", "ig_host_core.inc", "ig_host_upload.inc", "ig_host_genome.inc", "ig_host_rows.inc",
-                                                          "ig_host_map.inc", "ig_host_law.inc", "ig_host_junc.inc", "ig_host_lift.inc", "ig_host_join.inc", "ig_host_emap.inc", "ig_host_place.inc", "ig_host_orient.inc", "ig_host_bal.inc", "ig_host_gap.inc", "ig_host_zoom.inc", "ig_host_segplace.inc", "ig_host_edit.inc", "ig_host_cutjoin.inc", "ig_host_pairs.inc", "ig_host_pre.inc", "ig_host_seq.inc", "ig_host_pyr.inc",
+                                                          "ig_kernels_nuis.cuh", "ig_kernels_wave.cuh", "ig_kernels_genome.cuh", "ig_kernels_rows.cuh", "ig_kernels_map.cuh", "ig_kernels_law.cuh", "ig_kernels_junc.cuh", "ig_kernels_lift.cuh", "ig_kernels_join.cuh", "ig_kernels_emap.cuh", "ig_kernels_place.cuh", "ig_kernels_orient.cuh", "ig_kernels_bal.cuh", "ig_kernels_gap.cuh", "ig_kernels_zoom.cuh", "ig_kernels_segplace.cuh", "ig_kernels_edit.cuh", "ig_kernels_cutjoin.cuh", "ig_kernels_pairs.cuh", "ig_kernels_pre.cuh", "ig_kernels_seq.cuh", "ig_kernels_pyr.cuh", "ig_kernels_balsnap.cuh", "ig_host_core.inc", "ig_host_upload.inc", "ig_host_genome.inc", "ig_host_rows.inc",
+                                                          "ig_host_map.inc", "ig_host_law.inc", "ig_host_junc.inc", "ig_host_lift.inc", "ig_host_join.inc", "ig_host_emap.inc", "ig_host_place.inc", "ig_host_orient.inc", "ig_host_bal.inc", "ig_host_gap.inc", "ig_host_zoom.inc", "ig_host_segplace.inc", "ig_host_edit.inc", "ig_host_cutjoin.inc", "ig_host_pairs.inc", "ig_host_pre.inc", "ig_host_seq.inc", "ig_host_pyr.inc", "ig_host_balsnap.inc",
                                                           "ig_host_batch.inc", "ig_host_nuis.inc", "ig_host_debug.inc")] + \
        [os.path.join(ROOT, "include", f) for f in ("ig_detmath.h", "ig_detmath_tables.h", "instagraal_hip.h")]
 
@@ -34,6 +34,7 @@ ORIENTATION_SUPPORT_FORMS = {"observed": ("atomic", "combined"), "model": ("defa
 GAP_SUPPORT_WAVE_TERMS = 8192  # GAP_WAVE_TERMS (csrc/ig_kernels_gap.cuh): pairs * gaps beyond this take a workgroup in the model pass
 GAP_SUPPORT_PASSES = ("observed", "model", "model_wave", "model_workgroup")  # ig_debug_gap_support_time
 BALANCE_BUILD_PASSES = ("units", "count", "rows", "scatter", "sort_short", "sort_lds", "sort_long", "reduce")  # ig_debug_balance_build_time
+BALANCE_SNAPSHOT_PASSES = ("count", "rows", "scatter", "sort_short", "sort_lds", "sort_long", "gather")  # ig_debug_balance_snapshot_time
 ZOOM_PASSES = ("rowstart", "words", "sort_short", "sort_lds", "sort_long", "reduce")  # the passes of ig_assembly_contacts_coarsen
 BALANCE_FORMS = ("default", "wave", "packed")  # ig_debug_balance_form
 EDIT_PASSES = ("plan", "state", "tables", "delta", "zero", "whole")  # ig_debug_edit_time
@@ -1734,6 +1735,59 @@ class Context:
 
         ms = np.zeros((int(n), len(BALANCE_BUILD_PASSES)), np.float32)
         _ck(lib().ig_debug_balance_build_time(self._h, C.c_int32(LEVELS.index(level)), C.c_int32(int(max_side)), C.c_int32(int(ignore_diags)), C.c_int32(int(n)), _p(ms)))
+        return ms
+
+    # ---- the balancing's rows from a built map (the rule: balance.entries_of_rows)
+    @staticmethod
+    def _snapshot_mode(mode, group, who):
+        from .balance import MODES
+
+        if mode not in MODES:
+            raise HipError("%s: mode is one of %r (got %r)" % (who, MODES, mode))
+        g = None if group is None else as_int32_exact(group, who + ": group")
+        return MODES.index(mode), g
+
+    def _snapshot_rows(self, nu, ne, sc):
+        from .balance import SNAPSHOT_SCALARS
+
+        U = int(nu.value)
+        rowptr, nnz, total = np.zeros(U + 1, np.int64), np.zeros(U, np.int64), np.zeros(U, np.int64)
+        _ck(lib().ig_balance_rows(self._h, _p(rowptr), _p(nnz), _p(total), C.c_int64(rowptr.size)))
+        out = dict(level="units", rowptr=rowptr, nnz=nnz, total=total, n_entries=int(ne.value))
+        out.update((k, int(v)) for k, v in zip(SNAPSHOT_SCALARS, sc))
+        return out
+
+    def balance_build_snapshot(self, ignore_diags=2, mode="all", group=None):
+        """the balancing's rows from the snapshot on the device (``assembly_contacts("bin")``, ``assembly_contacts_units``,
+        ``assembly_contacts_coarsen`` or ``pairs_pixels`` left it there), which stays as it is.  ``mode`` "cis" / "trans" with ``group``
+        (int per unit: its scaffold) keeps the entries inside / between groups.  -> dict: rowptr (int64 [n_units + 1]), nnz and
+        total (int64 [n_units]), n_entries and the int64 scalars of ``balance.SNAPSHOT_SCALARS``; the entries come through
+        ``balance_fetch``, the iterations through ``balance_run``"""
+        m, g = self._snapshot_mode(mode, group, "balance_build_snapshot")
+        nu, ne, sc = C.c_int64(), C.c_int64(), np.zeros(8, np.int64)
+        _ck(lib().ig_balance_build_snapshot(self._h, C.c_int32(int(ignore_diags)), C.c_int32(m), _p(g), C.c_int64(0 if g is None else g.size), C.byref(nu), C.byref(ne),
+                                            _p(sc)))
+        return self._snapshot_rows(nu, ne, sc)
+
+    def debug_balance_snapshot(self, rowptr, col, count, ignore_diags=2, mode="all", group=None):
+        """``balance_build_snapshot`` over caller CSR data (upper triangular) on a bare handle (tests/test_hip_balance_snapshot.py): the
+        data becomes the handle's snapshot, which ``assembly_contacts_fetch`` and ``assembly_contacts_coarsen`` then see -> the same
+        dict"""
+        rowptr = np.ascontiguousarray(rowptr, np.int64)
+        col, count = np.ascontiguousarray(col, np.int32), np.ascontiguousarray(count, np.int64)
+        if rowptr.ndim != 1 or rowptr.size < 1 or col.shape != count.shape or col.ndim != 1 or col.size != int(rowptr[-1]):
+            raise HipError("debug_balance_snapshot: rowptr [U + 1], col and count [rowptr[U]]")
+        m, g = self._snapshot_mode(mode, group, "debug_balance_snapshot")
+        nu, ne, sc = C.c_int64(), C.c_int64(), np.zeros(8, np.int64)
+        _ck(lib().ig_debug_balance_snapshot(self._h, _p(rowptr), _p(col), _p(count), C.c_int64(rowptr.size - 1), C.c_int32(int(ignore_diags)), C.c_int32(m), _p(g),
+                                            C.c_int64(0 if g is None else g.size), C.byref(nu), C.byref(ne), _p(sc)))
+        return self._snapshot_rows(nu, ne, sc)
+
+    def debug_balance_snapshot_time(self, n=1):
+        """the build from the resident snapshot n times with hipEvents around each pass -> ms [n, 7]: ``BALANCE_SNAPSHOT_PASSES``; the
+        snapshot stays, and so do the last build's rows"""
+        ms = np.zeros((int(n), len(BALANCE_SNAPSHOT_PASSES)), np.float32)
+        _ck(lib().ig_debug_balance_snapshot_time(self._h, C.c_int32(int(n)), _p(ms)))
         return ms
 
     # ---- bookkeeping

@@ -1076,15 +1076,22 @@ class sampler:  # noqa: N801 - the reference's class name
         scaffold), or a caller's ``(unit, n_units)`` per position.  -> the dict ``assembly_contacts`` returns, with ``bins`` the table of
         the fixed bins (contig, start, end; None for a caller's units), ``unit`` per position and ``units_without_position`` -- the
         fixed bins no midpoint falls into: above 0 the resolution is below what the fragments carry.  ``diagonal`` and ``balance`` as
-        in ``assembly_contacts``.  The reference's post.py bins the raw read pairs instead: ``pairs_contacts(pairs, binsize)`` does that on the
+        in ``assembly_contacts``; the ``balance`` dict may hold ``source`` and ``mode`` as in ``write_zoom_levels``.  The reference's post.py bins the raw read pairs instead: ``pairs_contacts(pairs, binsize)`` does that on the
         device, a pair counted where it falls."""
         from . import assembly_contacts as ac, balance as bal, zoom_levels as zl
 
         order, table_sub, d = self._zoom_frame(diagonal)
         unit, U, bins = self._zoom_units(table_sub, binsize, units)
+        source, mode, bal_kw = self._balance_options(balance) if balance else ("contacts", "all", {})
+        if mode != "all" and bins is None:
+            raise ValueError("resolution_contacts: mode %r needs the scaffold of every unit, which a caller's units do not tell" % (mode,))
+        if mode == "cis" and units == "scaffold":
+            raise ValueError("resolution_contacts: mode \"cis\" keeps nothing of the scaffold matrix (every pixel off its diagonal lies between two scaffolds)")
         res = self.ctx.assembly_contacts_units(unit, U)
         try:
             col, count = self.ctx.assembly_contacts_fetch(0, res["n_entries"])
+            if source == "snapshot":  # from the snapshot where it lies, before it goes
+                weight = self._balance_snapshot(None if bins is None else bins["contig"], mode, **bal_kw)["weight"]
         finally:
             self.ctx.assembly_contacts_release()
         rowptr = res.pop("rowptr")
@@ -1096,7 +1103,7 @@ class sampler:  # noqa: N801 - the reference's class name
                    contacts_diagonal=0 if diag is None else int(diag.sum()), units_without_position=zl.units_without_position(unit, U),
                    binsize=None if binsize is None else int(binsize))
         if balance:
-            res["weight"] = self._balance_units(unit, U, **(balance if isinstance(balance, dict) else {}))["weight"]
+            res["weight"] = weight if source == "snapshot" else self._balance_units(unit, U, **bal_kw)["weight"]
             res["balanced"] = bal.balanced(count, ac.rows_of(rowptr), col, res["weight"])
         return res
 
@@ -1110,13 +1117,19 @@ class sampler:  # noqa: N801 - the reference's class name
         scaffold matrix to ``<folder>/scaffolds/``, each what ``cooler load -f coo`` takes.  ``zoom_levels.plan`` decides how a level is
         made: built from the contacts, or -- its bin size a multiple of the level before it -- coarsened on the device from that
         level (``ig_assembly_contacts_coarsen``); the scaffold matrix is coarsened from the last level.  The bytes do not depend on the
-        plan.  ``balance=True`` (or a dict of ``balance()``'s parameters): ``weights.tsv`` per level.  -> a list, per level in order:
+        plan.  ``balance=True`` (or a dict of ``balance()``'s parameters): ``weights.tsv`` per level.  The dict may hold ``source`` --
+        "contacts" (the default: every level's rows from a pass over the contacts, ``ig_balance_build_units``) or "snapshot" (from
+        the level where it lies on the device, ``ig_balance_build_snapshot``: the same weights, and one more comment line in the file that
+        names the source and the mode) -- and ``mode`` "cis" / "trans" (the
+        pixels inside / between scaffolds only; they imply the snapshot; under "cis" the scaffold matrix has nothing to keep: no
+        ``weights.tsv`` there and ``balanced: False`` in its dict).  -> a list, per level in order:
         dict of ``level`` (bp, or "scaffolds"), ``made`` (``("direct",)`` / ``("coarsen", factor)``), ``folder``, the scalars,
         ``n_units``, ``units_without_position``, ``contacts_diagonal`` and ``pixels_written``."""
-        from . import assembly_contacts as ac, zoom_levels as zl
+        from . import assembly_contacts as ac, balance as bal, zoom_levels as zl
 
         import os
 
+        source, mode, bal_kw = self._balance_options(balance) if balance else ("contacts", "all", {})
         res_list = zl.check_resolutions(resolutions)
         steps = list(zip(res_list, zl.plan(res_list)))
         order, table_sub, d = self._zoom_frame(diagonal)
@@ -1139,10 +1152,12 @@ class sampler:  # noqa: N801 - the reference's class name
                 one = {k: res[k] for k in ac.SCALARS}
                 one.update(level=B, made=made, folder=where, units_without_position=zl.units_without_position(unit, U),
                            contacts_diagonal=0 if diag is None else int(diag.sum()), pixels_written=n)
-                if balance:
-                    from . import balance as bal
-
-                    w = self._balance_units(unit, U, **(balance if isinstance(balance, dict) else {}))
+                if balance and source == "snapshot":  # from the level where it lies on the device: built or coarsened a moment ago
+                    one["balanced"] = not (B == "scaffolds" and mode == "cis")
+                    if one["balanced"]:
+                        bal.write_snapshot_weights(os.path.join(where, "weights.tsv"), bins, self._balance_snapshot(bins["contig"], mode, **bal_kw))
+                elif balance:
+                    w = self._balance_units(unit, U, **bal_kw)
                     w["level"] = "units"
                     bal.write_weights(os.path.join(where, "weights.tsv"), bins, w)
                 out.append(one)
@@ -1248,12 +1263,12 @@ class sampler:  # noqa: N801 - the reference's class name
         (the positions), "bin" (the placed bins: the rows of info_frags.txt) or "scaffold".  ``pairs``: a path or arrays -- lifted in a
         session of the call's own, ended behind it, and REFUSED (ValueError) while a session is open, whose store it would discard -- or
         None: the open session's store, which stays.  -> the dict ``resolution_contacts`` returns (rowptr, col, count, the scalars, ``bins``, ``chrom_sizes``,
-        ``binsize``) plus the lift's scalars.  ``balance``: not offered here -- the balancer builds its rows from the contacts, not
-        from a built snapshot."""
+        ``binsize``) plus the lift's scalars.  ``balance``: not offered by this method -- ``pairs_balance`` balances the same map from
+        its snapshot on the device and returns this dict with the weights."""
         from . import assembly_contacts as ac, pairs_lift as pl
 
         if balance:
-            raise NotImplementedError("pairs_contacts: balancing a map of pairs is not offered (the balancer reads the contacts, not a built snapshot)")
+            raise NotImplementedError("pairs_contacts: balancing is pairs_balance's (the same map with its weights, balanced from the snapshot on the device)")
         if (binsize is None) == (units is None):
             raise ValueError("pairs: give binsize (bp) or units (\"sub\", \"bin\", \"scaffold\"), not both")
         lifted = self._pairs_load(pairs)
@@ -1273,14 +1288,95 @@ class sampler:  # noqa: N801 - the reference's class name
                 self.pairs_end()
         return res
 
+    def _balance_snapshot(self, group=None, mode="all", ignore_diags=2, min_nnz=10, min_count=0, mad_max=0, tol=1e-5, max_iters=200):
+        """``balance`` over the snapshot that is on the device at this moment (``ig_balance_build_snapshot``; the rule:
+        ``balance.balance_rows_host``), which stays there as it is: the dict ``_balance_units`` returns, with the scalars of
+        ``balance.SNAPSHOT_SCALARS`` and ``mode``.  ``group``: the scaffold of every unit (read for "cis" / "trans")"""
+        from . import balance as bal
+
+        d = bal.check_ignore_diags(ignore_diags)
+        tol, max_iters = bal.check_run(tol, max_iters)
+        res = self.ctx.balance_build_snapshot(d, mode, group if bal.check_mode(mode) else None)
+        try:
+            masked = bal.mask_units(res["nnz"], res["total"], min_nnz, min_count, mad_max)
+            res.update(self.ctx.balance_run(np.where(masked, 0.0, 1.0), tol, max_iters))
+        finally:
+            self.ctx.balance_release()
+        res["weight"], res["scale"] = bal.finish(res["b"], res["marg_final"], masked)
+        res.update(masked=masked, mode=mode, ignore_diags=d, min_nnz=int(min_nnz), min_count=int(min_count), mad_max=mad_max, tol=tol, max_iters=max_iters)
+        return res
+
+    @staticmethod
+    def _balance_options(balance):
+        """``balance`` of the writers (True, or a dict of ``balance()``'s parameters with ``source`` and ``mode``) -> (source, mode,
+        the parameters); "cis" and "trans" imply the snapshot"""
+        from . import balance as bal
+
+        kw = dict(balance) if isinstance(balance, dict) else {}
+        mode = kw.pop("mode", "all")
+        source = kw.pop("source", "contacts" if bal.check_mode(mode) == 0 else "snapshot")
+        if source not in ("contacts", "snapshot"):
+            raise ValueError("balance: source is \"contacts\" or \"snapshot\" (got %r)" % (source,))
+        if mode != "all" and source != "snapshot":
+            raise ValueError("balance: mode %r is balanced from the snapshot (source=\"snapshot\")" % (mode,))
+        return source, mode, kw
+
+    def pairs_balance(self, pairs, binsize=None, units=None, mode="all", ignore_diags=2, min_nnz=10, min_count=0, mad_max=0, tol=1e-5, max_iters=200):
+        """``pairs_contacts`` balanced (``ig_pairs_pixels_build``, then ``ig_balance_build_snapshot`` / ``ig_balance_run`` over the
+        pixels where they lie on the device; the rule: ``balance.balance_rows_host``).  ``pairs``, ``binsize`` and ``units`` -- and the
+        rules of the session -- as in ``pairs_contacts``; the parameters as in ``balance``; ``mode``: "all", or "cis" / "trans": only the
+        pixels inside / between scaffolds are balanced (cooler's ``cis_only`` / ``trans_only``; "cis" at ``units="scaffold"`` has
+        nothing to keep: ValueError; under "cis" the one mean of the iteration ties no two scaffolds' scales together: every
+        scaffold's block comes out balanced, ``converged`` in general False -- DESIGN 4.29).  -> the dict ``pairs_contacts`` returns plus ``weight`` (f64 per unit, nan where it has none),
+        ``balanced`` (count * weight[row] * weight[col] per entry), ``masked``, ``scale``, ``n_iters``, ``converged``, ``variance``,
+        ``within_observed``, ``band_observed``, ``other_observed``, ``kept_observed``, ``entries``, and under ``balance_scalars`` all of
+        ``balance.SNAPSHOT_SCALARS`` (``entries_in`` and ``entries_out`` mean the map's in this dict, the balancer's rows there)."""
+        from . import assembly_contacts as ac, balance as bal, pairs_lift as pl
+
+        bal.check_mode(mode)
+        if (binsize is None) == (units is None):
+            raise ValueError("pairs: give binsize (bp) or units (\"sub\", \"bin\", \"scaffold\"), not both")
+        if mode == "cis" and units == "scaffold":
+            raise ValueError("pairs_balance: mode \"cis\" keeps nothing of the scaffold matrix (every pixel off its diagonal lies between two scaffolds)")
+        lifted = self._pairs_load(pairs)
+        try:
+            kind, B, _, _ = pl.check_units(self._pairs, units if binsize is None else binsize)
+            res = self.ctx.pairs_pixels(kind, B)
+            try:
+                bins = self._pairs_bins(kind, B)
+                w = self._balance_snapshot(bins["contig"], mode, ignore_diags, min_nnz, min_count, mad_max, tol, max_iters)
+                col, count = self.ctx.assembly_contacts_fetch(0, res["n_entries"])
+            finally:
+                self.ctx.assembly_contacts_release()
+            res.pop("n_entries")
+            res.update(col=col, count=count, bins=bins, chrom_sizes=ac.chrom_sizes(self._pairs["table_sub"]), binsize=B if kind == "binsize" else None, units=kind)
+            res.update(lifted)
+            res.update((k, w[k]) for k in ("weight", "masked", "scale", "n_iters", "converged", "variance", "mode", "ignore_diags", "within_observed", "band_observed",
+                                           "other_observed", "kept_observed", "entries"))
+            res["balance_scalars"] = {k: w[k] for k in bal.SNAPSHOT_SCALARS}
+            res["balanced"] = bal.balanced(count, ac.rows_of(res["rowptr"]), col, w["weight"])
+        finally:
+            if pairs is not None:
+                self.pairs_end()
+        return res
+
     def write_pairs_zoom_levels(self, folder, pairs, resolutions=_zoom_levels.DEFAULT_RESOLUTIONS, scaffolds=True, balance=False, block_rows=None):
         """``write_zoom_levels`` from read pairs: the same folders and writers, every level from the store of lifted pairs -- one
         build at the finest bin size of a run of multiples, coarsenings on the device behind it (``zoom_levels.plan``), the scaffold
-        matrix coarsened from the last level.  -> a list, per level: ``level``, ``made``, ``folder``, the scalars, ``pixels_written``."""
-        from . import assembly_contacts as ac, zoom_levels as zl
+        matrix coarsened from the last level.  ``balance=True`` (or a dict of ``pairs_balance``'s parameters, ``mode`` among them):
+        ``weights.tsv`` per level (``balance.write_snapshot_weights``: its last line names the mode), every level balanced from the snapshot that is on the device at that
+        moment -- built or coarsened --, the group of a fixed bin its scaffold; the other files are the same bytes.  Under ``mode="cis"``
+        the scaffold matrix has nothing to keep: no ``weights.tsv`` there, and its dict says ``balanced: False``.  -> a list, per level:
+        ``level``, ``made``, ``folder``, the scalars, ``pixels_written`` (and, balanced, ``balanced``, ``n_iters``, ``converged``)."""
+        import os
+
+        from . import assembly_contacts as ac, balance as bal, zoom_levels as zl
 
         if balance:
-            raise NotImplementedError("write_pairs_zoom_levels: balancing a map of pairs is not offered (the balancer reads the contacts, not a built snapshot)")
+            source, mode, bal_kw = self._balance_options(balance)
+            if "source" in (balance if isinstance(balance, dict) else {}) and source != "snapshot":
+                raise ValueError("write_pairs_zoom_levels: a map of pairs is balanced from its snapshot (source=\"snapshot\")")
+            bal.check_ignore_diags(bal_kw.get("ignore_diags", 2))
         res_list = zl.check_resolutions(resolutions)
         steps = list(zip(res_list, zl.plan(res_list)))
         rows = ac.DEFAULT_BLOCK_ROWS if block_rows is None else block_rows
@@ -1302,6 +1398,12 @@ class sampler:  # noqa: N801 - the reference's class name
                 one = {k: res[k] for k in ac.SCALARS}
                 one.update(level=B, made=made, folder=where, pixels_written=n)
                 one.update(lifted)
+                if balance:
+                    one["balanced"] = not (B == "scaffolds" and mode == "cis")
+                    if one["balanced"]:
+                        w = self._balance_snapshot(bins["contig"], mode, **bal_kw)
+                        bal.write_snapshot_weights(os.path.join(where, "weights.tsv"), bins, w)
+                        one.update(n_iters=w["n_iters"], converged=w["converged"])
                 out.append(one)
         finally:
             self.ctx.assembly_contacts_release()

@@ -196,7 +196,7 @@ class instagraal_class:
 
     def full_em(self, n_cycles, n_neighbours, bomb, id_start_sample_param, save_matrix=False, save_law=False, save_junctions=False,
                 save_contacts=False, save_joins=False, save_residuals=False, save_placements=False, save_orientations=False, save_weights=False, save_gaps=False,
-                save_resolutions=False, save_segment_placements=False, polish=False, save_cut_join=False, pairs=None, save_lifted_pairs=False):  # IG:196-291
+                save_resolutions=False, save_segment_placements=False, polish=False, save_cut_join=False, pairs=None, save_lifted_pairs=False, balance_pairs=False):  # IG:196-291
         sampler = self.simulation.sampler
         if bomb:
             sampler.bomb_the_genome()
@@ -269,7 +269,8 @@ class instagraal_class:
                     sampler.write_lifted_pairs(pairs, self._out("lifted.pairs.gz"), keep_session=True)
                 else:
                     sampler._pairs_load(pairs)
-                sampler.write_pairs_zoom_levels(self._out("pairs_zoom_levels"), None, zl.DEFAULT_RESOLUTIONS if save_resolutions in (False, True) else tuple(save_resolutions))
+                sampler.write_pairs_zoom_levels(self._out("pairs_zoom_levels"), None, zl.DEFAULT_RESOLUTIONS if save_resolutions in (False, True) else tuple(save_resolutions),
+                                                **(dict(balance=balance_pairs) if balance_pairs else {}))
                 law = sampler.pairs_distance_law(None)
                 pl.write_law(self._out("pairs_law.txt"), law["counts"], law["edges_bp"])
             finally:
@@ -377,7 +378,22 @@ def run_instagraal(hic_folder, reference_fa, output_folder=None, level=4, cycles
     folders of ``zoom_levels/`` built from the read pairs lifted onto the final genome, a pair counted where it falls (bin sizes:
     ``save_resolutions`` where it is a tuple, else the defaults) -- and ``pairs_law.txt``, their distance histogram per strand
     combination; with ``save_lifted_pairs`` also ``lifted.pairs.gz``, the pairs file in the coordinates of ``genome.fasta``
-    (``sampler.write_pairs_zoom_levels``, ``sampler.pairs_distance_law``, ``sampler.write_lifted_pairs``)."""
+    (``sampler.write_pairs_zoom_levels``, ``sampler.pairs_distance_law``, ``sampler.write_lifted_pairs``); the balancing
+    weights of those levels are ``run_balanced_pairs``' (this function's signature stays as it is)."""
+    return _run_instagraal(hic_folder, reference_fa, output_folder=output_folder, level=level, cycles=cycles, coverage_std=coverage_std, neighborhood=neighborhood,
+                           device=device, circular=circular, bomb=bomb, pyramid_only=pyramid_only, save_pickle=save_pickle, save_matrix=save_matrix, simple=simple,
+                           save_law=save_law, save_junctions=save_junctions, save_contacts=save_contacts, save_joins=save_joins, save_residuals=save_residuals,
+                           save_placements=save_placements, save_orientations=save_orientations, save_weights=save_weights, save_gaps=save_gaps,
+                           save_resolutions=save_resolutions, save_segment_placements=save_segment_placements, polish=polish, save_cut_join=save_cut_join, pairs=pairs,
+                           save_lifted_pairs=save_lifted_pairs)
+
+
+def _run_instagraal(hic_folder, reference_fa, output_folder=None, level=4, cycles=100, coverage_std=1, neighborhood=5, device=0,
+                    circular=False, bomb=False, pyramid_only=False, save_pickle=False, save_matrix=False, simple=False, save_law=False,
+                    save_junctions=False, save_contacts=False, save_joins=False, save_residuals=False, save_placements=False,
+                    save_orientations=False, save_weights=False, save_gaps=False, save_resolutions=False, save_segment_placements=False, polish=False,
+                    save_cut_join=False, pairs=None, save_lifted_pairs=False, balance_pairs=False):
+    """``run_instagraal``'s body, with the one keyword its pinned signature does not have: ``balance_pairs`` (``full_em``)"""
     import warnings
 
     if simple and not pyramid_only:
@@ -399,7 +415,8 @@ def run_instagraal(hic_folder, reference_fa, output_folder=None, level=4, cycles
     p2.full_em(n_cycles=cycles, n_neighbours=neighborhood, bomb=bomb, id_start_sample_param=4, save_matrix=save_matrix, save_law=save_law,
                save_junctions=save_junctions, save_contacts=save_contacts, save_joins=save_joins, save_residuals=save_residuals, save_placements=save_placements,
                save_orientations=save_orientations, save_weights=save_weights, save_gaps=save_gaps, save_resolutions=save_resolutions,
-               save_segment_placements=save_segment_placements, polish=polish, save_cut_join=save_cut_join, pairs=pairs, save_lifted_pairs=save_lifted_pairs)
+               save_segment_placements=save_segment_placements, polish=polish, save_cut_join=save_cut_join, pairs=pairs, save_lifted_pairs=save_lifted_pairs,
+               balance_pairs=balance_pairs)
     if save_pickle:  # IG:589-594
         import pickle
 
@@ -424,6 +441,14 @@ def run_from_pairs(fasta, pairs, enzymes, output_folder, **run_kw):
     folder = os.path.join(str(output_folder), "pre")
     pre.run_pre(fasta, pairs, enzymes, folder)
     return run_instagraal(folder, str(fasta), output_folder=str(output_folder), **run_kw)
+
+
+def run_balanced_pairs(hic_folder, reference_fa, pairs, output_folder=None, balance_pairs=True, **run_kw):
+    """``run_instagraal(..., pairs=pairs)`` with the balancing weights of the read-pair maps: ``balance_pairs`` (True, or a
+    dict of ``sampler.pairs_balance``'s parameters such as ``mode="cis"``) writes ``weights.tsv`` beside the pixels of every level of
+    ``pairs_zoom_levels/`` (``sampler.write_pairs_zoom_levels(balance=...)``), as the reference's ``post`` ends with ``cooler balance`` on
+    every zoom level; False: this IS ``run_instagraal``, the same files and bytes.  Returns what ``run_instagraal`` returns."""
+    return _run_instagraal(hic_folder, reference_fa, output_folder=output_folder, pairs=pairs, balance_pairs=balance_pairs, **run_kw)
 
 
 def run_device_pyramid(hic_folder, reference_fa, output_folder=None, **run_kw):
