@@ -1,27 +1,31 @@
 """ctypes binding of libinstagraal_hip.so (the C ABI of include/instagraal_hip.h).
 
+``lib()`` gives every entry point the ``restype`` / ``argtypes`` the header declares (``abi.py``), so the calls below pass plain Python
+values, arrays by ``_p(...)`` and outputs by ``byref``; an argument of the wrong C type raises ``ctypes.ArgumentError``.
+
 There is no CPU fallback: if the shared library or a HIP device is missing, every entry
 point raises.  The library is built in-tree by ``__graft_entry__.build()`` / ``build_lib()``.
 """
 from __future__ import annotations
 
 import ctypes as C
+import glob
 import os
 import subprocess
 
 import numpy as np
+
+from . import abi
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 LIB_PATH = os.path.join(HERE, "libinstagraal_hip.so")
 SRC = os.path.join(HERE, "csrc", "ig_hip.hip")
 SRC_HOST = os.path.join(HERE, "csrc", "ig_draw.cpp")  # host-only part: the candidate draw
-DEPS = [SRC, SRC_HOST] + [os.path.join(HERE, "csrc", f) for f in ("ig_ops.cuh", "ig_common.cuh", "ig_model.cuh", "ig_kernels_setup.cuh",
-                                                          "ig_kernels_score.cuh", "ig_kernels_screen.cuh", "ig_kernels_commit.cuh",
-                                                          "ig_kernels_nuis.cuh", "ig_kernels_wave.cuh", "ig_kernels_genome.cuh", "ig_kernels_rows.cuh", "ig_kernels_map.cuh", "ig_kernels_law.cuh", "ig_kernels_junc.cuh", "ig_kernels_lift.cuh", "ig_kernels_join.cuh", "ig_kernels_emap.cuh", "ig_kernels_place.cuh", "ig_kernels_orient.cuh", "ig_kernels_bal.cuh", "ig_kernels_gap.cuh", "ig_kernels_zoom.cuh", "ig_kernels_segplace.cuh", "ig_kernels_edit.cuh", "ig_kernels_cutjoin.cuh", "ig_kernels_pairs.cuh", "ig_kernels_pre.cuh", "ig_kernels_seq.cuh", "ig_kernels_pyr.cuh", "ig_kernels_balsnap.cuh", "ig_host_core.inc", "ig_host_upload.inc", "ig_host_genome.inc", "ig_host_rows.inc",
-                                                          "ig_host_map.inc", "ig_host_law.inc", "ig_host_junc.inc", "ig_host_lift.inc", "ig_host_join.inc", "ig_host_emap.inc", "ig_host_place.inc", "ig_host_orient.inc", "ig_host_bal.inc", "ig_host_gap.inc", "ig_host_zoom.inc", "ig_host_segplace.inc", "ig_host_edit.inc", "ig_host_cutjoin.inc", "ig_host_pairs.inc", "ig_host_pre.inc", "ig_host_seq.inc", "ig_host_pyr.inc", "ig_host_balsnap.inc",
-                                                          "ig_host_batch.inc", "ig_host_nuis.inc", "ig_host_debug.inc")] + \
-       [os.path.join(ROOT, "include", f) for f in ("ig_detmath.h", "ig_detmath_tables.h", "instagraal_hip.h")]
+HEADER = os.path.join(ROOT, "include", "instagraal_hip.h")  # the C ABI: abi.declarations reads the signatures out of it
+# what a rebuild depends on: the two sources, every kernel file and host part beside them, the headers
+DEPS = [SRC, SRC_HOST] + sorted(glob.glob(os.path.join(HERE, "csrc", "*.cuh")) + glob.glob(os.path.join(HERE, "csrc", "*.inc"))) + \
+       [os.path.join(ROOT, "include", f) for f in ("ig_detmath.h", "ig_detmath_tables.h")] + [HEADER]
 
 N_TMP_STRUCT = 24
 ASSEMBLY_CONTACTS_PASSES = ("count", "scan", "scatter", "sort_short", "sort_lds", "sort_long", "reduce")  # ig_debug_assembly_contacts_time
@@ -85,6 +89,8 @@ def lib():
         if not os.path.exists(LIB_PATH):
             raise RuntimeError("libinstagraal_hip.so is missing (%s): run __graft_entry__.build(); "
                                "the MI355X path has no CPU fallback" % LIB_PATH)
+        if not os.path.exists(HEADER):
+            raise RuntimeError("instagraal_hip.h is missing (%s): the library's signatures are read from it" % HEADER)
         # One HIP runtime per process: PyTorch-ROCm bundles its own libamdhip64 (same SONAME, requested under an
         # unversioned name), so if our library pulled in /opt/rocm's copy first a later `import torch` would bring a
         # second runtime that sees no devices.  Loading torch first makes our NEEDED entry resolve to its copy.
@@ -103,12 +109,10 @@ def lib():
 
                 warnings.warn("IG_HIP_LIB=%s is ignored without IG_DEBUG_TUNING=1: loading the product library %s"
                               % (os.environ["IG_HIP_LIB"], LIB_PATH), RuntimeWarning, stacklevel=2)
-        _lib = C.CDLL(path)
-        _lib.ig_last_error.restype = C.c_char_p
-        _lib.ig_partials_count.restype = C.c_int64
-        _lib.ig_partials_device_ptr.restype = C.c_void_p
-        _lib.ig_partials_count.argtypes = [C.c_void_p]
-        _lib.ig_partials_device_ptr.argtypes = [C.c_void_p]
+        loaded = C.CDLL(path)
+        with open(HEADER) as header:
+            abi.apply(loaded, header.read())  # restype and argtypes of every entry point, as the header declares it
+        _lib = loaded
     return _lib
 
 
@@ -125,7 +129,7 @@ def model_values_host(params, s):
         raise HipError("model_values_host: eight parameters in the order of ig_params (got %d)" % p.size)
     sep = np.ascontiguousarray(s, np.float32)
     e_q, l_q = np.zeros(sep.shape, np.int64), np.zeros(sep.shape, np.int64)
-    _ck(lib().ig_model_values_host(_p(p), _p(sep), C.c_int64(sep.size), _p(e_q), _p(l_q)))
+    _ck(lib().ig_model_values_host(_p(p), _p(sep), sep.size, _p(e_q), _p(l_q)))
     return e_q, l_q
 
 
@@ -144,7 +148,7 @@ def contact_terms_host(params, mean_kb, s, d, trans, count):
     sep = np.ascontiguousarray(s, np.float32)
     dd, tt, cc = (np.ascontiguousarray(np.broadcast_to(np.asarray(a), sep.shape), np.int32) for a in (d, trans, count))
     q = np.zeros(sep.shape, np.int64)
-    _ck(lib().ig_contact_terms_host(_p(p), C.c_float(float(np.float32(mean_kb))), _p(sep), _p(dd), _p(tt), _p(cc), C.c_int64(sep.size), _p(q)))
+    _ck(lib().ig_contact_terms_host(_p(p), float(np.float32(mean_kb)), _p(sep), _p(dd), _p(tt), _p(cc), sep.size, _p(q)))
     return q
 
 
@@ -155,7 +159,7 @@ def zero_terms_host(params, mean_kb, pos, length):
     pp = np.ascontiguousarray(pos, np.int32)
     ll = np.ascontiguousarray(np.broadcast_to(np.asarray(length), pp.shape), np.int32)
     q = np.zeros(pp.shape, np.int64)
-    _ck(lib().ig_zero_terms_host(_p(p), C.c_float(float(np.float32(mean_kb))), _p(pp), _p(ll), C.c_int64(pp.size), _p(q)))
+    _ck(lib().ig_zero_terms_host(_p(p), float(np.float32(mean_kb)), _p(pp), _p(ll), pp.size, _p(q)))
     return q
 
 
@@ -214,8 +218,7 @@ class Neighbours:
         p = np.ascontiguousarray(pk, np.float32)
         b = np.ascontiguousarray(list(blacklisted), np.int32)
         assert ip.size == n_frags + 1 and x.size == p.size == ip[-1]
-        _ck(lib().ig_neighbours_create(_p(ip), _p(x), _p(p), C.c_int32(int(n_frags)), _p(b) if b.size else C.c_void_p(0),
-                                       C.c_int32(b.size), C.byref(self._h)))
+        _ck(lib().ig_neighbours_create(_p(ip), _p(x), _p(p), int(n_frags), _p(b) if b.size else None, b.size, C.byref(self._h)))
         self.n_frags = int(n_frags)
 
     def __del__(self):
@@ -277,13 +280,12 @@ class Neighbours:
         addr = self.numpy_mt_address()
         if addr:  # on numpy's state in place
             with self.numpy_mt_lock():
-                rc = lib().ig_neighbours_draw(self._h, C.c_void_p(addr), C.c_void_p(addr + 624 * 4), _p(f), C.c_int32(f.size),
-                                              C.c_int32(int(n_neighbours)), _p(out))
+                rc = lib().ig_neighbours_draw(self._h, addr, addr + 624 * 4, _p(f), f.size, int(n_neighbours), _p(out))
             _ck(rc)
             return out
         key, pos, rest = self.take_numpy_state()
         cpos = C.c_int32(pos)
-        rc = lib().ig_neighbours_draw(self._h, _p(key), C.byref(cpos), _p(f), C.c_int32(f.size), C.c_int32(int(n_neighbours)), _p(out))
+        rc = lib().ig_neighbours_draw(self._h, _p(key), C.byref(cpos), _p(f), f.size, int(n_neighbours), _p(out))
         self.put_numpy_state(key, cpos.value, rest)
         _ck(rc)
         return out
@@ -301,8 +303,8 @@ def _neighbours_draw_nuisance(self, frags, n_neighbours, skip_normal_3=False):
     u = np.zeros(n, np.float64)
     key, pos, rest = self.take_numpy_state()
     cpos, hg, gz = C.c_int32(pos), C.c_int32(int(rest[0])), C.c_double(float(rest[1]))
-    rc = lib().ig_neighbours_draw_nuisance(self._h, _p(key), C.byref(cpos), C.byref(hg), C.byref(gz), _p(f), C.c_int32(n),
-                                           C.c_int32(int(n_neighbours)), C.c_int32(int(bool(skip_normal_3))), _p(cands), _p(idm), _p(g), _p(u))
+    rc = lib().ig_neighbours_draw_nuisance(self._h, _p(key), C.byref(cpos), C.byref(hg), C.byref(gz), _p(f), n,
+                                           int(n_neighbours), int(bool(skip_normal_3)), _p(cands), _p(idm), _p(g), _p(u))
     self.put_numpy_state(key, cpos.value, (hg.value, gz.value))
     _ck(rc)
     return cands, idm, g, u
@@ -313,35 +315,35 @@ Neighbours.draw_nuisance = _neighbours_draw_nuisance
 
 def set_batch_width(w):
     """moves scored per launch by ``Context.step_batch`` (1 = one move at a time; results do not depend on it)"""
-    _ck(lib().ig_set_batch_width(C.c_int(int(w))))
+    _ck(lib().ig_set_batch_width(int(w)))
 
 
 def set_window(w):
     """slots of the window of scored moves ig_step_batch keeps from launch to launch (0: off -- the batches of rounds 1 - 4)"""
-    _ck(lib().ig_set_window(C.c_int(int(w))))
+    _ck(lib().ig_set_window(int(w)))
 
 
 def set_nuis_width(w):
     """moves scored ahead per launch by the nuisance-on loop (``Context.nuis_step_begin``); 0 = follow the run lengths"""
-    _ck(lib().ig_set_nuis_width(C.c_int(int(w))))
+    _ck(lib().ig_set_nuis_width(int(w)))
 
 
 def set_nuis_screen(on):
     """the Metropolis test of the nuisance steps from the screened pass where it decides (default), or always from the exact one"""
-    _ck(lib().ig_set_nuis_screen(C.c_int(int(on))))
+    _ck(lib().ig_set_nuis_screen(int(on)))
 
 
 def set_nuis_hist(on):
     """the screened pass starts from the histogram of the cis contacts' distances where that pays (1, default: a cost model decides),
     always (2), or never (0)"""
-    _ck(lib().ig_set_nuis_hist(C.c_int(int(on))))
+    _ck(lib().ig_set_nuis_hist(int(on)))
 
 
 def set_nuis_chain(on):
     """runs of (move, nuisance step) pairs decided on the device, as far as they need no host (default), or one pair per library call"""
     global _nuis_chain
     _nuis_chain = bool(on)
-    _ck(lib().ig_set_nuis_chain(C.c_int(int(on))))
+    _ck(lib().ig_set_nuis_chain(int(on)))
 
 
 _nuis_chain = None
@@ -361,7 +363,7 @@ CHAIN_REASONS = ("sets used up", "test", "conflict", "pending", "overflow", "no 
 def debug_set_zero_inject(every):
     """tests: the decide step treats every n-th move of a two-tier batch as one whose contenders hold a score of exactly 0.0
     (the move is scored again with every column exact); 0 = off"""
-    _ck(lib().ig_debug_set_zero_inject(C.c_int(int(every))))
+    _ck(lib().ig_debug_set_zero_inject(int(every)))
 
 
 ROUND_CENSUS = ("launches", "rounds", "committed", "full", "tail_full", "tail_short", "changed", "flags", "stop1_first", "stop1_mid",
@@ -371,13 +373,13 @@ ROUND_CLASSES = ROUND_CENSUS[3:14] + ROUND_CENSUS[15:]  # one of them per round
 
 def debug_set_round_census(on):
     """tests: the decide rounds (k_decide_commit_par) count how each round ended (``Context.debug_round_census``); off by default"""
-    _ck(lib().ig_debug_set_round_census(C.c_int(int(bool(on)))))
+    _ck(lib().ig_debug_set_round_census(int(bool(on))))
 
 
 def debug_set_full_hist(on):
     """from-scratch pass over all contacts: tiles of trans pairs only from their count histograms (default) or contact by
     contact -- same exact sums (tests)"""
-    _ck(lib().ig_debug_set_full_hist(C.c_int(int(on))))
+    _ck(lib().ig_debug_set_full_hist(int(on)))
 
 
 class Context:
@@ -385,7 +387,7 @@ class Context:
 
     def __init__(self, device_id=0):
         self._h = C.c_void_p()
-        _ck(lib().ig_create(C.c_int(device_id), C.byref(self._h)))
+        _ck(lib().ig_create(device_id, C.byref(self._h)))
         self.N = 0
         self.M = 0
 
@@ -403,8 +405,7 @@ class Context:
     # ---- upload
     def upload_contacts(self, row, col, cnt, M, rank=0, world=1):
         row, col, cnt = as_int32_exact(row, "row"), as_int32_exact(col, "col"), as_int32_exact(cnt, "cnt")
-        _ck(lib().ig_upload_contacts(self._h, _p(row), _p(col), _p(cnt), C.c_int64(row.size), C.c_int32(M), C.c_int32(rank),
-                                     C.c_int32(world)))
+        _ck(lib().ig_upload_contacts(self._h, _p(row), _p(col), _p(cnt), row.size, M, rank, world))
         self.M = int(M)
 
     def upload_subfrag_table(self, table):
@@ -413,13 +414,13 @@ class Context:
         if t.dtype.names:
             t = np.stack([t["x"], t["y"], t["z"], t["w"]], axis=1)
         t = np.ascontiguousarray(t, np.float32)
-        _ck(lib().ig_upload_subfrag_table(self._h, _p(t), C.c_int32(t.shape[0])))
+        _ck(lib().ig_upload_subfrag_table(self._h, _p(t), t.shape[0]))
         self.M = int(t.shape[0])
 
     def upload_state(self, soa17):
         s = np.ascontiguousarray(soa17, np.int32)
         assert s.ndim == 2 and s.shape[0] == 17
-        _ck(lib().ig_upload_state(self._h, _p(s), C.c_int32(s.shape[1])))
+        _ck(lib().ig_upload_state(self._h, _p(s), s.shape[1]))
         self.N = int(s.shape[1])
 
     def download_state(self):
@@ -430,43 +431,43 @@ class Context:
     def set_params(self, p8, mean_subfrag_kb, which=0):
         p = np.ascontiguousarray(p8, np.float32)
         assert p.size == 8
-        _ck(lib().ig_set_params(self._h, _p(p), C.c_float(float(mean_subfrag_kb)), C.c_int(which)))
+        _ck(lib().ig_set_params(self._h, _p(p), float(mean_subfrag_kb), which))
 
     def set_insert_config(self, list_bounds6, max_bounds_insert):
         b = np.ascontiguousarray(list_bounds6, np.int32)
         assert b.size == 6
-        _ck(lib().ig_set_insert_config(self._h, _p(b), C.c_int32(int(max_bounds_insert))))
+        _ck(lib().ig_set_insert_config(self._h, _p(b), int(max_bounds_insert)))
 
     def set_initial_genome(self, init_prev, init_next, orientable, blacklisted=()):
         ip = np.ascontiguousarray(init_prev, np.int32)
         inn = np.ascontiguousarray(init_next, np.int32)
         o = np.ascontiguousarray(orientable, np.int32)
         b = np.ascontiguousarray(list(blacklisted), np.int32)
-        _ck(lib().ig_set_initial_genome(self._h, _p(ip), _p(inn), _p(o), _p(b) if b.size else C.c_void_p(0), C.c_int32(b.size)))
+        _ck(lib().ig_set_initial_genome(self._h, _p(ip), _p(inn), _p(o), _p(b) if b.size else None, b.size))
 
     # ---- likelihood
     def full_likelihood(self, which=0, use_prev_tables=False):
         nz = C.c_double()
         z = C.c_double()
         limbs = np.zeros(5, np.int64)
-        _ck(lib().ig_full_likelihood(self._h, C.c_int(which), C.c_int(int(use_prev_tables)), C.byref(nz), C.byref(z), _p(limbs)))
+        _ck(lib().ig_full_likelihood(self._h, which, int(use_prev_tables), C.byref(nz), C.byref(z), _p(limbs)))
         return nz.value, z.value, limbs
 
     # ---- moves
     def score_move(self, frag_a, cands):
         c = np.ascontiguousarray(cands, np.int32)
         out = np.zeros(c.size * N_TMP_STRUCT, np.float64)
-        _ck(lib().ig_score_move(self._h, C.c_int32(int(frag_a)), _p(c), C.c_int32(c.size), _p(out)))
+        _ck(lib().ig_score_move(self._h, int(frag_a), _p(c), c.size, _p(out)))
         return out
 
     def apply(self, frag_a, frag_b, op):
-        _ck(lib().ig_apply(self._h, C.c_int32(int(frag_a)), C.c_int32(int(frag_b)), C.c_int32(int(op))))
+        _ck(lib().ig_apply(self._h, int(frag_a), int(frag_b), int(op)))
 
     def step(self, frag_a, cands, want_scores=True):
         c = np.ascontiguousarray(cands, np.int32)
         res = MoveResult()
         sc = np.zeros(c.size * N_TMP_STRUCT, np.float64) if want_scores else None
-        _ck(lib().ig_step(self._h, C.c_int32(int(frag_a)), _p(c), C.c_int32(c.size), C.byref(res), _p(sc)))
+        _ck(lib().ig_step(self._h, int(frag_a), _p(c), c.size, C.byref(res), _p(sc)))
         return res, sc
 
     def step_draw(self, neighbours, frag_a, n_neighbours, cands=None, want_scores=True):
@@ -474,9 +475,6 @@ class Context:
         place (``cands`` given: the caller's list), lists and results through mapped host memory, the move decided and applied as a
         batch of one -> (MoveResult, scores [C x 24], candidate list).  ``want_scores=False`` -> scores None, and the library is free to
         score the move in two tiers (the exact kernel for the columns that can still win only)"""
-        fn = lib().ig_step_draw
-        if fn.argtypes is None:
-            fn.argtypes = [C.c_void_p] * 4 + [C.c_int32, C.c_int32] + [C.c_void_p] * 4
         io = self.__dict__.get("_step_io")
         if io is None:
             sc = np.zeros(MAX_CANDIDATES * N_TMP_STRUCT, np.float64)
@@ -491,15 +489,15 @@ class Context:
                 r, s2 = self.step(int(frag_a), lst, want_scores=want_scores)
                 return r, s2, lst
             with Neighbours.numpy_mt_lock():
-                rc = fn(self._h, neighbours._h, addr, addr + 624 * 4, int(frag_a), int(n_neighbours), cbuf, C.byref(ncand), C.byref(res),
-                        sc_addr if want_scores else None)
+                rc = lib().ig_step_draw(self._h, neighbours._h, addr, addr + 624 * 4, int(frag_a), int(n_neighbours), cbuf, C.byref(ncand),
+                                            C.byref(res), sc_addr if want_scores else None)
         else:
             n = len(cands)
             if n > MAX_CANDIDATES:
                 raise HipError("a move needs 1..%d candidates (got %d)" % (MAX_CANDIDATES, n))
             cbuf[:n] = [int(x) for x in cands]
             ncand.value = n
-            rc = fn(self._h, None, None, None, int(frag_a), 0, cbuf, C.byref(ncand), C.byref(res), sc_addr if want_scores else None)
+            rc = lib().ig_step_draw(self._h, None, None, None, int(frag_a), 0, cbuf, C.byref(ncand), C.byref(res), sc_addr if want_scores else None)
         if rc != 0:
             _ck(rc)
         n = ncand.value
@@ -517,7 +515,7 @@ class Context:
         c = np.ascontiguousarray(cands, np.int32)
         assert c.ndim == 2 and c.shape[0] == f.size
         res = np.zeros(f.size, MOVE_RESULT_DTYPE)
-        _ck(lib().ig_step_batch(self._h, C.c_int32(f.size), _p(f), _p(c), C.c_int32(c.shape[1]), _p(res)))
+        _ck(lib().ig_step_batch(self._h, f.size, _p(f), _p(c), c.shape[1], _p(res)))
         return res
 
     def step_batch_draw(self, neighbours, frags, n_neighbours):
@@ -529,14 +527,12 @@ class Context:
         addr = Neighbours.numpy_mt_address()
         if addr:  # on numpy's generator state in place (this thread waits inside the call while the library's thread draws)
             with Neighbours.numpy_mt_lock():
-                rc = lib().ig_step_batch_draw(self._h, neighbours._h, C.c_void_p(addr), C.c_void_p(addr + 624 * 4), C.c_int32(f.size), _p(f),
-                                              C.c_int32(int(n_neighbours)), _p(cands), _p(res))
+                rc = lib().ig_step_batch_draw(self._h, neighbours._h, addr, addr + 624 * 4, f.size, _p(f), int(n_neighbours), _p(cands), _p(res))
             _ck(rc)
             return res, cands
         key, pos, rest = Neighbours.take_numpy_state()
         cpos = C.c_int32(pos)
-        rc = lib().ig_step_batch_draw(self._h, neighbours._h, _p(key), C.byref(cpos), C.c_int32(f.size), _p(f),
-                                      C.c_int32(int(n_neighbours)), _p(cands), _p(res))
+        rc = lib().ig_step_batch_draw(self._h, neighbours._h, _p(key), C.byref(cpos), f.size, _p(f), int(n_neighbours), _p(cands), _p(res))
         Neighbours.put_numpy_state(key, cpos.value, rest)
         _ck(rc)
         return res, cands
@@ -545,7 +541,7 @@ class Context:
     def nuis_begin(self, frag_a, cands, p_test8, mean_subfrag_kb):
         c = np.ascontiguousarray(cands, np.int32)
         p = np.ascontiguousarray(p_test8, np.float32)
-        _ck(lib().ig_nuis_begin(self._h, C.c_int32(int(frag_a)), _p(c), C.c_int32(c.size), _p(p), C.c_float(float(mean_subfrag_kb))))
+        _ck(lib().ig_nuis_begin(self._h, int(frag_a), _p(c), c.size, _p(p), float(mean_subfrag_kb)))
 
     def links_inverse(self):
         return bool(lib().ig_links_inverse(self._h))
@@ -555,11 +551,11 @@ class Context:
         f = np.ascontiguousarray(frags, np.int32)
         c = np.ascontiguousarray(cands, np.int32)
         assert c.ndim == 2 and c.shape[0] == f.size
-        _ck(lib().ig_nuis_run_begin(self._h, C.c_int32(f.size), _p(f), _p(c), C.c_int32(c.shape[1])))
+        _ck(lib().ig_nuis_run_begin(self._h, f.size, _p(f), _p(c), c.shape[1]))
 
     def nuis_step_begin(self, move, p_test8, mean_subfrag_kb):
         p = np.ascontiguousarray(p_test8, np.float32)
-        _ck(lib().ig_nuis_step_begin(self._h, C.c_int32(int(move)), _p(p), C.c_float(float(mean_subfrag_kb))))
+        _ck(lib().ig_nuis_step_begin(self._h, int(move), _p(p), float(mean_subfrag_kb)))
 
     def nuis_step_next(self, temperature, u, p_next_rejected, p_next_accepted, mean_subfrag_kb, has_next):
         """end of the step in flight + acceptance test + promotion + begin of the next step (ig_nuis_step_next)
@@ -569,9 +565,8 @@ class Context:
         nz, z, acc = C.c_double(), C.c_double(), C.c_int32()
         pr = None if p_next_rejected is None else np.ascontiguousarray(p_next_rejected, np.float32)
         pa = None if p_next_accepted is None else np.ascontiguousarray(p_next_accepted, np.float32)
-        _ck(lib().ig_nuis_step_next(self._h, C.c_double(float(temperature)), C.c_double(float(u)), _p(pr), _p(pa),
-                                    C.c_float(float(mean_subfrag_kb)), C.c_int32(int(has_next)), C.byref(res), C.byref(nz), C.byref(z),
-                                    C.byref(acc)))
+        _ck(lib().ig_nuis_step_next(self._h, float(temperature), float(u), _p(pr), _p(pa),
+                                    float(mean_subfrag_kb), int(has_next), C.byref(res), C.byref(nz), C.byref(z), C.byref(acc)))
         return res, nz.value, z.value, acc.value
 
     def nuis_chain_begin(self, move, p_tests, u, temperature, mean_subfrag_kb):
@@ -581,7 +576,7 @@ class Context:
         uu = np.ascontiguousarray(u, np.float64)
         tt = np.ascontiguousarray(temperature, np.float64)
         assert p.ndim == 2 and p.shape[1] == 8 and uu.size == p.shape[0] == tt.size
-        _ck(lib().ig_nuis_chain_begin(self._h, C.c_int32(int(move)), C.c_int32(p.shape[0]), _p(p), _p(uu), _p(tt), C.c_float(float(mean_subfrag_kb))))
+        _ck(lib().ig_nuis_chain_begin(self._h, int(move), p.shape[0], _p(p), _p(uu), _p(tt), float(mean_subfrag_kb)))
 
     def nuis_chain_done(self):
         return bool(lib().ig_nuis_chain_done(self._h))
@@ -606,7 +601,7 @@ class Context:
     def nuis_end(self):
         res = MoveResult()
         nz, z = C.c_double(), C.c_double()
-        _ck(lib().ig_nuis_end(self._h, C.byref(res), C.byref(nz), C.byref(z), C.c_void_p(0)))
+        _ck(lib().ig_nuis_end(self._h, C.byref(res), C.byref(nz), C.byref(z), None))
         return res, nz.value, z.value
 
     def nuis_accept(self):
@@ -614,16 +609,16 @@ class Context:
 
     # ---- speculative batches in steps (slots of a batch split over several GPUs)
     def batch_max_width(self, max_c=5):
-        return int(lib().ig_batch_max_width(self._h, C.c_int32(int(max_c))))
+        return int(lib().ig_batch_max_width(self._h, int(max_c)))
 
     def batch_upload(self, frags, cands, max_w):
         f = np.ascontiguousarray(frags, np.int32)
         c = np.ascontiguousarray(cands, np.int32)
         assert c.ndim == 2 and c.shape[0] == f.size
-        _ck(lib().ig_batch_upload(self._h, C.c_int32(f.size), _p(f), _p(c), C.c_int32(c.shape[1]), C.c_int32(int(max_w))))
+        _ck(lib().ig_batch_upload(self._h, f.size, _p(f), _p(c), c.shape[1], int(max_w)))
 
     def batch_score(self, move0, w, slot_begin, slot_end):
-        _ck(lib().ig_batch_score(self._h, C.c_int32(int(move0)), C.c_int32(int(w)), C.c_int32(int(slot_begin)), C.c_int32(int(slot_end))))
+        _ck(lib().ig_batch_score(self._h, int(move0), int(w), int(slot_begin), int(slot_end)))
 
     def batch_records(self):
         """-> (device pointer, bytes per slot) of the slot-major score records: slot w lives at pointer + w * bytes"""
@@ -634,30 +629,30 @@ class Context:
 
     def batch_commit(self, move0, w):
         n = C.c_int32()
-        _ck(lib().ig_batch_commit(self._h, C.c_int32(int(move0)), C.c_int32(int(w)), C.byref(n)))
+        _ck(lib().ig_batch_commit(self._h, int(move0), int(w), C.byref(n)))
         return n.value
 
     def batch_results(self, n_moves):
         res = np.zeros(int(n_moves), MOVE_RESULT_DTYPE)
-        _ck(lib().ig_batch_results(self._h, C.c_int32(int(n_moves)), _p(res)))
+        _ck(lib().ig_batch_results(self._h, int(n_moves), _p(res)))
         return res
 
     def debug_tile_trace(self):
         """one from-scratch pass -> (n, 4) int64: start, end (100 MHz clock), XCC_ID << 32 | HW_ID, contacts of every workgroup"""
         n = C.c_int64()
-        _ck(lib().ig_debug_tile_trace(self._h, C.c_void_p(0), C.c_int64(0), C.byref(n)))
+        _ck(lib().ig_debug_tile_trace(self._h, None, 0, C.byref(n)))
         out = np.zeros((n.value, 4), np.int64)
-        _ck(lib().ig_debug_tile_trace(self._h, _p(out), C.c_int64(n.value), C.byref(n)))
+        _ck(lib().ig_debug_tile_trace(self._h, _p(out), n.value, C.byref(n)))
         return out
 
     def debug_diff_trace(self, p_test8, mean_subfrag_kb):
         """one screened nuisance pass under p_test -> ((n, 8) int64 per-workgroup clocks, the pass's 8 output words)"""
         p = np.ascontiguousarray(p_test8, np.float32)
         n = C.c_int64()
-        _ck(lib().ig_debug_diff_trace(self._h, _p(p), C.c_float(float(mean_subfrag_kb)), C.c_void_p(0), C.c_int64(0), C.byref(n), C.c_void_p(0)))
+        _ck(lib().ig_debug_diff_trace(self._h, _p(p), float(mean_subfrag_kb), None, 0, C.byref(n), None))
         out = np.zeros((n.value, 8), np.int64)
         sums = np.zeros(8, np.int64)
-        _ck(lib().ig_debug_diff_trace(self._h, _p(p), C.c_float(float(mean_subfrag_kb)), _p(out), C.c_int64(n.value), C.byref(n), _p(sums)))
+        _ck(lib().ig_debug_diff_trace(self._h, _p(p), float(mean_subfrag_kb), _p(out), n.value, C.byref(n), _p(sums)))
         return out, sums
 
     def debug_nuis_wait(self):
@@ -695,7 +690,7 @@ class Context:
         """how the decide rounds of this handle ended since the census was switched on (``debug_set_round_census``) -> dict over
         ROUND_CENSUS; counts depend on timing, the identities between them do not"""
         o = np.zeros(16, np.int32)
-        _ck(lib().ig_debug_round_census(self._h, _p(o), C.c_int32(int(bool(clear)))))
+        _ck(lib().ig_debug_round_census(self._h, _p(o), int(bool(clear))))
         return dict(zip(ROUND_CENSUS, (int(x) for x in o)))
 
     def debug_pool_retries(self):
@@ -708,7 +703,7 @@ class Context:
         """set the bytes the per-window arrays of this handle's move buffers may take (<= 0: the default, 64e9) and size them again ->
         the move slots they hold now (0: no move buffers yet)"""
         n = C.c_int32()
-        _ck(lib().ig_debug_window_budget(self._h, C.c_double(float(nbytes)), C.byref(n)))
+        _ck(lib().ig_debug_window_budget(self._h, float(nbytes), C.byref(n)))
         return int(n.value)
 
     def debug_nuis_hist_check(self):
@@ -752,7 +747,7 @@ class Context:
             cap = max(binning(self.contact_map_order().size, max_side)[1], 1)
         img = np.empty(cap * cap, np.int64)
         side, b = C.c_int32(), C.c_int32()
-        _ck(lib().ig_contact_map(self._h, C.c_int32(max_side), _p(img), C.c_int64(img.size), C.byref(side), C.byref(b)))
+        _ck(lib().ig_contact_map(self._h, max_side, _p(img), img.size, C.byref(side), C.byref(b)))
         n = side.value
         return img[:n * n].reshape(n, n).copy(), b.value
 
@@ -760,8 +755,7 @@ class Context:
         """the map's pass n times with hipEvents around each -> (milliseconds [n], sum of the last image)"""
         ms = np.zeros(int(n), np.float32)
         tot = C.c_int64()
-        _ck(lib().ig_debug_contact_map_time(self._h, C.c_int32(int(max_side)), C.c_int32(int(bool(combine))), C.c_int32(int(n)), _p(ms),
-                                            C.byref(tot)))
+        _ck(lib().ig_debug_contact_map_time(self._h, int(max_side), int(bool(combine)), int(n), _p(ms), C.byref(tot)))
         return ms, int(tot.value)
 
     # ---- the distance law of the current genome (the rule: distance_law.py)
@@ -775,7 +769,7 @@ class Context:
         obs = np.zeros(nb, np.int64)
         prs = np.zeros(nb, np.int64) if pairs else None
         sc = np.zeros(8, np.int64)
-        _ck(lib().ig_distance_law(self._h, _p(e), C.c_int32(int(e.size)), _p(obs), _p(prs), _p(sc)))
+        _ck(lib().ig_distance_law(self._h, _p(e), int(e.size), _p(obs), _p(prs), _p(sc)))
         out = dict(edges=e, observed=obs, pairs=prs)
         out.update((k, int(v)) for k, v in zip(SCALARS, sc))
         return out
@@ -787,8 +781,7 @@ class Context:
         ms_o = np.zeros(int(n), np.float32)
         ms_p = np.zeros(int(n), np.float32) if pairs else None
         ck = C.c_int64()
-        _ck(lib().ig_debug_distance_law_time(self._h, _p(e), C.c_int32(int(e.size)), C.c_int32(int(bool(privatised))), C.c_int32(int(n)),
-                                             _p(ms_o), _p(ms_p), C.byref(ck)))
+        _ck(lib().ig_debug_distance_law_time(self._h, _p(e), int(e.size), int(bool(privatised)), int(n), _p(ms_o), _p(ms_p), C.byref(ck)))
         return ms_o, ms_p, int(ck.value)
 
     # ---- the junction support profile of the current genome (the rule: junction_profile.py)
@@ -804,7 +797,7 @@ class Context:
         exq = np.zeros(cap, np.int64) if model else None
         sc = np.zeros(8, np.int64)
         n = C.c_int32()
-        _ck(lib().ig_junction_profile(self._h, C.c_int32(int(window)), _p(obs), _p(prs), _p(exq), C.c_int64(cap), C.byref(n), _p(sc)))
+        _ck(lib().ig_junction_profile(self._h, int(window), _p(obs), _p(prs), _p(exq), cap, C.byref(n), _p(sc)))
         T = n.value
         out = dict(window=int(window), n_placed=T, observed=obs[:T].copy(), pairs=prs[:T].copy() if model else None,
                    expected_q=exq[:T].copy() if model else None)
@@ -818,8 +811,7 @@ class Context:
         ms_m = np.zeros(int(n), np.float32) if model else None
         ms_s = np.zeros(int(n), np.float32) if scan else None
         ck = C.c_int64()
-        _ck(lib().ig_debug_junction_profile_time(self._h, C.c_int32(int(window)), C.c_int32(int(bool(combine))), C.c_int32(int(n)), _p(ms_o),
-                                                 _p(ms_m), _p(ms_s), C.byref(ck)))
+        _ck(lib().ig_debug_junction_profile_time(self._h, int(window), int(bool(combine)), int(n), _p(ms_o), _p(ms_m), _p(ms_s), C.byref(ck)))
         return ms_o, ms_m, ms_s, int(ck.value)
 
     # ---- the expected contact map of the current genome (the rule: expected_map.py)
@@ -838,7 +830,7 @@ class Context:
         img = np.empty((3, cap * cap), np.int64)
         side, b = C.c_int32(), C.c_int32()
         sc = np.zeros(8, np.int64)
-        _ck(lib().ig_expected_map(self._h, C.c_int32(max_side), _p(img[0]), _p(img[1]), _p(img[2]), C.c_int64(cap * cap), C.byref(side), C.byref(b), _p(sc)))
+        _ck(lib().ig_expected_map(self._h, max_side, _p(img[0]), _p(img[1]), _p(img[2]), cap * cap, C.byref(side), C.byref(b), _p(sc)))
         n = side.value
         out = dict(side=n, bin=b.value)
         out.update((k, img[i, :n * n].reshape(n, n).copy()) for i, k in enumerate(IMAGES))
@@ -849,7 +841,7 @@ class Context:
         """the form of this handle's builds: 0 / "default", 1 / "rows", 2 / "tiles", 3 / "tiles_plain" (``expected_map.FORMS``)"""
         from .expected_map import FORMS
 
-        _ck(lib().ig_debug_expected_map_form(self._h, C.c_int32(FORMS.index(form) if form in FORMS else int(form))))
+        _ck(lib().ig_debug_expected_map_form(self._h, FORMS.index(form) if form in FORMS else int(form)))
 
     def debug_expected_map_time(self, max_side, form=0, n=1):
         """the build under ``form`` n times with hipEvents around each -> (milliseconds [n], checksum of the last build)"""
@@ -857,8 +849,7 @@ class Context:
 
         ms = np.zeros(int(n), np.float32)
         ck = C.c_int64()
-        _ck(lib().ig_debug_expected_map_time(self._h, C.c_int32(int(max_side)), C.c_int32(FORMS.index(form) if form in FORMS else int(form)), C.c_int32(int(n)),
-                                             _p(ms), C.byref(ck)))
+        _ck(lib().ig_debug_expected_map_time(self._h, int(max_side), FORMS.index(form) if form in FORMS else int(form), int(n), _p(ms), C.byref(ck)))
         return ms, int(ck.value)
 
     # ---- the contacts in the coordinates of the current genome (the rule: assembly_contacts.py)
@@ -871,9 +862,9 @@ class Context:
         lv = LEVELS.index(level) if level in LEVELS else int(level)
         nu, ne = C.c_int64(), C.c_int64()
         sc = np.zeros(8, np.int64)
-        _ck(lib().ig_assembly_contacts_build(self._h, C.c_int32(lv), C.byref(nu), C.byref(ne), _p(sc)))
+        _ck(lib().ig_assembly_contacts_build(self._h, lv, C.byref(nu), C.byref(ne), _p(sc)))
         rowptr = np.zeros(nu.value + 1, np.int64)
-        _ck(lib().ig_assembly_contacts_rows(self._h, _p(rowptr), C.c_int64(rowptr.size)))
+        _ck(lib().ig_assembly_contacts_rows(self._h, _p(rowptr), rowptr.size))
         out = dict(level=LEVELS[lv], rowptr=rowptr, n_entries=int(ne.value))
         out.update((k, int(v)) for k, v in zip(SCALARS, sc))
         return out
@@ -882,7 +873,7 @@ class Context:
         """entries first .. first + n - 1 of the built result -> (col int32 [n], count int64 [n])"""
         n = int(n)
         col, cnt = np.zeros(max(n, 0), np.int32), np.zeros(max(n, 0), np.int64)
-        _ck(lib().ig_assembly_contacts_fetch(self._h, C.c_int64(int(first)), C.c_int64(n), _p(col), _p(cnt)))
+        _ck(lib().ig_assembly_contacts_fetch(self._h, int(first), n, _p(col), _p(cnt)))
         return col, cnt
 
     def assembly_contacts_release(self):
@@ -890,12 +881,12 @@ class Context:
 
     def debug_assembly_contacts_limits(self, short_max=0, lds_max=0):
         """the row lengths up to which the build sorts a row with a wave / with a workgroup in LDS (0: the default)"""
-        _ck(lib().ig_debug_assembly_contacts_limits(self._h, C.c_int32(int(short_max)), C.c_int32(int(lds_max))))
+        _ck(lib().ig_debug_assembly_contacts_limits(self._h, int(short_max), int(lds_max)))
 
     def debug_assembly_contacts_combine(self, combine=True):
         """the two passes over the contacts: one atomic per run of a wave's lanes with the same row (True, the default) or one per
         contact (False, the yardstick)"""
-        _ck(lib().ig_debug_assembly_contacts_combine(self._h, C.c_int32(int(bool(combine)))))
+        _ck(lib().ig_debug_assembly_contacts_combine(self._h, int(bool(combine))))
 
     def debug_assembly_contacts_forms(self):
         """the last build's work lists -> dict of (rows, entries) per sort form, the runs of the long rows, the longest long row"""
@@ -905,7 +896,7 @@ class Context:
 
     def debug_set_bin_active(self, bin_id, active):
         """tests: the ``activ`` flag of one bin on the device (a contig with an inactive bin is not placed in the genome order)"""
-        _ck(lib().ig_debug_set_bin_active(self._h, C.c_int32(int(bin_id)), C.c_int32(int(bool(active)))))
+        _ck(lib().ig_debug_set_bin_active(self._h, int(bin_id), int(bool(active))))
 
     def debug_assembly_contacts_time(self, level="sub", n=1):
         """the build n times with hipEvents around each pass -> (ms [n, 7]: ``ASSEMBLY_CONTACTS_PASSES``, checksum of the last result)"""
@@ -913,7 +904,7 @@ class Context:
 
         ms = np.zeros((int(n), len(ASSEMBLY_CONTACTS_PASSES)), np.float32)
         ck = C.c_int64()
-        _ck(lib().ig_debug_assembly_contacts_time(self._h, C.c_int32(LEVELS.index(level)), C.c_int32(int(n)), _p(ms), C.byref(ck)))
+        _ck(lib().ig_debug_assembly_contacts_time(self._h, LEVELS.index(level), int(n), _p(ms), C.byref(ck)))
         return ms, int(ck.value)
 
     # ---- fixed-resolution maps: a caller's unit per position, and a built level coarsened (the rule: zoom_levels.py)
@@ -934,7 +925,7 @@ class Context:
         from .assembly_contacts import SCALARS
 
         rowptr = np.zeros(int(n_units) + 1, np.int64)
-        _ck(lib().ig_assembly_contacts_rows(self._h, _p(rowptr), C.c_int64(rowptr.size)))
+        _ck(lib().ig_assembly_contacts_rows(self._h, _p(rowptr), rowptr.size))
         out = dict(rowptr=rowptr, n_entries=int(ne.value))
         out.update((k, int(v)) for k, v in zip(SCALARS, sc))
         return out
@@ -945,7 +936,7 @@ class Context:
         ``assembly_contacts.SCALARS``; a snapshot: the entries come through ``assembly_contacts_fetch``"""
         t = self._unit_table(unit, n_units, "assembly_contacts_units: unit table")
         ne, sc = C.c_int64(), np.zeros(8, np.int64)
-        _ck(lib().ig_assembly_contacts_build_units(self._h, _p(t), C.c_int64(t.size), C.c_int64(int(n_units)), C.byref(ne), _p(sc)))
+        _ck(lib().ig_assembly_contacts_build_units(self._h, _p(t), t.size, int(n_units), C.byref(ne), _p(sc)))
         return self._lift_result(n_units, ne, sc)
 
     def assembly_contacts_coarsen(self, coarse_of_unit, n_coarse):
@@ -954,7 +945,7 @@ class Context:
         refusal leaves nothing built"""
         t = self._unit_table(coarse_of_unit, n_coarse, "assembly_contacts_coarsen: coarse map")
         ne, sc = C.c_int64(), np.zeros(8, np.int64)
-        _ck(lib().ig_assembly_contacts_coarsen(self._h, _p(t), C.c_int64(t.size), C.c_int64(int(n_coarse)), C.byref(ne), _p(sc)))
+        _ck(lib().ig_assembly_contacts_coarsen(self._h, _p(t), t.size, int(n_coarse), C.byref(ne), _p(sc)))
         return self._lift_result(n_coarse, ne, sc)
 
     # ---- read pairs lifted onto the current genome (the rule: pairs_lift.py)
@@ -975,9 +966,8 @@ class Context:
         rev = np.ascontiguousarray(iv["reversed"] != 0, np.uint8)
         slen = np.ascontiguousarray(table["scaffold_len"], np.int64)
         unit = self._i32(table["bin_unit"], "pairs_begin: bin_unit")
-        _ck(lib().ig_pairs_begin(self._h, _p(rowptr), C.c_int32(rowptr.size - 1), _p(cols[0]), _p(cols[1]), _p(cols[2]), _p(cols[3]), _p(rev), _p(cols[4]),
-                                 C.c_int64(iv.size), _p(slen), C.c_int32(slen.size), _p(unit), C.c_int64(unit.size), C.c_int64(int(table["n_bin_units"])),
-                                 C.c_int64(int(reserve_pairs))))
+        _ck(lib().ig_pairs_begin(self._h, _p(rowptr), rowptr.size - 1, _p(cols[0]), _p(cols[1]), _p(cols[2]), _p(cols[3]), _p(rev), _p(cols[4]),
+                                 iv.size, _p(slen), slen.size, _p(unit), unit.size, int(table["n_bin_units"]), int(reserve_pairs)))
 
     def pairs_lift(self, c1, p1, c2, p2, strands=None, outputs=True):
         """one chunk: contig ids and 1-based positions (a position outside 1 .. 2^31 - 1 is covered by nothing), ``strands``: uint8 codes
@@ -1014,7 +1004,7 @@ class Context:
             for k in ("rev1", "rev2", "status"):
                 out[k] = np.zeros(n, np.uint8)
         o = lambda k: _p(out[k]) if outputs else None  # noqa: E731
-        _ck(lib().ig_pairs_lift(self._h, _p(a[0]), _p(a[1]), _p(a[2]), _p(a[3]), None if st is None else _p(st), C.c_int64(n), o("scaffold1"), o("pos1"), o("unit1"),
+        _ck(lib().ig_pairs_lift(self._h, _p(a[0]), _p(a[1]), _p(a[2]), _p(a[3]), None if st is None else _p(st), n, o("scaffold1"), o("pos1"), o("unit1"),
                                 o("rev1"), o("scaffold2"), o("pos2"), o("unit2"), o("rev2"), o("status"), _p(sc)))
         out.update((k, int(v)) for k, v in zip(SCALARS[:6], sc))
         return out
@@ -1026,7 +1016,7 @@ class Context:
         from .pairs_lift import UNIT_KINDS
 
         nu, ne, sc = C.c_int64(), C.c_int64(), np.zeros(8, np.int64)
-        _ck(lib().ig_pairs_pixels_build(self._h, C.c_int32(UNIT_KINDS.index(kind) if kind in UNIT_KINDS else int(kind)), C.c_int64(int(binsize)), C.byref(nu),
+        _ck(lib().ig_pairs_pixels_build(self._h, UNIT_KINDS.index(kind) if kind in UNIT_KINDS else int(kind), int(binsize), C.byref(nu),
                                         C.byref(ne), _p(sc)))
         return self._lift_result(nu.value, ne, sc)
 
@@ -1034,7 +1024,7 @@ class Context:
         """-> (counts int64 [4][n_edges - 1], dict of pairs_stored, pairs_cis, pairs_trans)"""
         e = np.ascontiguousarray(edges_bp, np.int64).ravel()
         counts, sc = np.zeros((4, max(e.size - 1, 1)), np.int64), np.zeros(8, np.int64)
-        _ck(lib().ig_pairs_law(self._h, _p(e), C.c_int32(e.size), C.c_int32(int(bool(flip_strands))), _p(counts), _p(sc)))
+        _ck(lib().ig_pairs_law(self._h, _p(e), e.size, int(bool(flip_strands)), _p(counts), _p(sc)))
         return counts, dict(pairs_stored=int(sc[0]), pairs_cis=int(sc[1]), pairs_trans=int(sc[2]))
 
     def pairs_clear(self):
@@ -1053,8 +1043,8 @@ class Context:
         e = np.ascontiguousarray(edges_bp, np.int64).ravel()
         ms = np.zeros((int(n), len(PAIRS_PASSES)), np.float32)
         ck = C.c_int64()
-        _ck(lib().ig_debug_pairs_time(self._h, _p(a[0]), _p(a[1]), _p(a[2]), _p(a[3]), None if st is None else _p(st), C.c_int64(a[0].size),
-                                      C.c_int32(UNIT_KINDS.index(kind)), C.c_int64(int(binsize)), _p(e), C.c_int32(e.size), C.c_int32(int(n)), _p(ms), C.byref(ck)))
+        _ck(lib().ig_debug_pairs_time(self._h, _p(a[0]), _p(a[1]), _p(a[2]), _p(a[3]), None if st is None else _p(st), a[0].size,
+                                      UNIT_KINDS.index(kind), int(binsize), _p(e), e.size, int(n), _p(ms), C.byref(ck)))
         return ms, int(ck.value)
 
     # ---- the input folder from a FASTA and read pairs (the rule: pre.py)
@@ -1065,7 +1055,7 @@ class Context:
         ln = self._i32(rec_len, "pre_begin: rec_len")
         if off.size != ln.size:
             raise HipError("pre_begin: one offset and one length per record")
-        _ck(lib().ig_pre_begin(self._h, _p(s), C.c_int64(s.size), _p(off), _p(ln), C.c_int32(ln.size)))
+        _ck(lib().ig_pre_begin(self._h, _p(s), s.size, _p(off), _p(ln), ln.size))
         self._pre_records = int(ln.size)
 
     def pre_digest(self, enzymes, piece=1 << 22, times=False):
@@ -1080,13 +1070,13 @@ class Context:
         masks = np.ascontiguousarray(np.stack([pre.site_masks(s) for s, _ in enzymes]), np.uint8)
         per, nf = np.zeros(R, np.int64), C.c_int64()
         ms = np.zeros(len(PRE_DIGEST_PASSES), np.float32) if times else None
-        _ck(lib().ig_pre_digest(self._h, C.c_int32(ln.size), _p(ln), _p(cut), _p(masks), _p(per), C.byref(nf), _p(ms)))
+        _ck(lib().ig_pre_digest(self._h, ln.size, _p(ln), _p(cut), _p(masks), _p(per), C.byref(nf), _p(ms)))
         n = int(nf.value)
         cols = [np.zeros(n, np.int32) for _ in range(4)]
         for a in range(0, n, int(piece)):
             m = min(int(piece), n - a)
             v = [x[a:a + m] for x in cols]
-            _ck(lib().ig_pre_fragments(self._h, C.c_int64(a), C.c_int64(m), _p(v[0]), _p(v[1]), _p(v[2]), _p(v[3])))
+            _ck(lib().ig_pre_fragments(self._h, a, m, _p(v[0]), _p(v[1]), _p(v[2]), _p(v[3])))
         out = dict(rec_first=np.concatenate(([0], np.cumsum(per))).astype(np.int64), frag_rec=cols[0], start=cols[1].astype(np.int64), end=cols[2].astype(np.int64),
                    gc_count=cols[3].astype(np.int64), n_frags=n, enzymes=enzymes)
         out["rec_len"] = np.zeros(R, np.int64)
@@ -1105,7 +1095,7 @@ class Context:
             raise HipError("pre_add_pairs: the four arrays of the pairs have one length")
         sc = np.zeros(8, np.int64)
         ms = np.zeros(1, np.float32) if times else None
-        _ck(lib().ig_pre_add_pairs(self._h, _p(a[0]), _p(a[1]), _p(a[2]), _p(a[3]), C.c_int64(a[0].size), _p(sc), _p(ms)))
+        _ck(lib().ig_pre_add_pairs(self._h, _p(a[0]), _p(a[1]), _p(a[2]), _p(a[3]), a[0].size, _p(sc), _p(ms)))
         out = {k: int(sc[i]) for i, k in enumerate(SCALARS[:5])}
         out["pairs_stored"] = int(sc[5])
         if times:
@@ -1121,11 +1111,11 @@ class Context:
         _ck(lib().ig_pre_pixels_build(self._h, C.byref(npx), _p(sc), _p(ms)))
         U, n = int(sc[6]), int(npx.value)
         rowptr, col, count = np.zeros(U + 1, np.int64), np.zeros(n, np.int32), np.zeros(n, np.int64)
-        _ck(lib().ig_pre_pixels_rows(self._h, _p(rowptr), C.c_int64(rowptr.size)))
+        _ck(lib().ig_pre_pixels_rows(self._h, _p(rowptr), rowptr.size))
         for a in range(0, n, int(piece)):
             m = min(int(piece), n - a)
             vc, vn = col[a:a + m], count[a:a + m]
-            _ck(lib().ig_pre_pixels_fetch(self._h, C.c_int64(a), C.c_int64(m), _p(vc), _p(vn)))
+            _ck(lib().ig_pre_pixels_fetch(self._h, a, m, _p(vc), _p(vn)))
         out = dict(rowptr=rowptr, col=col.astype(np.int64), count=count)
         out.update({k: int(sc[i]) for i, k in enumerate(SCALARS)})
         out.update(n_frags=U, pairs_stored=int(sc[7]))
@@ -1147,7 +1137,7 @@ class Context:
         ln = self._i32(rec_len, "seq_begin: rec_len")
         if off.size != ln.size:
             raise HipError("seq_begin: one offset and one length per record")
-        _ck(lib().ig_seq_begin(self._h, _p(s), C.c_int64(s.size), _p(off), _p(ln), C.c_int32(ln.size)))
+        _ck(lib().ig_seq_begin(self._h, _p(s), s.size, _p(off), _p(ln), ln.size))
         self._seq_records = int(ln.size)
 
     def seq_composition(self, times=None):
@@ -1169,23 +1159,23 @@ class Context:
             raise HipError("seq_plan: the tables of the output records have %d and %d + 1 entries" % (n_out, n_out))
         if len({b["src"].size, b["ori"].size, a["start"].size, a["length"].size, a["body"].size}) != 1:
             raise HipError("seq_plan: the five arrays of the pieces have one length")
-        _ck(lib().ig_seq_plan(self._h, C.c_int32(n_out), C.c_int32(int(plan["width"])), _p(a["rec_off"]), _p(b["hdr_len"]), _p(a["hdr_lit"]), _p(a["body_len"]),
-                              _p(a["piece_first"]), C.c_int64(b["src"].size), _p(b["src"]), _p(a["start"]), _p(a["length"]), _p(b["ori"]), _p(a["body"]), _p(lit),
-                              C.c_int64(lit.size)))
+        _ck(lib().ig_seq_plan(self._h, n_out, int(plan["width"]), _p(a["rec_off"]), _p(b["hdr_len"]), _p(a["hdr_lit"]), _p(a["body_len"]),
+                              _p(a["piece_first"]), b["src"].size, _p(b["src"]), _p(a["start"]), _p(a["length"]), _p(b["ori"]), _p(a["body"]), _p(lit),
+                              lit.size))
 
     def seq_window(self, first_byte, out, times=None):
         """fills ``out`` (a contiguous uint8 array) with the file's bytes from ``first_byte`` on; ``times``: ``stitch`` gets the kernel's ms"""
         if not (isinstance(out, np.ndarray) and out.dtype == np.uint8 and out.flags.c_contiguous and out.flags.writeable):
             raise HipError("seq_window: the window is a contiguous writeable uint8 array")
         ms = np.zeros(1, np.float32) if times is not None else None
-        _ck(lib().ig_seq_window(self._h, C.c_int64(int(first_byte)), C.c_int64(out.size), _p(out), _p(ms)))
+        _ck(lib().ig_seq_window(self._h, int(first_byte), out.size, _p(out), _p(ms)))
         if times is not None:
             times.setdefault("stitch", []).append(float(ms[0]))
 
     def seq_out_composition(self, n_out):
         """-> int64 [n_out, 8] of the stitched bodies, once every window has been fetched in file order"""
         counts = np.zeros((int(n_out), SEQ_CLASSES), np.int64)
-        _ck(lib().ig_seq_out_composition(self._h, _p(counts), C.c_int64(counts.size)))
+        _ck(lib().ig_seq_out_composition(self._h, _p(counts), counts.size))
         return counts
 
     def seq_end(self):
@@ -1199,7 +1189,7 @@ class Context:
         if not (a.size == b.size == cnt.size):
             raise HipError("pyr_begin: one a, one b and one count per entry")
         flag = C.c_int32()
-        _ck(lib().ig_pyr_begin(self._h, C.c_int32(int(n_frags)), _p(a), _p(b), _p(cnt), C.c_int64(a.size), C.byref(flag)))
+        _ck(lib().ig_pyr_begin(self._h, int(n_frags), _p(a), _p(b), _p(cnt), a.size, C.byref(flag)))
         self._pyr_frags = int(n_frags)
         return bool(flag.value)
 
@@ -1227,7 +1217,7 @@ class Context:
         t = self._i32(lut, "pyr_remap: lut")
         n, sc = C.c_int64(), np.zeros(8, np.int64)
         ms = np.zeros(len(ASSEMBLY_CONTACTS_PASSES), np.float32) if times is not None else None
-        _ck(lib().ig_pyr_remap(self._h, _p(t), C.c_int32(t.size), C.c_int32(int(n_new)), C.c_int32(1 if skip_first else 0), C.byref(n), _p(sc), _p(ms)))
+        _ck(lib().ig_pyr_remap(self._h, _p(t), t.size, int(n_new), 1 if skip_first else 0, C.byref(n), _p(sc), _p(ms)))
         self._pyr_frags = int(n_new)
         if times is not None:
             times.append(ms)
@@ -1237,13 +1227,13 @@ class Context:
         """the current level -> (data3: int32 [3, nnz] = rows, columns, counts; rowptr: int64 [n_frags + 1])"""
         U = getattr(self, "_pyr_frags", 0)
         rowptr = np.zeros(U + 1, np.int64)
-        _ck(lib().ig_pyr_rows(self._h, _p(rowptr), C.c_int64(rowptr.size)))
+        _ck(lib().ig_pyr_rows(self._h, _p(rowptr), rowptr.size))
         n = int(rowptr[-1])
         data3 = np.zeros((3, n), np.int32)
         for a in range(0, n, int(piece)):
             m = min(int(piece), n - a)
             v = [np.zeros(m, np.int32) for _ in range(3)]
-            _ck(lib().ig_pyr_fetch(self._h, C.c_int64(a), C.c_int64(m), _p(v[0]), _p(v[1]), _p(v[2])))
+            _ck(lib().ig_pyr_fetch(self._h, a, m, _p(v[0]), _p(v[1]), _p(v[2])))
             for k in range(3):
                 data3[k, a:a + m] = v[k]
         return data3, rowptr
@@ -1253,7 +1243,7 @@ class Context:
 
     def debug_pyr_piece(self, entries):
         """entries per upload piece of ``pyr_begin`` (0: the default)"""
-        _ck(lib().ig_debug_pyr_piece(self._h, C.c_int64(int(entries))))
+        _ck(lib().ig_debug_pyr_piece(self._h, int(entries)))
 
     def balance_build_units(self, unit, n_units, ignore_diags=2):
         """``balance_build("bin")`` with the caller's unit of every position -> the dict ``balance_build`` returns (level: "units")"""
@@ -1261,10 +1251,10 @@ class Context:
 
         t = self._unit_table(unit, n_units, "balance_build_units: unit table")
         ne, sc = C.c_int64(), np.zeros(8, np.int64)
-        _ck(lib().ig_balance_build_units(self._h, _p(t), C.c_int64(t.size), C.c_int64(int(n_units)), C.c_int32(int(ignore_diags)), C.byref(ne), _p(sc)))
+        _ck(lib().ig_balance_build_units(self._h, _p(t), t.size, int(n_units), int(ignore_diags), C.byref(ne), _p(sc)))
         U = int(n_units)
         rowptr, nnz, total = np.zeros(U + 1, np.int64), np.zeros(U, np.int64), np.zeros(U, np.int64)
-        _ck(lib().ig_balance_rows(self._h, _p(rowptr), _p(nnz), _p(total), C.c_int64(rowptr.size)))
+        _ck(lib().ig_balance_rows(self._h, _p(rowptr), _p(nnz), _p(total), rowptr.size))
         out = dict(level="units", rowptr=rowptr, nnz=nnz, total=total, n_entries=int(ne.value))
         out.update((k, int(v)) for k, v in zip(SCALARS, sc))
         return out
@@ -1278,10 +1268,10 @@ class Context:
         if rowptr.ndim != 1 or rowptr.size < 1 or col.shape != count.shape or col.ndim != 1 or m.shape != (rowptr.size - 1,) or col.size != int(rowptr[-1]):
             raise HipError("debug_zoom_coarsen: rowptr [U + 1], col and count [rowptr[U]], coarse_of_unit [U]")
         no, o = C.c_int64(), np.zeros(8, np.int64)
-        _ck(lib().ig_debug_zoom_coarsen(self._h, _p(rowptr), _p(col), _p(count), C.c_int64(rowptr.size - 1), _p(m), C.c_int64(int(n_coarse)), C.byref(no), _p(o)))
+        _ck(lib().ig_debug_zoom_coarsen(self._h, _p(rowptr), _p(col), _p(count), rowptr.size - 1, _p(m), int(n_coarse), C.byref(no), _p(o)))
         out = dict(n_out=int(no.value), rowptr=np.zeros(int(n_coarse) + 1, np.int64), col=np.zeros(no.value, np.int32), count=np.zeros(no.value, np.int64),
                    forms=dict(short=(int(o[0]), int(o[1])), lds=(int(o[2]), int(o[3])), long=(int(o[4]), int(o[5])), runs=int(o[6]), longest=int(o[7])))
-        _ck(lib().ig_debug_zoom_fetch(self._h, _p(out["rowptr"]), C.c_int64(out["rowptr"].size), _p(out["col"]), _p(out["count"]), C.c_int64(out["n_out"])))
+        _ck(lib().ig_debug_zoom_fetch(self._h, _p(out["rowptr"]), out["rowptr"].size, _p(out["col"]), _p(out["count"]), out["n_out"]))
         return out
 
     def debug_zoom_time(self, n=1, coarse_of_unit=None, n_coarse=None):
@@ -1290,8 +1280,7 @@ class Context:
         ms = np.zeros((int(n), len(ZOOM_PASSES)), np.float32)
         ck = C.c_int64()
         t = None if coarse_of_unit is None else self._unit_table(coarse_of_unit, n_coarse, "debug_zoom_time: coarse map")
-        _ck(lib().ig_debug_zoom_time(self._h, _p(t), C.c_int64(0 if t is None else t.size), C.c_int64(0 if t is None else int(n_coarse)), C.c_int32(int(n)), _p(ms),
-                                     C.byref(ck)))
+        _ck(lib().ig_debug_zoom_time(self._h, _p(t), 0 if t is None else t.size, 0 if t is None else int(n_coarse), int(n), _p(ms), C.byref(ck)))
         return ms, int(ck.value)
 
     # ---- the layers the reports share, over caller data (tests/test_hip_rows_direct.py)
@@ -1304,7 +1293,7 @@ class Context:
             raise HipError("debug_scan64: the words are an array of [n_arrays, stride]")
         after = words.copy()
         out = np.full(words.shape, sentinel, np.uint64)
-        _ck(lib().ig_debug_scan64(self._h, _p(after), C.c_int32(int(n)), C.c_int32(words.shape[0]), C.c_int64(words.shape[1]), _p(out)))
+        _ck(lib().ig_debug_scan64(self._h, _p(after), int(n), words.shape[0], words.shape[1], _p(out)))
         return out, after
 
     def debug_rows_build(self, lo, word, n_rows, reduce=False, combine=True):
@@ -1317,16 +1306,16 @@ class Context:
             raise HipError("debug_rows_build: lo and word are vectors of one length")
         ne, no = C.c_int64(), C.c_int64()
         o = np.zeros(8, np.int64)
-        _ck(lib().ig_debug_rows_build(self._h, _p(lo), _p(word), C.c_int64(lo.size), C.c_int32(int(n_rows)), C.c_int32(int(bool(reduce))),
-                                      C.c_int32(int(bool(combine))), C.byref(ne), C.byref(no), _p(o)))
+        _ck(lib().ig_debug_rows_build(self._h, _p(lo), _p(word), lo.size, int(n_rows), int(bool(reduce)),
+                                      int(bool(combine)), C.byref(ne), C.byref(no), _p(o)))
         out = dict(n_entries=int(ne.value), n_out=int(no.value), rowptr=np.zeros(int(n_rows) + 1, np.int64),
                    forms=dict(short=(int(o[0]), int(o[1])), lds=(int(o[2]), int(o[3])), long=(int(o[4]), int(o[5])), runs=int(o[6]), longest=int(o[7])))
         if reduce:
             out["col"], out["count"] = np.zeros(out["n_out"], np.int32), np.zeros(out["n_out"], np.int64)
         else:
             out["word"] = np.zeros(out["n_out"], np.uint64)
-        _ck(lib().ig_debug_rows_fetch(self._h, _p(out["rowptr"]), C.c_int64(out["rowptr"].size), _p(out.get("word")), _p(out.get("col")), _p(out.get("count")),
-                                      C.c_int64(out["n_out"])))
+        _ck(lib().ig_debug_rows_fetch(self._h, _p(out["rowptr"]), out["rowptr"].size, _p(out.get("word")), _p(out.get("col")), _p(out.get("count")),
+                                      out["n_out"]))
         return out
 
     def debug_wave_runs(self, keys, values, n_dest, wide=False):
@@ -1338,8 +1327,7 @@ class Context:
         if keys.ndim != 1 or keys.shape != values.shape:
             raise HipError("debug_wave_runs: keys and values are vectors of one length")
         out, n_at = np.zeros(max(int(n_dest), 0), np.int64), C.c_int64()
-        _ck(lib().ig_debug_wave_runs(self._h, _p(keys), _p(values), C.c_int64(keys.size), C.c_int32(int(n_dest)), C.c_int32(int(bool(wide))), _p(out),
-                                     C.byref(n_at)))
+        _ck(lib().ig_debug_wave_runs(self._h, _p(keys), _p(values), keys.size, int(n_dest), int(bool(wide)), _p(out), C.byref(n_at)))
         return out, int(n_at.value)
 
     # ---- join support: which scaffold ends the contacts would link (the rule: join_support.py)
@@ -1351,12 +1339,12 @@ class Context:
 
         ne, nl = C.c_int64(), C.c_int64()
         sc = np.zeros(8, np.int64)
-        _ck(lib().ig_join_support_build(self._h, C.c_int32(int(window)), C.c_int32(int(bool(model))), C.byref(ne), C.byref(nl), _p(sc)))
+        _ck(lib().ig_join_support_build(self._h, int(window), int(bool(model)), C.byref(ne), C.byref(nl), _p(sc)))
         K = ne.value // 2
         rowptr = np.zeros(ne.value + 1, np.int64)
-        _ck(lib().ig_join_support_rows(self._h, _p(rowptr), C.c_int64(rowptr.size)))
+        _ck(lib().ig_join_support_rows(self._h, _p(rowptr), rowptr.size))
         first, n = np.zeros(K, np.int32), np.zeros(K, np.int32)
-        _ck(lib().ig_join_support_ends(self._h, _p(first), _p(n), C.c_int64(K)))
+        _ck(lib().ig_join_support_ends(self._h, _p(first), _p(n), K))
         out = dict(window=int(window), model=bool(model), rowptr=rowptr, first_position=first, n_positions=n)
         out.update((k, int(v)) for k, v in zip(SCALARS, sc))
         return out
@@ -1368,7 +1356,7 @@ class Context:
         col, obs = np.zeros(max(n, 0), np.int32), np.zeros(max(n, 0), np.int64)
         prs = np.zeros(max(n, 0), np.int64) if model else None
         exq = np.zeros(max(n, 0), np.int64) if model else None
-        _ck(lib().ig_join_support_fetch(self._h, C.c_int64(int(first)), C.c_int64(n), _p(col), _p(obs), _p(prs), _p(exq)))
+        _ck(lib().ig_join_support_fetch(self._h, int(first), n, _p(col), _p(obs), _p(prs), _p(exq)))
         return col, obs, prs, exq
 
     def join_support_release(self):
@@ -1377,7 +1365,7 @@ class Context:
     def debug_join_support_combine(self, combine=True):
         """the two passes over the contacts of the join support: one atomic per run of a wave's lanes with the same row (True) or
         one per emission (False, the yardstick); None: the form the library ships"""
-        _ck(lib().ig_debug_join_support_combine(self._h, C.c_int32(-1 if combine is None else int(bool(combine)))))
+        _ck(lib().ig_debug_join_support_combine(self._h, -1 if combine is None else int(bool(combine))))
 
     def debug_join_support_forms(self):
         """the last join support build's work lists, as ``debug_assembly_contacts_forms``"""
@@ -1390,7 +1378,7 @@ class Context:
         of the last result)"""
         ms = np.zeros((int(n), len(JOIN_SUPPORT_PASSES)), np.float32)
         ck = C.c_int64()
-        _ck(lib().ig_debug_join_support_time(self._h, C.c_int32(int(window)), C.c_int32(int(n)), _p(ms), C.byref(ck)))
+        _ck(lib().ig_debug_join_support_time(self._h, int(window), int(n), _p(ms), C.byref(ck)))
         return ms, int(ck.value)
 
     # ---- orientation support: which segments the contacts would reverse (the rule: orientation_support.py)
@@ -1417,8 +1405,7 @@ class Context:
         exq = np.zeros((n_seg, 2), np.int64) if model else None
         sc = np.zeros(8, np.int64)
         n = C.c_int32()
-        _ck(lib().ig_orientation_support(self._h, C.c_int32(int(window)), C.c_int32(int(bool(model))), C.c_int32(n_seg), _p(f), _p(l), _p(geo), _p(obs), _p(exq),
-                                         _p(sc), C.byref(n)))
+        _ck(lib().ig_orientation_support(self._h, int(window), int(bool(model)), n_seg, _p(f), _p(l), _p(geo), _p(obs), _p(exq), _p(sc), C.byref(n)))
         out = dict(window=int(window), n_placed=n.value, n_seg=n_seg, first=f.astype(np.int64), last=l.astype(np.int64), geometry=geo, observed=obs, expected_q=exq)
         out.update((k, int(v)) for k, v in zip(SCALARS, sc))
         return out
@@ -1430,9 +1417,8 @@ class Context:
         f, l = self._segments(first, last)
         ms = np.zeros(int(n), np.float32)
         ck = C.c_int64()
-        _ck(lib().ig_debug_orientation_support_time(self._h, C.c_int32(int(window)), C.c_int32(int(f.size)), _p(f), _p(l),
-                                                    C.c_int32(("observed", "model").index(which)), C.c_int32(forms.index(forms[0] if form is None else form)),
-                                                    C.c_int32(int(n)), _p(ms), C.byref(ck)))
+        _ck(lib().ig_debug_orientation_support_time(self._h, int(window), int(f.size), _p(f), _p(l), ("observed", "model").index(which),
+                                                    forms.index(forms[0] if form is None else form), int(n), _p(ms), C.byref(ck)))
         return ms, int(ck.value)
 
     # ---- gap support: the distance the contacts put across each join (the rule: gap_support.py)
@@ -1462,7 +1448,7 @@ class Context:
         lgq = np.zeros((max(n_j, 1), max(K, 1)), np.int64)
         exq = np.zeros((max(n_j, 1), max(K, 1)), np.int64) if model else None
         sc = np.zeros(8, np.int64)
-        _ck(lib().ig_gap_support(self._h, C.c_int32(int(window)), C.c_int32(int(bool(model))), C.c_int32(n_j), _p(j), C.c_int32(K), _p(g), _p(status), _p(geo),
+        _ck(lib().ig_gap_support(self._h, int(window), int(bool(model)), n_j, _p(j), K, _p(g), _p(status), _p(geo),
                                  _p(obs), _p(prs), _p(lgq), _p(exq), _p(sc)))
         out = dict(window=int(window), n_junctions=n_j, junction=j.astype(np.int64), gaps_kb=g, status=status, geometry=geo, observed=obs, pairs=prs, log_q=lgq,
                    expected_q=exq)
@@ -1476,8 +1462,8 @@ class Context:
         j, g = self._junctions_and_gaps(junctions, gaps_kb)
         ms = np.zeros(int(n), np.float32)
         ck = C.c_int64()
-        _ck(lib().ig_debug_gap_support_time(self._h, C.c_int32(int(window)), C.c_int32(int(j.size)), _p(j), C.c_int32(int(g.size)), _p(g),
-                                            C.c_int32(GAP_SUPPORT_PASSES.index(which)), C.c_int32(int(n)), _p(ms), C.byref(ck)))
+        _ck(lib().ig_debug_gap_support_time(self._h, int(window), int(j.size), _p(j), int(g.size), _p(g),
+                                            GAP_SUPPORT_PASSES.index(which), int(n), _p(ms), C.byref(ck)))
         return ms, int(ck.value)
 
     # ---- placement support: where the contacts say each bin belongs (the rule: placement_support.py)
@@ -1494,7 +1480,7 @@ class Context:
         out.update((k, np.zeros(max(self.N, 1), np.int32)) for k in INT_ARRAYS)
         out.update((k, np.zeros(max(self.N, 1), np.int64)) for k in LONG_ARRAYS)
         sc = np.zeros(7, np.int64)
-        _ck(lib().ig_placement_support(self._h, C.c_int32(window), C.c_int32(min_hosts), *[_p(out[k]) for k in INT_ARRAYS + LONG_ARRAYS], _p(sc)))
+        _ck(lib().ig_placement_support(self._h, window, min_hosts, *[_p(out[k]) for k in INT_ARRAYS + LONG_ARRAYS], _p(sc)))
         for k in INT_ARRAYS + LONG_ARRAYS:
             out[k] = out[k][:self.N]
         out.update((k, int(v)) for k, v in zip(SCALARS, sc))
@@ -1503,7 +1489,7 @@ class Context:
     def debug_placement_support_form(self, form="default"):
         """the scan of the placement support: ``"thread"`` (a thread per row, the yardstick), ``"wave"`` (a wave per row) or
         ``"default"`` (the form the library ships: by the row's length)"""
-        _ck(lib().ig_debug_placement_support_form(self._h, C.c_int32(PLACEMENT_SUPPORT_FORMS.index(form))))
+        _ck(lib().ig_debug_placement_support_form(self._h, PLACEMENT_SUPPORT_FORMS.index(form)))
 
     def debug_placement_support_forms(self):
         """the last placement support call's work lists, as ``debug_assembly_contacts_forms``"""
@@ -1516,7 +1502,7 @@ class Context:
         the last call)"""
         ms = np.zeros((int(n), len(PLACEMENT_SUPPORT_PASSES)), np.float32)
         ck = C.c_int64()
-        _ck(lib().ig_debug_placement_support_time(self._h, C.c_int32(int(window)), C.c_int32(int(window) if min_hosts is None else int(min_hosts)), C.c_int32(int(n)),
+        _ck(lib().ig_debug_placement_support_time(self._h, int(window), int(window) if min_hosts is None else int(min_hosts), int(n),
                                                   _p(ms), C.byref(ck)))
         return ms, int(ck.value)
 
@@ -1546,7 +1532,7 @@ class Context:
         longs = np.zeros((len(LONG_ARRAYS), n_seg), np.int64)
         quad = np.zeros((n_seg, 3, 4), np.int64)
         sc = np.zeros(len(SCALARS), np.int64)
-        _ck(lib().ig_segment_placement(self._h, C.c_int32(window), C.c_int32(min_hosts), C.c_int32(n_seg), _p(f), _p(l), _p(ints), _p(longs), _p(quad), _p(sc)))
+        _ck(lib().ig_segment_placement(self._h, window, min_hosts, n_seg, _p(f), _p(l), _p(ints), _p(longs), _p(quad), _p(sc)))
         out = dict(window=window, min_hosts=min_hosts, n_seg=n_seg, first=f.astype(np.int64), last=l.astype(np.int64), quadrants=quad)
         out.update((k, ints[i].copy()) for i, k in enumerate(INT_ARRAYS))
         out.update((k, longs[i].copy()) for i, k in enumerate(LONG_ARRAYS))
@@ -1559,8 +1545,8 @@ class Context:
         f, l = self._placement_segments(first, last)
         ms = np.zeros((int(n), len(SEGMENT_PLACEMENT_PASSES)), np.float32)
         ck = C.c_int64()
-        _ck(lib().ig_debug_segment_placement_time(self._h, C.c_int32(int(window)), C.c_int32(int(window) if min_hosts is None else int(min_hosts)), C.c_int32(int(f.size)),
-                                                  _p(f), _p(l), C.c_int32(int(n)), _p(ms), C.byref(ck)))
+        _ck(lib().ig_debug_segment_placement_time(self._h, int(window), int(window) if min_hosts is None else int(min_hosts), int(f.size),
+                                                  _p(f), _p(l), int(n), _p(ms), C.byref(ck)))
         return ms, int(ck.value)
 
     # ---- segment edits: the moves the block-level reports propose, scored exactly and applied (the rule: rearrange.py)
@@ -1579,7 +1565,7 @@ class Context:
         n = int(e.shape[0])
         status, limbs = np.zeros(n, np.int32), np.zeros((n, 5), np.int64)
         nz, z = np.zeros(n, np.float64), np.zeros(n, np.float64)
-        _ck(lib().ig_edit_score(self._h, C.c_int32(n), _p(e), C.c_int32(int(form)), _p(status), _p(limbs), _p(nz), _p(z)))
+        _ck(lib().ig_edit_score(self._h, n, _p(e), int(form), _p(status), _p(limbs), _p(nz), _p(z)))
         return status, limbs, nz, z
 
     def edit_state(self, edit):
@@ -1609,7 +1595,7 @@ class Context:
         e = self._edits(edits)
         ms = np.zeros((int(n), len(EDIT_PASSES)), np.float32)
         ck = C.c_int64()
-        _ck(lib().ig_debug_edit_time(self._h, C.c_int32(int(e.shape[0])), _p(e), C.c_int32(int(form)), C.c_int32(int(n)), _p(ms), C.byref(ck)))
+        _ck(lib().ig_debug_edit_time(self._h, int(e.shape[0]), _p(e), int(form), int(n), _p(ms), C.byref(ck)))
         return ms, int(ck.value)
 
     # ---- cut and join scores: the closed part of the likelihood change of every cut and every link (the rule: cut_join.py)
@@ -1644,12 +1630,12 @@ class Context:
         sep = np.ascontiguousarray(s, np.float32)
         dd, tt, cc = (np.ascontiguousarray(np.broadcast_to(np.asarray(a), sep.shape), np.int32) for a in (d, trans, count))
         q = np.zeros(sep.shape, np.int64)
-        _ck(lib().ig_debug_contact_terms(self._h, _p(sep), _p(dd), _p(tt), _p(cc), C.c_int64(sep.size), _p(q)))
+        _ck(lib().ig_debug_contact_terms(self._h, _p(sep), _p(dd), _p(tt), _p(cc), sep.size, _p(q)))
         return q
 
     def debug_cut_join_form(self, form=-1):
         """tests: the form of the join pass: -1 by the number of pairs, 0 accumulators in LDS, 1 atomics per run of a wave"""
-        _ck(lib().ig_debug_cut_join_form(self._h, C.c_int32(int(form))))
+        _ck(lib().ig_debug_cut_join_form(self._h, int(form)))
 
     def debug_join_scores_forms(self):
         """the LIFT_C_* words of the pairs' rows of the last finished ``join_scores`` build (the handle keeps them behind the release)"""
@@ -1662,7 +1648,7 @@ class Context:
         (ms [n, 12]: ``CUT_JOIN_PASSES``, checksum of the integer words of the last result: the forms agree on it)"""
         ms = np.zeros((int(n), len(CUT_JOIN_PASSES)), np.float32)
         ck = C.c_int64()
-        _ck(lib().ig_debug_cut_join_time(self._h, C.c_int32(("cuts", "joins").index(what)), C.c_int32(int(n)), _p(ms), C.byref(ck)))
+        _ck(lib().ig_debug_cut_join_time(self._h, ("cuts", "joins").index(what), int(n), _p(ms), C.byref(ck)))
         return ms, int(ck.value)
 
     # ---- balancing the contact map of the current genome (the rule: balance.py)
@@ -1675,10 +1661,10 @@ class Context:
         lv = LEVELS.index(level) if level in LEVELS else int(level)
         nu, ne = C.c_int64(), C.c_int64()
         sc = np.zeros(8, np.int64)
-        _ck(lib().ig_balance_build(self._h, C.c_int32(lv), C.c_int32(int(max_side)), C.c_int32(int(ignore_diags)), C.byref(nu), C.byref(ne), _p(sc)))
+        _ck(lib().ig_balance_build(self._h, lv, int(max_side), int(ignore_diags), C.byref(nu), C.byref(ne), _p(sc)))
         U = int(nu.value)
         rowptr, nnz, total = np.zeros(U + 1, np.int64), np.zeros(U, np.int64), np.zeros(U, np.int64)
-        _ck(lib().ig_balance_rows(self._h, _p(rowptr), _p(nnz), _p(total), C.c_int64(rowptr.size)))
+        _ck(lib().ig_balance_rows(self._h, _p(rowptr), _p(nnz), _p(total), rowptr.size))
         out = dict(level=level, rowptr=rowptr, nnz=nnz, total=total)
         out.update((k, int(v)) for k, v in zip(SCALARS, sc))
         return out
@@ -1687,7 +1673,7 @@ class Context:
         """entries first .. first + n - 1 of the built rows -> (col int32 [n], count int64 [n])"""
         n = int(n)
         col, cnt = np.zeros(max(n, 0), np.int32), np.zeros(max(n, 0), np.int64)
-        _ck(lib().ig_balance_fetch(self._h, C.c_int64(int(first)), C.c_int64(n), _p(col), _p(cnt)))
+        _ck(lib().ig_balance_fetch(self._h, int(first), n, _p(col), _p(cnt)))
         return col, cnt
 
     def balance_run(self, b0, tol=1e-5, max_iters=200):
@@ -1698,7 +1684,7 @@ class Context:
         b, marg = np.zeros(b0.size, np.float64), np.zeros(b0.size, np.float64)
         var = np.zeros(max(max_iters, 1), np.float64)
         n, conv = C.c_int32(), C.c_int32()
-        _ck(lib().ig_balance_run(self._h, _p(b0), C.c_double(float(tol)), C.c_int32(max_iters), _p(b), _p(marg), _p(var), C.byref(n), C.byref(conv)))
+        _ck(lib().ig_balance_run(self._h, _p(b0), float(tol), max_iters, _p(b), _p(marg), _p(var), C.byref(n), C.byref(conv)))
         return dict(b=b, marg_final=marg, variance=var[:n.value].copy(), n_iters=int(n.value), converged=bool(conv.value))
 
     def balance_release(self):
@@ -1707,11 +1693,11 @@ class Context:
     def debug_balance_form(self, form="default"):
         """the marginals kernel: ``"wave"`` (a wave per row, the yardstick), ``"packed"`` (four rows of at most 16 entries share a
         wave) or ``"default"`` (the form the library ships)"""
-        _ck(lib().ig_debug_balance_form(self._h, C.c_int32(BALANCE_FORMS.index(form))))
+        _ck(lib().ig_debug_balance_form(self._h, BALANCE_FORMS.index(form)))
 
     def debug_balance_group(self, group=0):
         """the iterations ``balance_run`` enqueues between two looks at the device's done flag (0: the default)"""
-        _ck(lib().ig_debug_balance_group(self._h, C.c_int32(int(group))))
+        _ck(lib().ig_debug_balance_group(self._h, int(group)))
 
     def debug_lane_sums(self, values, rowptr):
         """the ordered sum (``balance.lane_sum``) of every row of caller data on the device, in the handle's form -> f64 [n_rows]"""
@@ -1720,13 +1706,13 @@ class Context:
         if rowptr.size < 2 or rowptr[-1] != values.size:
             raise HipError("debug_lane_sums: rowptr has n_rows + 1 >= 2 words and ends at the number of values")
         out = np.zeros(rowptr.size - 1, np.float64)
-        _ck(lib().ig_debug_lane_sums(self._h, _p(values), _p(rowptr), C.c_int64(rowptr.size - 1), _p(out)))
+        _ck(lib().ig_debug_lane_sums(self._h, _p(values), _p(rowptr), rowptr.size - 1, _p(out)))
         return out
 
     def debug_balance_time(self, what="marginals", n=1):
         """over the built rows, from b = 1: ``"marginals"`` (the kernel alone) or ``"iteration"`` n times, event-timed -> ms [n]"""
         ms = np.zeros(int(n), np.float32)
-        _ck(lib().ig_debug_balance_time(self._h, C.c_int32(("marginals", "iteration").index(what)), C.c_int32(int(n)), _p(ms)))
+        _ck(lib().ig_debug_balance_time(self._h, ("marginals", "iteration").index(what), int(n), _p(ms)))
         return ms
 
     def debug_balance_build_time(self, level="bin", max_side=2048, ignore_diags=2, n=1):
@@ -1734,7 +1720,7 @@ class Context:
         from .balance import LEVELS
 
         ms = np.zeros((int(n), len(BALANCE_BUILD_PASSES)), np.float32)
-        _ck(lib().ig_debug_balance_build_time(self._h, C.c_int32(LEVELS.index(level)), C.c_int32(int(max_side)), C.c_int32(int(ignore_diags)), C.c_int32(int(n)), _p(ms)))
+        _ck(lib().ig_debug_balance_build_time(self._h, LEVELS.index(level), int(max_side), int(ignore_diags), int(n), _p(ms)))
         return ms
 
     # ---- the balancing's rows from a built map (the rule: balance.entries_of_rows)
@@ -1752,7 +1738,7 @@ class Context:
 
         U = int(nu.value)
         rowptr, nnz, total = np.zeros(U + 1, np.int64), np.zeros(U, np.int64), np.zeros(U, np.int64)
-        _ck(lib().ig_balance_rows(self._h, _p(rowptr), _p(nnz), _p(total), C.c_int64(rowptr.size)))
+        _ck(lib().ig_balance_rows(self._h, _p(rowptr), _p(nnz), _p(total), rowptr.size))
         out = dict(level="units", rowptr=rowptr, nnz=nnz, total=total, n_entries=int(ne.value))
         out.update((k, int(v)) for k, v in zip(SNAPSHOT_SCALARS, sc))
         return out
@@ -1765,8 +1751,7 @@ class Context:
         ``balance_fetch``, the iterations through ``balance_run``"""
         m, g = self._snapshot_mode(mode, group, "balance_build_snapshot")
         nu, ne, sc = C.c_int64(), C.c_int64(), np.zeros(8, np.int64)
-        _ck(lib().ig_balance_build_snapshot(self._h, C.c_int32(int(ignore_diags)), C.c_int32(m), _p(g), C.c_int64(0 if g is None else g.size), C.byref(nu), C.byref(ne),
-                                            _p(sc)))
+        _ck(lib().ig_balance_build_snapshot(self._h, int(ignore_diags), m, _p(g), 0 if g is None else g.size, C.byref(nu), C.byref(ne), _p(sc)))
         return self._snapshot_rows(nu, ne, sc)
 
     def debug_balance_snapshot(self, rowptr, col, count, ignore_diags=2, mode="all", group=None):
@@ -1779,15 +1764,15 @@ class Context:
             raise HipError("debug_balance_snapshot: rowptr [U + 1], col and count [rowptr[U]]")
         m, g = self._snapshot_mode(mode, group, "debug_balance_snapshot")
         nu, ne, sc = C.c_int64(), C.c_int64(), np.zeros(8, np.int64)
-        _ck(lib().ig_debug_balance_snapshot(self._h, _p(rowptr), _p(col), _p(count), C.c_int64(rowptr.size - 1), C.c_int32(int(ignore_diags)), C.c_int32(m), _p(g),
-                                            C.c_int64(0 if g is None else g.size), C.byref(nu), C.byref(ne), _p(sc)))
+        _ck(lib().ig_debug_balance_snapshot(self._h, _p(rowptr), _p(col), _p(count), rowptr.size - 1, int(ignore_diags), m, _p(g),
+                                            0 if g is None else g.size, C.byref(nu), C.byref(ne), _p(sc)))
         return self._snapshot_rows(nu, ne, sc)
 
     def debug_balance_snapshot_time(self, n=1):
         """the build from the resident snapshot n times with hipEvents around each pass -> ms [n, 7]: ``BALANCE_SNAPSHOT_PASSES``; the
         snapshot stays, and so do the last build's rows"""
         ms = np.zeros((int(n), len(BALANCE_SNAPSHOT_PASSES)), np.float32)
-        _ck(lib().ig_debug_balance_snapshot_time(self._h, C.c_int32(int(n)), _p(ms)))
+        _ck(lib().ig_debug_balance_snapshot_time(self._h, int(n), _p(ms)))
         return ms
 
     # ---- bookkeeping
@@ -1816,14 +1801,14 @@ class Context:
         _ck(lib().ig_sync(self._h))
 
     def set_stream(self, hip_stream_ptr):
-        _ck(lib().ig_set_stream(self._h, C.c_void_p(hip_stream_ptr)))
+        _ck(lib().ig_set_stream(self._h, hip_stream_ptr))
 
     # ---- timing
     def reset_timers(self, enable=True):
-        _ck(lib().ig_reset_timers(self._h, C.c_int(int(enable))))
+        _ck(lib().ig_reset_timers(self._h, int(enable)))
 
     def set_timer_sampling(self, every):
-        _ck(lib().ig_set_timer_sampling(self._h, C.c_int(int(every))))
+        _ck(lib().ig_set_timer_sampling(self._h, int(every)))
 
     def kernel_time_ms(self, name):
         avg = C.c_double()
@@ -1833,14 +1818,14 @@ class Context:
 
     # ---- multi-GPU two-phase move
     def set_shard(self, rank, world):
-        _ck(lib().ig_set_shard(self._h, C.c_int32(rank), C.c_int32(world)))
+        _ck(lib().ig_set_shard(self._h, rank, world))
 
     def partials(self):
         return lib().ig_partials_device_ptr(self._h), lib().ig_partials_count(self._h)
 
     def step_begin(self, frag_a, cands):
         c = np.ascontiguousarray(cands, np.int32)
-        _ck(lib().ig_step_begin(self._h, C.c_int32(int(frag_a)), _p(c), C.c_int32(c.size)))
+        _ck(lib().ig_step_begin(self._h, int(frag_a), _p(c), c.size))
 
     def step_finish(self, n_cands, want_scores=False):
         res = MoveResult()
@@ -1858,12 +1843,12 @@ class Context:
         exc = np.zeros(n, np.float32)
         term = np.zeros(n, np.float64)
         q = np.zeros(n, np.int64)
-        _ck(lib().ig_debug_eval_terms(self._h, _p(s), _p(st), _p(ob), C.c_int64(n), _p(ex), _p(exc), _p(term), _p(q)))
+        _ck(lib().ig_debug_eval_terms(self._h, _p(s), _p(st), _p(ob), n, _p(ex), _p(exc), _p(term), _p(q)))
         return ex, exc, term, q
 
     def debug_candidate_state(self, cand, slot):
         out = np.zeros((17, self.N), np.int32)
-        _ck(lib().ig_debug_candidate_state(self._h, C.c_int32(cand), C.c_int32(slot), _p(out)))
+        _ck(lib().ig_debug_candidate_state(self._h, cand, slot, _p(out)))
         return out
 
     def debug_last_sums(self, n_cands):
@@ -1900,14 +1885,14 @@ class Context:
     def debug_dbg(self, clear=False):
         """Glob.dbg (what raised a device-side consistency failure; in a tuning build a kernel's tick counters)"""
         o = np.zeros(8, np.int32)
-        _ck(lib().ig_debug_dbg(self._h, _p(o), C.c_int32(int(bool(clear)))))
+        _ck(lib().ig_debug_dbg(self._h, _p(o), int(bool(clear))))
         return o
 
     def debug_pz_table(self, which=0):
         """the P_z table set_params built for parameter set ``which``: pz[d] for every rank distance d below its length"""
         out = np.zeros(4096, np.float32)
         n = C.c_int32()
-        _ck(lib().ig_debug_pz_table(self._h, C.c_int32(int(which)), _p(out), C.c_int32(out.size), C.byref(n)))
+        _ck(lib().ig_debug_pz_table(self._h, int(which), _p(out), out.size, C.byref(n)))
         assert 0 <= n.value <= out.size, n.value
         return out[: n.value].copy()
 

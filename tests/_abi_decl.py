@@ -1,12 +1,15 @@
-"""What the ABI tests read out of the sources: an entry point's declaration in the header and its one call in hip_lib.py."""
-import re
+"""What the ABI tests read out of the sources: an entry point's declaration in the header (``instagraal_amd.abi``, the parser the binding
+itself loads its signatures with) and its one call in hip_lib.py."""
+import functools
+
+from instagraal_amd import abi
+
+declarations = functools.lru_cache(maxsize=None)(abi.declarations)
 
 
 def declaration(header, name):
-    """the arguments of ``int <name>(...);`` in the header's text, one string each"""
-    m = re.search(r"\bint %s\(([^;]*)\);" % name, header)
-    assert m, name
-    return [a.strip() for a in m.group(1).replace("\n", " ").split(",")]
+    """the parameters of ``<name>`` as the header's text declares them, one string each"""
+    return [p.text for p in declarations(header)[name].params]
 
 
 def call_args(source, name):
@@ -24,3 +27,13 @@ def call_args(source, name):
             cur += ch
         i += 1
     return args + [cur.strip()]
+
+
+def assert_bound_as_declared(header, binding, name):
+    """the loaded library's function carries the header's types, and the binding's call passes one argument for each, the handle first"""
+    from instagraal_amd import hip_lib
+
+    decl, fn = declarations(header)[name], getattr(hip_lib.lib(), name)
+    assert fn.restype is decl.restype and list(fn.argtypes) == [p.ctype for p in decl.params], (name, fn.restype, fn.argtypes)
+    call = call_args(binding, name)
+    assert len(call) == len(decl.params) and call[0] == "self._h", (name, call)

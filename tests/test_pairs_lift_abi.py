@@ -8,33 +8,12 @@ import re
 
 from conftest import ROOT
 
+from _abi_decl import assert_bound_as_declared as _assert_bound_as_declared, declaration as _declaration
+
 ENTRY_POINTS = ("ig_pairs_begin", "ig_pairs_lift", "ig_pairs_pixels_build", "ig_pairs_law", "ig_pairs_clear", "ig_pairs_end", "ig_debug_pairs_time")
 # the number of arguments of every entry point in the header, the handle included: what the ctypes calls of hip_lib pass
 N_ARGS = dict(ig_pairs_begin=16, ig_pairs_lift=17, ig_pairs_pixels_build=6, ig_pairs_law=6, ig_pairs_clear=1, ig_pairs_end=1, ig_debug_pairs_time=14)
 EMPTY = inspect.Parameter.empty
-
-
-def _declaration(header, name):
-    m = re.search(r"\bint %s\(([^;]*)\);" % name, header)
-    assert m, name
-    return [a.strip() for a in m.group(1).replace("\n", " ").split(",")]
-
-
-def _call_args(source, name):
-    """the arguments of the one call of lib().<name>( in hip_lib.py, split at the top level"""
-    i = source.index("lib().%s(" % name) + len("lib().%s(" % name)
-    depth, args, cur = 1, [], ""
-    while depth:
-        ch = source[i]
-        depth += ch in "(["
-        depth -= ch in ")]"
-        if depth == 1 and ch == ",":
-            args.append(cur.strip())
-            cur = ""
-        elif depth:
-            cur += ch
-        i += 1
-    return args + [cur.strip()]
 
 
 def test_the_entry_points_are_declared_exported_and_bound_with_matching_signatures():
@@ -60,13 +39,7 @@ def test_the_entry_points_are_declared_exported_and_bound_with_matching_signatur
         defn = re.search(r'extern "C" int %s\(([^)]*)\)' % name, source).group(1).replace("\n", " ").split(",")
         strip = lambda a: re.sub(r"\s+", " ", a.strip())  # noqa: E731
         assert [strip(a).replace("ig_ctx* c", "ig_ctx* ctx") for a in defn] == [strip(a) for a in decl], name  # the definition is the declaration
-        call = _call_args(binding, name)
-        assert len(call) == len(decl) and call[0] == "self._h", (name, call)
-        for passed, want in zip(call[1:], decl[1:]):  # a scalar goes by its own ctypes type, an array by its address
-            if "*" in want or "[" in want:
-                assert "c_int" not in passed.split("(")[0] and ("_p(" in passed or "byref(" in passed or passed.startswith("o(")), (name, passed, want)
-            else:
-                assert passed.startswith("C.c_%s(" % want.split()[0].replace("_t", "")), (name, passed, want)
+        _assert_bound_as_declared(header, binding, name)  # the live argtypes are the header's; one argument each, the handle first
     for name in os.listdir(csrc):  # ... and defined nowhere else
         if name != "ig_host_pairs.inc":
             other = open(os.path.join(csrc, name)).read()

@@ -8,7 +8,7 @@ import re
 
 from conftest import ROOT
 
-from _abi_decl import call_args as _call_args, declaration as _declaration
+from _abi_decl import assert_bound_as_declared as _assert_bound_as_declared, declaration as _declaration
 
 ENTRY_POINTS = ("ig_seq_begin", "ig_seq_composition", "ig_seq_plan", "ig_seq_window", "ig_seq_out_composition", "ig_seq_end")
 N_ARGS = dict(ig_seq_begin=6, ig_seq_composition=3, ig_seq_plan=16, ig_seq_window=5, ig_seq_out_composition=3, ig_seq_end=1)
@@ -38,13 +38,7 @@ def test_the_entry_points_are_declared_exported_and_bound_with_matching_signatur
         defn = re.search(r'extern "C" int %s\(([^)]*)\)' % name, source).group(1).replace("\n", " ").split(",")
         strip = lambda a: re.sub(r"\s+", " ", a.strip())  # noqa: E731
         assert [strip(a).replace("ig_ctx* c", "ig_ctx* ctx") for a in defn] == [strip(a) for a in decl], name  # the definition is the declaration
-        call = _call_args(binding, name)
-        assert len(call) == len(decl) and call[0] == "self._h", (name, call)
-        for passed, want in zip(call[1:], decl[1:]):  # a scalar goes by its own ctypes type, an array by its address
-            if "*" in want or "[" in want:
-                assert "c_int" not in passed.split("(")[0] and ("_p(" in passed or "byref(" in passed), (name, passed, want)
-            else:
-                assert passed.startswith("C.c_%s(" % want.split()[0].replace("_t", "")), (name, passed, want)
+        _assert_bound_as_declared(header, binding, name)  # the live argtypes are the header's; one argument each, the handle first
     for name in os.listdir(csrc):  # ... and defined nowhere else
         if name != "ig_host_seq.inc":
             other = open(os.path.join(csrc, name)).read()

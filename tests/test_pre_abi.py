@@ -8,7 +8,7 @@ import re
 
 from conftest import ROOT
 
-from _abi_decl import call_args as _call_args, declaration as _declaration
+from _abi_decl import assert_bound_as_declared as _assert_bound_as_declared, declaration as _declaration
 
 ENTRY_POINTS = ("ig_pre_begin", "ig_pre_digest", "ig_pre_fragments", "ig_pre_add_pairs", "ig_pre_pixels_build", "ig_pre_pixels_rows", "ig_pre_pixels_fetch", "ig_pre_clear",
                 "ig_pre_end")
@@ -41,13 +41,7 @@ def test_the_entry_points_are_declared_exported_and_bound_with_matching_signatur
         defn = re.search(r'extern "C" int %s\(([^)]*)\)' % name, source).group(1).replace("\n", " ").split(",")
         strip = lambda a: re.sub(r"\s+", " ", a.strip())  # noqa: E731
         assert [strip(a).replace("ig_ctx* c", "ig_ctx* ctx") for a in defn] == [strip(a) for a in decl], name  # the definition is the declaration
-        call = _call_args(binding, name)
-        assert len(call) == len(decl) and call[0] == "self._h", (name, call)
-        for passed, want in zip(call[1:], decl[1:]):  # a scalar goes by its own ctypes type, an array by its address
-            if "*" in want or "[" in want:
-                assert "c_int" not in passed.split("(")[0] and ("_p(" in passed or "byref(" in passed), (name, passed, want)
-            else:
-                assert passed.startswith("C.c_%s(" % want.split()[0].replace("_t", "")), (name, passed, want)
+        _assert_bound_as_declared(header, binding, name)  # the live argtypes are the header's; one argument each, the handle first
     for name in os.listdir(csrc):  # ... and defined nowhere else
         if name != "ig_host_pre.inc":
             other = open(os.path.join(csrc, name)).read()

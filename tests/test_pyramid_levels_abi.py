@@ -8,7 +8,7 @@ import re
 
 from conftest import ROOT
 
-from _abi_decl import call_args as _call_args, declaration as _declaration
+from _abi_decl import assert_bound_as_declared as _assert_bound_as_declared, declaration as _declaration
 
 ENTRY_POINTS = ("ig_pyr_begin", "ig_pyr_matrix", "ig_pyr_degrees", "ig_pyr_remap", "ig_pyr_rows", "ig_pyr_fetch", "ig_pyr_end", "ig_debug_pyr_piece")
 # the number of arguments of every entry point in the header, the handle included: what the ctypes calls of hip_lib pass
@@ -40,13 +40,7 @@ def test_the_entry_points_are_declared_exported_and_bound_with_matching_signatur
         strip = lambda a: re.sub(r"\s+", " ", a.strip())  # noqa: E731
         assert [strip(a).replace("ig_ctx* c", "ig_ctx* ctx") for a in defn] == [strip(a) for a in decl], name  # the definition is the declaration
         assert binding.count("lib().%s(" % name) == 1, name
-        call = _call_args(binding, name)
-        assert len(call) == len(decl) and call[0] == "self._h", (name, call)
-        for passed, want in zip(call[1:], decl[1:]):  # a scalar goes by its own ctypes type, an array by its address
-            if "*" in want or "[" in want:
-                assert "c_int" not in passed.split("(")[0] and ("_p(" in passed or "byref(" in passed), (name, passed, want)
-            else:
-                assert passed.startswith("C.c_%s(" % want.split()[0].replace("_t", "")), (name, passed, want)
+        _assert_bound_as_declared(header, binding, name)  # the live argtypes are the header's; one argument each, the handle first
     for name in os.listdir(csrc):  # ... and defined nowhere else
         if name != "ig_host_pyr.inc":
             other = open(os.path.join(csrc, name)).read()
