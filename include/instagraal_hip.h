@@ -854,6 +854,35 @@ int ig_pre_pixels_fetch(ig_ctx* ctx, int64_t first, int64_t n, int32_t* col, int
 int ig_pre_clear(ig_ctx* ctx);
 int ig_pre_end(ig_ctx* ctx);
 
+/* ---- 4DN pairs text on the device: the lines of a chunk of bytes, their fields, the two decimal positions, the strand bits and the
+ * contig names (the rule, stated once: instagraal_amd/pairs_text.py).  A SESSION lives between ig_text_begin and
+ * ig_text_end (ig_destroy frees a live one) on a created handle; it needs no contacts and no state and changes nothing a move reads; no
+ * nuisance step or chain may be in flight.  ig_text_begin while a session is live is refused; ig_text_end without one does nothing.
+ *
+ * The vocabulary: name k is name_bytes[name_off[k] .. name_off[k + 1]) and has the id name_id[k]; where a name stands twice the later
+ * id wins.  A field is looked up by its exact bytes (64-bit FNV-1a into an open-addressing table at load <= 0.5, a hit confirmed by the
+ * bytes); an unknown name, the empty one included, is -1. */
+int ig_text_begin(ig_ctx* ctx, const uint8_t* name_bytes, const int64_t* name_off, const int32_t* name_id, int32_t n_names);
+/* One chunk of whole lines, 0 <= n_bytes <= 2^30 (refused on the argument beyond that): every line ends in '\n' except possibly the
+ * last; line j starts behind the j-th '\n'.  cols: the column indices of chr1, pos1, chr2, pos2, strand1, strand2 (0 .. 65535).  A
+ * line's status: 1 COMMENT (its first byte is '#'), 2 MALFORMED (fewer than max(cols[0..3]) + 1 fields, split at '\t' only), 3 DEFERRED
+ * (a position that is not exactly [+-]?[0-9]{1,18}: left to the caller), 0 DATA.  The lines from the first one that starts with
+ * "#columns:" on are not parsed (status COMMENT, counted nowhere but in `lines`).  A chunk that holds a '\r' or a byte >= 0x80 is not
+ * parsed at all: to_host is raised, nothing else of the result is defined and the call succeeds.
+ * scalars: {lines, data, comment, malformed, deferred, first_columns_line (-1: none), to_host, 0}.  ms (may be NULL): the times of the
+ * four passes {mark, scan, parse, compact}. */
+int ig_text_parse(ig_ctx* ctx, const uint8_t* bytes, int64_t n_bytes, const int32_t cols[6], int64_t scalars[8], float* ms);
+/* the last chunk's result: status [lines], line_start [lines + 1], contig id and position of both ends and the strand code (bit 0: end
+ * 1 on '-', bit 1: end 2) of the DATA lines in input order [data], the indices of the DEFERRED lines [deferred]; any pointer may be NULL */
+int ig_text_fetch(ig_ctx* ctx, uint8_t* status, int32_t* line_start, int32_t* c1, int64_t* p1, int32_t* c2, int64_t* p2, uint8_t* strands, int32_t* deferred);
+/* The DATA pairs of the last chunk from the session's device arrays straight into the live pre store (positions clipped to 0 ..
+ * 2^31 - 1, then what ig_pre_add_pairs does; scalars, ms: as there) or the live pairs session (a position outside 1 .. 2^31 - 1 as 0, a
+ * negative id as -1, the strand codes, then what ig_pairs_lift does without its per-pair outputs; scalars: as there).  Refused without
+ * the respective live session. */
+int ig_text_feed_pre(ig_ctx* ctx, int64_t scalars[8], float* ms);
+int ig_text_feed_pairs(ig_ctx* ctx, int64_t scalars[8]);
+int ig_text_end(ig_ctx* ctx);
+
 /* ---- the polished FASTA of the polish step: the composition of the input records and the output file stitched from their bases (the
  * rule, stated once: instagraal_amd/scaffold_polish.py).  A SESSION lives between ig_seq_begin and ig_seq_end (ig_destroy
  * frees a live one) on a created handle; it needs no contacts and no state and changes nothing a move reads; no nuisance step or chain

@@ -683,6 +683,33 @@ struct PreBuf {
     long long forms[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 };
 
+/* 4DN pairs text (ig_kernels_text.cuh): one session between ig_text_begin and ig_text_end, freed by free_text_buffers
+ * (ig_host_text.inc): the vocabulary and its table, the bytes of the last chunk, the per-run, per-block and per-line arrays of its
+ * parse (all grow-only, by the bytes and by the lines of the largest chunk so far) and the result of the last parse */
+struct TextBuf {
+    bool live = false, parsed = false;
+    int n_names = 0;
+    unsigned char* names = nullptr;        /* the names' bytes, one behind the other */
+    long long* name_off = nullptr;         /* [n_names + 1] */
+    int* name_id = nullptr;                /* [n_names] */
+    int* table = nullptr;                  /* [table_mask + 1] name indices, -1: free */
+    unsigned table_mask = 0;
+    unsigned char* bytes = nullptr;        /* [bytes_cap]: a multiple of 16, plus 16 */
+    unsigned short* nl_bits = nullptr;     /* [bytes_cap / 16] the newlines of every run of 16 bytes */
+    unsigned long long *blk = nullptr, *blk_incl = nullptr, *tot = nullptr; /* per block of 4096 bytes: the newlines, their scan and its scratch */
+    long long bytes_cap = 0;
+    unsigned long long *lblk = nullptr, *lblk_incl = nullptr, *ltot = nullptr; /* per block of 256 lines, [2][n]: DATA and DEFERRED lines likewise */
+    int* line_start = nullptr;             /* [line_cap + 1] */
+    unsigned char* status = nullptr;       /* [line_cap] */
+    int *raw_c[2] = {nullptr, nullptr}, *out_c[2] = {nullptr, nullptr}, *deferred = nullptr; /* [line_cap] per line, then compacted */
+    long long *raw_p[2] = {nullptr, nullptr}, *out_p[2] = {nullptr, nullptr};
+    unsigned char *raw_s = nullptr, *out_s = nullptr;
+    long long line_cap = 0;
+    unsigned* sc = nullptr;                /* TEXT_SC_WORDS */
+    long long n_bytes = 0, n_lines = 0, n_data = 0, n_deferred = 0; /* of the last parse */
+    bool to_host = false;
+};
+
 /* the polished FASTA of the polish step (ig_kernels_seq.cuh): one session between ig_seq_begin and ig_seq_end, freed by
  * free_seq_buffers (ig_host_seq.inc): the sequence bytes, the input's counts, the plan of the output file, one window of it */
 struct SeqPiece;
@@ -849,6 +876,7 @@ struct ig_ctx {
     PairsBuf pairs;
     PreBuf pre;
     SeqBuf seq;
+    TextBuf text;
     PyrBuf pyr;
     DebugRows debug_rows;
     DebugRows debug_zoom; /* the last ig_debug_zoom_coarsen's result (ig_debug_zoom_fetch) */

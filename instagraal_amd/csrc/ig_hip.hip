@@ -6,7 +6,7 @@
  *
  * One translation unit; the device code lives in the ig_kernels_*.cuh parts included below, the host side (handles, uploads, the
  * launch sequences, the extern "C" entry points) in the ig_host_*.inc parts: core, upload; genome and rows, the layers the reports
- * on the current genome share; map, law, junc, lift, join, emap, place, orient, bal, gap, one per report; edit, the segment edits; cutjoin, the cut and join scores; pairs, the read pairs lifted onto the genome; pre, the input folder from a FASTA and read pairs; seq, the polished FASTA of the polish step; pyr, the pyramid's levels; balsnap, the balancing's rows from a built map; batch, nuis, debug.
+ * on the current genome share; map, law, junc, lift, join, emap, place, orient, bal, gap, one per report; edit, the segment edits; cutjoin, the cut and join scores; pairs, the read pairs lifted onto the genome; pre, the input folder from a FASTA and read pairs; seq, the polished FASTA of the polish step; text, 4DN pairs text parsed on the device; pyr, the pyramid's levels; balsnap, the balancing's rows from a built map; batch, nuis, debug.
  *
  * A batch of W moves (CL:1401-1465 each) is one launch sequence on one stream, no host round trip inside:
  *   k_gather        O(N)            local fragment lists of the touched contigs, uniq-mutation lists, flags
@@ -39,7 +39,7 @@
  * k_edit_zero_delta, k_edit_commit (4.23); the cut and join scores: k_cut_span, k_cut_zero, k_cj_vk, k_cj_pairs_emit, k_cj_join,
  * k_cj_contig_zero, k_cj_join_zero (4.24); the read pairs lifted onto the genome: k_pairs_lift, k_pairs_emit, k_pairs_law (4.25); the input
  * folder from a FASTA and read pairs: k_pre_sites, k_pre_marks, k_pre_popc, k_pre_cuts, k_pre_frags, k_pre_assign, k_pre_emit (4.26); the polished FASTA
- * of the polish step: k_seq_composition, k_seq_stitch (4.27); the balancing's rows from a built map: k_balsnap_emit, k_balsnap_gather (4.29).
+ * of the polish step: k_seq_composition, k_seq_stitch (4.27); 4DN pairs text: k_text_mark, k_text_lines, k_text_parse, k_text_compact, k_text_convert (4.30); the balancing's rows from a built map: k_balsnap_emit, k_balsnap_gather (4.29).
  *
  * Environment knobs (tests, fault injection and tuning only; the table in INTEGRATION.md section 4 is the reference): IG_BATCH_W, IG_WINDOW
  * (widths), IG_POOL_ENTRIES, IG_WIDE_LISTS, IG_NO_HOST_FLAG, IG_POISON_ALLOC / IG_POISON_ONLY (force the rare paths), IG_SCREEN,
@@ -79,10 +79,11 @@
 #include "ig_kernels_pairs.cuh"
 #include "ig_kernels_pre.cuh"
 #include "ig_kernels_seq.cuh"
+#include "ig_kernels_text.cuh"
 #include "ig_kernels_pyr.cuh"
 #include "ig_kernels_balsnap.cuh"
 
-/* ================================================================== host side (one translation unit, twenty-six parts) */
+/* ================================================================== host side (one translation unit, twenty-seven parts) */
 #include "ig_host_core.inc"
 #include "ig_host_upload.inc"
 #include "ig_host_genome.inc"
@@ -104,6 +105,7 @@
 #include "ig_host_pairs.inc"
 #include "ig_host_pre.inc"
 #include "ig_host_seq.inc"
+#include "ig_host_text.inc"
 #include "ig_host_pyr.inc"
 #include "ig_host_balsnap.inc"
 #include "ig_host_batch.inc"

@@ -18,6 +18,7 @@ static void free_cutjoin_buffers(ig_ctx* c);  /* ig_host_cutjoin.inc */
 static void free_pairs_buffers(ig_ctx* c);    /* ig_host_pairs.inc */
 static void free_pre_buffers(ig_ctx* c);      /* ig_host_pre.inc */
 static void free_seq_buffers(ig_ctx* c);      /* ig_host_seq.inc */
+static void free_text_buffers(ig_ctx* c);     /* ig_host_text.inc */
 static void free_pyr_buffers(ig_ctx* c);      /* ig_host_pyr.inc */
 static void flush_pending_sums(ig_ctx* c); /* behind a decisively accepted nuisance step: see k_nuis_promote */
 
@@ -422,6 +423,7 @@ extern "C" void ig_destroy(ig_ctx* c)
     free_pairs_buffers(c);
     free_pre_buffers(c);
     free_seq_buffers(c);
+    free_text_buffers(c);
     free_pyr_buffers(c);
     hipFree(c->st_block);
     hipFree(c->tab.dist);

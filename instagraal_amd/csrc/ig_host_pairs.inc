@@ -191,8 +191,9 @@ extern "C" int ig_pairs_begin(ig_ctx* c, const int32_t* src_rowptr, int32_t n_co
 
 /* One chunk: piece by piece through the staging arrays.  ms (may be null): the kernel's time, summed over the pieces, goes to
  * ms[PAIRS_P_LIFT].  On an error behind the first launch the store is what it was before the call. */
-static int pairs_lift_impl(ig_ctx* c, const char* who, const int32_t* c1, const int32_t* p1, const int32_t* c2, const int32_t* p2, const uint8_t* strands, long long n,
-                           int32_t* const out_i[6], uint8_t* const out_b[3], long long scalars[8], LiftTimer& timer)
+template <class Stage>
+static int pairs_lift_staged(ig_ctx* c, const char* who, bool strands, long long n, Stage stage, int32_t* const out_i[6], uint8_t* const out_b[3], long long scalars[8],
+                             LiftTimer& timer)
 {
     PairsBuf& p = c->pairs;
     const bool want_out = out_b[2] != nullptr;
@@ -202,11 +203,9 @@ static int pairs_lift_impl(ig_ctx* c, const char* who, const int32_t* c1, const 
     unsigned long long h_sc[PAIRS_SC_WORDS] = {0};
     h_sc[PAIRS_SC_CURSOR] = (unsigned long long)before;
     HIPCK(hipMemcpyAsync(p.sc, h_sc, sizeof(h_sc), hipMemcpyHostToDevice, c->stream));
-    const int32_t* in[4] = {c1, p1, c2, p2};
     for (long long o = 0; o < n; o += PAIRS_PIECE) {
         const long long m = std::min<long long>(PAIRS_PIECE, n - o);
-        for (int k = 0; k < 4; k++) HIPCK(hipMemcpyAsync(p.in[k], in[k] + o, (size_t)m * sizeof(int), hipMemcpyHostToDevice, c->stream));
-        if (strands) HIPCK(hipMemcpyAsync(p.in_strands, strands + o, (size_t)m, hipMemcpyHostToDevice, c->stream));
+        if (stage(o, m)) return -1; /* the pairs o .. o + m - 1 into the staging arrays: a copy from the host, or ig_text_feed_pairs' conversion on the device */
         PairsOut out = {p.out_i[0], p.out_i[1], p.out_i[2], p.out_i[3], p.out_i[4], p.out_i[5], p.out_b[0], p.out_b[1], want_out ? p.out_b[2] : nullptr};
         const PairsStore store = {p.ends, p.unit, p.flag};
         timer.begin();
@@ -231,6 +230,18 @@ static int pairs_lift_impl(ig_ctx* c, const char* who, const int32_t* c1, const 
     scalars[5] = p.size;
     scalars[6] = scalars[7] = 0;
     return 0;
+}
+
+static int pairs_lift_impl(ig_ctx* c, const char* who, const int32_t* c1, const int32_t* p1, const int32_t* c2, const int32_t* p2, const uint8_t* strands, long long n,
+                           int32_t* const out_i[6], uint8_t* const out_b[3], long long scalars[8], LiftTimer& timer)
+{
+    PairsBuf& p = c->pairs;
+    const int32_t* in[4] = {c1, p1, c2, p2};
+    return pairs_lift_staged(c, who, strands != nullptr, n, [&](long long o, long long m) -> int {
+        for (int k = 0; k < 4; k++) HIPCK(hipMemcpyAsync(p.in[k], in[k] + o, (size_t)m * sizeof(int), hipMemcpyHostToDevice, c->stream));
+        if (strands) HIPCK(hipMemcpyAsync(p.in_strands, strands + o, (size_t)m, hipMemcpyHostToDevice, c->stream));
+        return 0;
+    }, out_i, out_b, scalars, timer);
 }
 
 extern "C" int ig_pairs_lift(ig_ctx* c, const int32_t* c1, const int32_t* p1, const int32_t* c2, const int32_t* p2, const uint8_t* strands, int64_t n,

@@ -324,19 +324,14 @@ static int pre_reserve_piece(PreBuf& p, long long n)
     return 0;
 }
 
-/* One chunk of pairs: record (-1: unknown) and 1-based position of both ends.  The kept pairs are appended to the store; scalars: the
- * chunk's pairs_in, pairs_kept, end1_without_fragment, end2_without_fragment, ends_beyond_record, then the pairs stored in all, 0, 0.
- * ms (may be null): the assign kernel's time, summed over the pieces.  An earlier build's pixels are gone. */
-extern "C" int ig_pre_add_pairs(ig_ctx* c, const int32_t* c1, const int32_t* p1, const int32_t* c2, const int32_t* p2, int64_t n, int64_t scalars[8], float* ms)
+/* One chunk of n pairs behind the checks of its arguments: stage(o, m) enqueues the pairs o .. o + m - 1 into the staging arrays (a copy
+ * from the host, or ig_text_feed_pre's conversion on the device).  The kept pairs are appended to the store; scalars: the chunk's
+ * pairs_in, pairs_kept, end1_without_fragment, end2_without_fragment, ends_beyond_record, then the pairs stored in all, 0, 0.  ms (may
+ * be null): the assign kernel's time, summed over the pieces.  An earlier build's pixels are gone. */
+template <class Stage>
+static int pre_add_impl(ig_ctx* c, const char* who, long long n, int64_t scalars[8], float* ms, Stage stage)
 {
-    IG_JOIN(c);
-    HIPCK(hipSetDevice(c->device));
-    const char* who = "ig_pre_add_pairs";
-    if (pre_usable(c, who)) return -1;
     PreBuf& p = c->pre;
-    if (!p.digested) return fail("%s: nothing is digested (ig_pre_digest first)", who);
-    if (!scalars) return fail("%s: NULL output", who);
-    if (n < 0 || (n > 0 && (!c1 || !p1 || !c2 || !p2))) return fail("%s: bad arguments (%lld pairs)", who, (long long)n);
     pre_free_pixels(p);
     if (pre_grow_store(c, who, p.size + n)) return -1;
     if (pre_reserve_piece(p, std::min<long long>(std::max<long long>(n, 1), PRE_PIECE))) return -1;
@@ -344,11 +339,10 @@ extern "C" int ig_pre_add_pairs(ig_ctx* c, const int32_t* c1, const int32_t* p1,
     unsigned long long h_sc[PRE_SC_WORDS] = {0};
     h_sc[PRE_SC_CURSOR] = (unsigned long long)before;
     HIPCK(hipMemcpyAsync(p.sc, h_sc, sizeof(h_sc), hipMemcpyHostToDevice, c->stream));
-    const int32_t* in[4] = {c1, p1, c2, p2};
     LiftTimer timer(c, ms, 1);
     for (long long o = 0; o < n; o += PRE_PIECE) {
         const long long m = std::min<long long>(PRE_PIECE, n - o);
-        for (int k = 0; k < 4; k++) HIPCK(hipMemcpyAsync(p.in[k], in[k] + o, (size_t)m * sizeof(int), hipMemcpyHostToDevice, c->stream));
+        if (stage(o, m)) return -1;
         timer.begin();
         hipLaunchKernelGGL(k_pre_assign, dim3(lift_blocks(m)), dim3(PRE_THREADS), 0, c->stream, (const int*)p.in[0], (const int*)p.in[1], (const int*)p.in[2],
                            (const int*)p.in[3], m, (const long long*)p.rec_first, (const int*)p.len, p.R, (const int*)p.start, p.store, p.sc + PRE_SC_CURSOR,
@@ -371,6 +365,24 @@ extern "C" int ig_pre_add_pairs(ig_ctx* c, const int32_t* c1, const int32_t* p1,
     scalars[5] = p.size;
     scalars[6] = scalars[7] = 0;
     return 0;
+}
+
+/* One chunk of pairs from the host: record (-1: unknown) and 1-based position of both ends */
+extern "C" int ig_pre_add_pairs(ig_ctx* c, const int32_t* c1, const int32_t* p1, const int32_t* c2, const int32_t* p2, int64_t n, int64_t scalars[8], float* ms)
+{
+    IG_JOIN(c);
+    HIPCK(hipSetDevice(c->device));
+    const char* who = "ig_pre_add_pairs";
+    if (pre_usable(c, who)) return -1;
+    PreBuf& p = c->pre;
+    if (!p.digested) return fail("%s: nothing is digested (ig_pre_digest first)", who);
+    if (!scalars) return fail("%s: NULL output", who);
+    if (n < 0 || (n > 0 && (!c1 || !p1 || !c2 || !p2))) return fail("%s: bad arguments (%lld pairs)", who, (long long)n);
+    const int32_t* in[4] = {c1, p1, c2, p2};
+    return pre_add_impl(c, who, n, scalars, ms, [&](long long o, long long m) -> int {
+        for (int k = 0; k < 4; k++) HIPCK(hipMemcpyAsync(p.in[k], in[k] + o, (size_t)m * sizeof(int), hipMemcpyHostToDevice, c->stream));
+        return 0;
+    });
 }
 
 /* The pixels of the store: rows_build with the sum of the equal columns, into the session's own rows.  scalars: the six of

@@ -46,6 +46,7 @@ CUT_JOIN_PASSES = ("span", "scan", "zero", "count", "rowscan", "scatter", "sort_
 CUT_JOIN_LDS_PAIRS = 256  # CJ_LDS_PAIRS (csrc/ig_kernels_cutjoin.cuh): pairs up to which the join pass keeps its accumulators in LDS
 PAIRS_PASSES = ("lift",) + ASSEMBLY_CONTACTS_PASSES + ("law",)  # ig_debug_pairs_time
 PRE_DIGEST_PASSES = ("sites", "scan", "cuts", "fragments")  # ig_pre_digest
+TEXT_PASSES = ("mark", "scan", "parse", "compact")  # ig_text_parse
 SEQ_CLASSES = 8  # SEQ_NC (csrc/ig_kernels_seq.cuh): scaffold_polish.CLASSES
 CONTIG_ARRAYS = ("head_bin", "tail_bin", "n_sub", "length_bp")  # ig_join_scores_fetch: per linear contig
 MAX_CANDIDATES = 16
@@ -1128,6 +1129,70 @@ class Context:
 
     def pre_end(self):
         _ck(lib().ig_pre_end(self._h))
+
+    # ---- 4DN pairs text (the rule: pairs_text.py)
+    def text_begin(self, names):
+        """opens the session over the vocabulary ``names``: {contig name: id}"""
+        from . import pairs_text
+
+        b, off, ids = pairs_text.vocabulary(names)
+        b = np.ascontiguousarray(b, np.uint8)
+        _ck(lib().ig_text_begin(self._h, _p(b), _p(off), _p(ids), ids.size))
+
+    def text_parse(self, buf, cols=(1, 2, 3, 4, 5, 6), times=False):
+        """one chunk of whole lines (bytes or uint8) under the six column indices -> dict: ``counts`` (lines, data, comment, malformed,
+        deferred), ``first_columns_line``, ``to_host`` and with ``times`` ``ms`` (float32 [4]: ``TEXT_PASSES``); the arrays stay on the
+        device for ``text_fetch`` / ``text_feed_pre`` / ``text_feed_pairs``"""
+        a = np.frombuffer(buf, np.uint8) if isinstance(buf, (bytes, bytearray, memoryview)) else np.ascontiguousarray(buf, np.uint8).ravel()
+        cc = np.ascontiguousarray(cols, np.int32).ravel()
+        if cc.size != 6:
+            raise HipError("text_parse: six column indices (got %d)" % cc.size)
+        sc = np.zeros(8, np.int64)
+        ms = np.zeros(len(TEXT_PASSES), np.float32) if times else None
+        _ck(lib().ig_text_parse(self._h, _p(a) if a.size else None, a.size, _p(cc), _p(sc), _p(ms)))
+        out = dict(counts=dict(lines=int(sc[0]), data=int(sc[1]), comment=int(sc[2]), malformed=int(sc[3]), deferred=int(sc[4])),
+                   first_columns_line=int(sc[5]), to_host=bool(sc[6]))
+        if times:
+            out["ms"] = ms
+        return out
+
+    def text_fetch(self, res, only=None):
+        """the arrays of the last chunk, ``res`` being what ``text_parse`` returned for it -> ``res`` with ``status``, ``line_start``,
+        ``c1``, ``p1``, ``c2``, ``p2``, ``strands``, ``deferred`` added (``only``: the names wanted): the dict of ``pairs_text.parse_chunk``"""
+        if res["to_host"]:
+            return res
+        n, d, f = (res["counts"][k] for k in ("lines", "data", "deferred"))
+        shape = dict(status=(n, np.uint8), line_start=(n + 1, np.int32), c1=(d, np.int32), p1=(d, np.int64), c2=(d, np.int32), p2=(d, np.int64),
+                     strands=(d, np.uint8), deferred=(f, np.int32))
+        got = {k: np.zeros(s, t) for k, (s, t) in shape.items() if only is None or k in only}
+        g = lambda k: _p(got.get(k))  # noqa: E731
+        _ck(lib().ig_text_fetch(self._h, g("status"), g("line_start"), g("c1"), g("p1"), g("c2"), g("p2"), g("strands"), g("deferred")))
+        res.update(got)
+        return res
+
+    def text_feed_pre(self, times=False):
+        """the DATA pairs of the last chunk into the live ``pre`` store, without a round trip -> as ``pre_add_pairs``"""
+        from .pre import SCALARS
+
+        sc = np.zeros(8, np.int64)
+        ms = np.zeros(1, np.float32) if times else None
+        _ck(lib().ig_text_feed_pre(self._h, _p(sc), _p(ms)))
+        out = {k: int(sc[i]) for i, k in enumerate(SCALARS[:5])}
+        out["pairs_stored"] = int(sc[5])
+        if times:
+            out["ms"] = float(ms[0])
+        return out
+
+    def text_feed_pairs(self):
+        """the DATA pairs of the last chunk into the live pairs session, without a round trip -> the scalars of ``pairs_lift``"""
+        from .pairs_lift import SCALARS
+
+        sc = np.zeros(8, np.int64)
+        _ck(lib().ig_text_feed_pairs(self._h, _p(sc)))
+        return {k: int(v) for k, v in zip(SCALARS[:6], sc)}
+
+    def text_end(self):
+        _ck(lib().ig_text_end(self._h))
 
     # ---- the polished FASTA of the polish step (the rule: scaffold_polish.py)
     def seq_begin(self, seq, rec_off, rec_len):

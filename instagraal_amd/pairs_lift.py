@@ -26,7 +26,7 @@ n_edges - 2)``, counted per strand combination ``++ +- -+ --``; with ``flip_stra
 flipped (the read now lies on the other strand of the scaffold), without it the strands stay as read, as the reference leaves them.
 
 The text side (``read_pairs``, ``write_lifted_pairs``) parses and formats lines in Python and is bound by that; the arrays are the
-fast path."""
+fast path.  ``read_pairs_device`` is ``read_pairs`` with the parse on the device (the rule: ``pairs_text.py``), asked for by name."""
 from __future__ import annotations
 
 import gzip
@@ -363,6 +363,70 @@ def read_pairs(path, names, chunk_pairs=DEFAULT_CHUNK_PAIRS, with_lines=False):
         yield flush()
 
 
+def device_parse(ctx, feed=False):
+    """``pairs_text.walk``'s ``parse`` on an open text session of ``ctx`` (``Context.text_begin``): the four passes on the device, then
+    the arrays to the host -- or, with ``feed``, nothing but the scalars: the DATA pairs stay on the device for ``text_feed_pre`` /
+    ``text_feed_pairs``, and ``line_start`` and ``deferred`` come only where a line is deferred or starts with ``#columns:``"""
+    def parse(seg, cols):
+        res = ctx.text_parse(seg, cols)
+        if not feed:
+            return ctx.text_fetch(res)
+        if res["counts"]["deferred"] or res["first_columns_line"] >= 0:
+            return ctx.text_fetch(res, ("line_start", "deferred"))
+        res["deferred"] = ()
+        return res
+    return parse
+
+
+def feed_device(path, names, ctx, feed, add, chunk_bytes=None):
+    """A pairs file parsed on the device and fed to a live session of ``ctx`` without a round trip: ``feed()`` after every parsed
+    stretch (``Context.text_feed_pre`` / ``text_feed_pairs``), ``add(c1, p1, c2, p2, strands)`` (int64, uint8) for what Python had to
+    decide: the deferred lines that ``_parse`` takes and the chunks refused whole.  -> the malformed lines"""
+    from . import pairs_text
+
+    def late(rows):
+        if rows:
+            a = np.array(rows, np.int64).reshape(-1, 5)
+            add(a[:, 0].copy(), a[:, 1].copy(), a[:, 2].copy(), a[:, 3].copy(), a[:, 4].astype(np.uint8))
+
+    malformed = 0
+    ctx.text_begin(names)
+    try:
+        for ev in pairs_text.walk(path, names, device_parse(ctx, feed=True), chunk_bytes or pairs_text.DEFAULT_CHUNK_BYTES):
+            if ev[0] == "parsed":
+                res, seg, cols = ev[1:]
+                feed()  # (in front of the next parse: the session holds one chunk's result)
+                malformed += res["counts"]["malformed"]
+                recs = [_parse(parts, cols, names) for parts in pairs_text.deferred_lines(res, seg)]
+                malformed += sum(r is None for r in recs)
+                late([r for r in recs if r is not None])
+            elif ev[0] == "rows":
+                late(ev[1])
+                malformed += ev[2]
+    finally:
+        ctx.text_end()
+    return malformed
+
+
+def read_pairs_device(path, names, ctx, chunk_bytes=None):
+    """``read_pairs`` (without ``with_lines``) with the lines, fields, integers and names parsed on the device (``ig_text_parse``; the
+    rule: ``pairs_text.py``): the same yields chunk for chunk of bytes, a flush at every ``#columns:`` line.  ctx: a ``hip_lib.Context``
+    with no text session open; the session is this call's own."""
+    from . import pairs_text
+
+    ctx.text_begin(names)
+    try:
+        yield from pairs_text.read_pairs_bytes(path, names, device_parse(ctx), chunk_bytes or pairs_text.DEFAULT_CHUNK_BYTES)
+    finally:
+        ctx.text_end()
+
+
+def check_reader(reader):
+    if reader not in ("host", "device"):
+        raise ValueError("pairs: reader is \"host\" (the Python line loop) or \"device\" (pairs_text on the device), got %r" % (reader,))
+    return reader
+
+
 def read_header(path):
     """-> (format line, the other header lines kept, the columns line) as the reference's ``_write_lifted_pairs`` sorts them"""
     fmt, other, columns = "## pairs format v1.0", [], "#columns: " + " ".join(DEFAULT_COLUMNS)
@@ -387,7 +451,8 @@ def write_lifted_pairs(pairs_path, out_path, table, lift=None, chunk_pairs=DEFAU
     line, ``#sorted: none``, the other lines kept, ``#chromosomes:`` and ``#chromsize:`` of the scaffolds under their genome.fasta
     names (``assembly_contacts.scaffold_names``), the columns line; the kept pairs in input order, every other field as it was.
     lift: ``(c1, p1, c2, p2, strands) -> lifted`` (the device's, which also stores what it keeps, or None: ``lift_host``).  -> dict of the scalars plus ``malformed`` and
-    ``lines`` (data lines read)"""
+    ``lines`` (data lines read).  The lines are read by the Python reader whatever the other calls use: every field of every kept line is
+    written out again, and the output side is bound by gzip."""
     if table.get("names") is None:
         raise ValueError("pairs lift: the table has no contig names")
     names = ac.scaffold_names(table["scaffold_ids"])

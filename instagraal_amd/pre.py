@@ -324,7 +324,19 @@ def _clip32(p):
 def run_pre(fasta, pairs, enzymes, output_dir, device=True, plot=False, chunk_pairs=DEFAULT_CHUNK_PAIRS):
     """FASTA + pairs -> ``fragments_list.txt``, ``info_contigs.txt``, ``abs_fragments_contacts_weighted.txt`` in ``output_dir``; returns
     the scalars of ``SCALARS`` plus ``n_frags``, ``n_records`` and ``malformed_lines``.  ``device``: True (a handle of its own on device
-    0), a ``hip_lib.Context``, or False: the rule alone."""
+    0), a ``hip_lib.Context``, or False: the rule alone.  The pairs are read by the Python line loop (``pairs_lift.read_pairs``);
+    ``run_pre_reader`` is this call with the reader chosen."""
+    return run_pre_reader(fasta, pairs, enzymes, output_dir, "host", device, plot, chunk_pairs)
+
+
+def run_pre_reader(fasta, pairs, enzymes, output_dir, reader="host", device=True, plot=False, chunk_pairs=DEFAULT_CHUNK_PAIRS):
+    """``run_pre`` with the reader of the pairs text chosen: "host" (``pairs_lift.read_pairs``, the Python line loop) or "device": the
+    text is parsed by ``pairs_text`` -- on the device, which feeds the store without a round trip, or with ``device=False`` by the rule
+    on the host; the files and the dict are the same.  (``run_pre``'s own parameter list is pinned, so the choice lives here.)"""
+    from . import pairs_text
+
+    pairs_lift.check_reader(reader)
+    chunk_bytes = pairs_text.DEFAULT_CHUNK_BYTES
     enzymes = expand_enzymes(enzymes)
     records = read_fasta(fasta)
     check_records(records)
@@ -342,7 +354,7 @@ def run_pre(fasta, pairs, enzymes, output_dir, device=True, plot=False, chunk_pa
             dig = digest(records, enzymes)
             gc = gc_counts(records, dig)
             parts = []
-            for chunk in pairs_lift.read_pairs(pairs, names, chunk_pairs):
+            for chunk in pairs_lift.read_pairs(pairs, names, chunk_pairs) if reader == "host" else pairs_text.read_pairs_bytes(pairs, names, None, chunk_bytes):
                 malformed = chunk["malformed"]
                 parts.append(pixels_host(dig, chunk["c1"], chunk["p1"], chunk["c2"], chunk["p2"]))
             px = merge_pixels(parts, dig["n_frags"])
@@ -353,9 +365,16 @@ def run_pre(fasta, pairs, enzymes, output_dir, device=True, plot=False, chunk_pa
                 dig = ctx.pre_digest(enzymes)
                 dig["names"] = [n for n, _ in records]
                 gc = dig.pop("gc_count")
-                for chunk in pairs_lift.read_pairs(pairs, names, chunk_pairs):
-                    malformed = chunk["malformed"]
-                    ctx.pre_add_pairs(chunk["c1"].astype(np.int32), _clip32(chunk["p1"]), chunk["c2"].astype(np.int32), _clip32(chunk["p2"]))
+
+                def add(c1, p1, c2, p2, strands=None):
+                    ctx.pre_add_pairs(c1.astype(np.int32), _clip32(p1), c2.astype(np.int32), _clip32(p2))
+
+                if reader == "device":
+                    malformed = pairs_lift.feed_device(pairs, names, ctx, ctx.text_feed_pre, add, chunk_bytes)
+                else:
+                    for chunk in pairs_lift.read_pairs(pairs, names, chunk_pairs):
+                        malformed = chunk["malformed"]
+                        add(chunk["c1"], chunk["p1"], chunk["c2"], chunk["p2"])
                 px = ctx.pre_pixels()
             finally:
                 ctx.pre_end()

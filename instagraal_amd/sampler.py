@@ -1167,6 +1167,10 @@ class sampler:  # noqa: N801 - the reference's class name
 
     # ------------------------------------------------------- read pairs lifted
     contig_names = None  # {input contig name: id in S_o_A_sub_frags["id_c"]} (``simulation`` sets it): lets the pairs come by name
+    # how the calls that take a pairs PATH read it (``_pairs_load``): "host" (``pairs_lift.read_pairs``, the Python line loop) or "device"
+    # (the text parsed on the device and fed to the session without a round trip: ``pairs_text.py``).  An attribute and no keyword: the
+    # parameter lists of ``pairs_contacts``, ``pairs_balance``, ``write_pairs_zoom_levels`` and ``pairs_distance_law`` are pinned
+    pairs_reader = "host"
 
     def pairs_begin(self, reserve_pairs=0):
         """Opens a pairs session on the genome as it stands (``ig_pairs_begin``; the rule: ``pairs_lift.py``): the source table of
@@ -1214,12 +1218,15 @@ class sampler:  # noqa: N801 - the reference's class name
             raise ValueError("pairs: a session is open and its store would be lost: pairs_end() first, or pass pairs=None to build from what it holds")
         return self.pairs_begin()
 
-    def _pairs_load(self, pairs, chunk_pairs=None):
+    def _pairs_load(self, pairs, chunk_pairs=None, reader=None):
         """``pairs``: None (the open session's store as it is), a path (a 4DN pairs file, read chunk by chunk) or arrays ``(contig,
         pos1, contig2, pos2[, strands])``: a fresh session with them lifted (refused while one is open: ``_pairs_fresh``) -> the summed
-        scalars (plus ``malformed`` for a file)"""
+        scalars (plus ``malformed`` for a file).  ``reader``: how a file is read -- None: ``self.pairs_reader``; "host"
+        (``pairs_lift.read_pairs``) or "device" (the text parsed on the device and fed to the session without a round trip:
+        ``pairs_text.py``); the order in the store is unspecified either way"""
         from . import pairs_lift as pl
 
+        reader = pl.check_reader(self.pairs_reader if reader is None else reader)
         if pairs is None:
             if getattr(self, "_pairs", None) is None:
                 raise ValueError("pairs: no session is open (lift_pairs first, or give the pairs)")
@@ -1231,11 +1238,18 @@ class sampler:  # noqa: N801 - the reference's class name
                 if t["names"] is None:
                     raise ValueError("pairs: a pairs file names its contigs and this sampler has no contig_names")
                 malformed = 0
-                for ch in pl.read_pairs(pairs, t["names"], chunk_pairs or pl.DEFAULT_CHUNK_PAIRS):
-                    malformed = ch["malformed"]
-                    res = self.ctx.pairs_lift(ch["c1"], ch["p1"], ch["c2"], ch["p2"], ch["strands"], outputs=False)
+
+                def add(res):
                     for k in total:
                         total[k] += res[k]
+
+                if reader == "device":
+                    malformed = pl.feed_device(pairs, t["names"], self.ctx, lambda: add(self.ctx.text_feed_pairs()),
+                                               lambda c1, p1, c2, p2, strands: add(self.ctx.pairs_lift(c1, p1, c2, p2, strands, outputs=False)))
+                else:
+                    for ch in pl.read_pairs(pairs, t["names"], chunk_pairs or pl.DEFAULT_CHUNK_PAIRS):
+                        malformed = ch["malformed"]
+                        add(self.ctx.pairs_lift(ch["c1"], ch["p1"], ch["c2"], ch["p2"], ch["strands"], outputs=False))
                 total["malformed"] = malformed
             else:
                 res = self.ctx.pairs_lift(pl.contig_ids(t, pairs[0]), pairs[1], pl.contig_ids(t, pairs[2]), pairs[3], pairs[4] if len(pairs) > 4 else None, outputs=False)
@@ -1258,7 +1272,9 @@ class sampler:  # noqa: N801 - the reference's class name
         return zl.binnify(ac.chrom_sizes(t["table_sub"]), binsize)
 
     def pairs_contacts(self, pairs, binsize=None, units=None, balance=False):
-        """The map of read pairs at any resolution (``ig_pairs_pixels_build``): the pairs lifted onto the genome as it stands and
+        """(How a pairs FILE is read, here and in ``pairs_balance``, ``write_pairs_zoom_levels``, ``pairs_distance_law`` and
+        ``display_pairs_distance_law``: the attribute ``pairs_reader``, "host" or "device".)
+        The map of read pairs at any resolution (``ig_pairs_pixels_build``): the pairs lifted onto the genome as it stands and
         counted per pixel -- ``binsize`` in bp (the bins of ``zoom_levels.binnify``; a pair counts where it falls), or ``units`` "sub"
         (the positions), "bin" (the placed bins: the rows of info_frags.txt) or "scaffold".  ``pairs``: a path or arrays -- lifted in a
         session of the call's own, ended behind it, and REFUSED (ValueError) while a session is open, whose store it would discard -- or

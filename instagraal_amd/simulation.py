@@ -434,12 +434,13 @@ def _run_instagraal(hic_folder, reference_fa, output_folder=None, level=4, cycle
 
 def run_from_pairs(fasta, pairs, enzymes, output_folder, **run_kw):
     """FASTA + 4DN pairs -> assembly: ``pre.run_pre`` writes the three input files into ``<output_folder>/pre/`` (the digest, G+C and
-    the pixels on the device: DESIGN 4.26), then ``run_instagraal`` runs on that folder unchanged with ``fasta`` as the reference and
-    ``run_kw`` as its keywords.  Returns what ``run_instagraal`` returns."""
+    the pixels on the device: DESIGN 4.26; the keyword ``reader`` is ``pre.run_pre_reader``'s, "host" or "device": who parses the pairs text), then
+    ``run_instagraal`` runs on that folder unchanged with ``fasta`` as the reference and ``run_kw`` as its keywords.  Returns what
+    ``run_instagraal`` returns."""
     from . import pre
 
     folder = os.path.join(str(output_folder), "pre")
-    pre.run_pre(fasta, pairs, enzymes, folder)
+    pre.run_pre_reader(fasta, pairs, enzymes, folder, reader=run_kw.pop("reader", "host"))
     return run_instagraal(folder, str(fasta), output_folder=str(output_folder), **run_kw)
 
 
